@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — tree-evaluations/s of the SR fitness hot path on N MI355X (one process per GPU over RCCL).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Headline workload (BASELINE.json north_star / configs[2]): SymbolicRegression synthetic 10-var, GLOBAL population
 1 000 000 trees x 1024 datapoints, max_tree_len 64, funcs + - * /.  It fits one GPU (512 MB of trees), so N = 1 runs all
@@ -13,7 +13,14 @@ path: `tree_SR_fitness` over the rank's shard, inputs resident in HBM; the fitne
 With N > 1 and no torch.distributed environment, bench.py launches its N ranks itself (torch.distributed.run, one per
 GPU, backend nccl = RCCL) and fails loudly when fewer than N GPUs are visible.
 
-The same JSON line also carries
+A plain run sets up, warms up (PREWARM untimed passes, then W steps), times exactly K steps and prints one JSON line with
+the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step).
+--dump-outputs DIR writes what the last timed step computed (the fitness of every tree) to DIR/fitness.npy, finite values
+with 0 where a fitness is NaN or infinite, and that class per tree to DIR/fitness_nonfinite.npy (both float32); the
+inputs are the same in every run with the same arguments.
+
+With --full the same JSON line also carries cold_start, config.reference_op (the same steps through the reference's own
+operator), the stage split, the division modes, and
   configs1      BASELINE configs[1] (pop 100k PER GPU x 1024 datapoints, weak), same protocol: ms_per_step, tree-evals/s,
                 generation_ms (fitness + DefaultSelection + DefaultCrossover + DefaultMutation on one shard)
   generation_ms_sharded  one generation of the GLOBAL population: local fitness + all-gather of the fitness values +
@@ -32,6 +39,7 @@ import hashlib
 import json
 import os
 import socket
+import subprocess
 import sys
 import threading
 import time
@@ -50,10 +58,12 @@ DATAPOINTS = 1024
 VAR_LEN = 10
 GP_LEN = 64
 PREWARM = 40       # untimed passes in front of the warm-up steps: the device's clock ramp (see main)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs writes at most this much
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a torch.distributed environment: become the launcher of N ranks."""
+    """`python bench.py --gpus N` without a torch.distributed environment: run the launcher of N ranks as a child process and
+    leave with its exit status (a fresh process: this one may have opened the GPU runtime to count the devices)."""
     have = torch.cuda.device_count()
     share = os.environ.get("EVOGP_BENCH_SHARE_GPU", "0") == "1"
     if have < args.gpus and not share:
@@ -64,7 +74,8 @@ def self_launch(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)   # (killed by a signal: the shell's 128 + signal number)
 
 
 def sr_inputs(lo, pop, device):
@@ -177,10 +188,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--global-pop", type=int, default=GLOBAL_POP, help="trees of the headline workload, split over the ranks")
     ap.add_argument("--pop-per-gpu", type=int, default=POP_PER_GPU, help="trees per rank of the configs[1] line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: cold start, stage split, the reference's operator, roofline and VALU issue, "
+                         "division modes, shard model, configs[1], [3], [4], whole generations, other workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the fitness of every tree) to DIR/fitness.npy "
+                         "(0 where not finite) and DIR/fitness_nonfinite.npy (0 finite, 1 NaN, 2 +inf, 3 -inf)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline steps (profiling runs: every launch of the fitness kernels then has the headline's shape)")
+                    help="--full with the headline's own measurements only (profiling runs: every launch of the fitness kernels then has "
+                         "the headline's shape)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)  # does not return
@@ -263,7 +283,7 @@ def main():
 
     def timed_steps(forest, Xd, yd, warmup, steps, call=None):
         """W untimed + exactly K timed fitness passes, barrier + synchronize on both sides, max over ranks;
-        also the average duration of one call from a HIP event pair on the launch stream (this rank).
+        also the average duration of one call from a HIP event pair on the launch stream (this rank), and what the last pass returned.
         call: the pass (default Forest.SR_fitness, which hands the engine the forest's function mask)"""
         call = call or (lambda f, X_, y_: f.SR_fitness(X_, y_, True, "auto"))
         for _ in range(warmup):
@@ -272,11 +292,34 @@ def main():
         _lib.check(_lib.lib.evogp_hip_timer_begin(stream), "timer_begin")
         t0 = time.perf_counter()
         for _ in range(steps):
-            call(forest, Xd, yd)
+            last = call(forest, Xd, yd)
         ev_ms = ctypes.c_float(0)
         _lib.check(_lib.lib.evogp_hip_timer_end(stream, ctypes.byref(ev_ms)), "timer_end")
         barrier()
-        return max_over_ranks(time.perf_counter() - t0), ev_ms.value / steps
+        return max_over_ranks(time.perf_counter() - t0), ev_ms.value / steps, last
+
+    def dump_outputs(path, fitness):
+        """--dump-outputs: what a caller of the timed pass receives from the last step -- the fitness of every tree of the global
+        population, in tree order (the ranks' shards put together) -- as two finite float32 arrays of one entry per tree (4 MB each
+        at the headline's size; above DUMP_MAX_BYTES every k-th tree from the first on):
+          DIR/fitness.npy            the fitness where it is finite, 0 where it is not
+          DIR/fitness_nonfinite.npy  0 finite, 1 NaN, 2 +inf, 3 -inf (NaN: the tree is undefined on some row, e.g. 0 / 0)
+        Together they are the call's result (a NaN's sign and payload carry no meaning)."""
+        part = fitness.detach().cpu().numpy().astype(np.float32, copy=False)
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+            part = np.concatenate(parts)
+        trees = len(part)
+        stride = -(-2 * part.nbytes // DUMP_MAX_BYTES)
+        part = part[::stride]
+        kind = np.select([np.isnan(part), np.isposinf(part), np.isneginf(part)], [1, 2, 3], 0).astype(np.float32)
+        if rank == 0:
+            os.makedirs(path, exist_ok=True)
+            np.save(os.path.join(path, "fitness.npy"), np.where(kind == 0, part, np.float32(0)).astype(np.float32))
+            np.save(os.path.join(path, "fitness_nonfinite.npy"), kind)
+        return {"fitness": {"files": ["fitness.npy", "fitness_nonfinite.npy"], "dtype": "float32", "trees": trees,
+                            "every_kth_tree": stride, "nan": int((kind == 1).sum()), "inf": int((kind >= 2).sum())}}
 
     # ---- headline: the global population, split over the ranks ------------------------------------------------------
     P = args.global_pop
@@ -288,14 +331,59 @@ def main():
     # 1-4 of a fresh process take 1.28 ms, 5-9 1.23, 10-19 1.18, every later one 1.14): the W warm-up steps the driver asks for
     # (5) end inside that ramp.  PREWARM untimed passes of the same step precede them, so that W + K measure the state a run of
     # thousands of generations is in; the count is reported in the JSON line (`device_prewarm_calls`).
-    # (for the record, the same W + K steps are timed once BEFORE those passes: `cold_start.ms_per_step` in the JSON line is what a
+    # (for the record, --full times the same W + K steps once BEFORE those passes: `cold_start.ms_per_step` in the JSON line is what a
     # process that has done nothing else yet measures)
-    cold_elapsed, _ = timed_steps(forest, Xd, yd, args.warmup, args.steps)
+    if args.full:
+        cold_elapsed, _, _ = timed_steps(forest, Xd, yd, args.warmup, args.steps)
     for _ in range(PREWARM):
         forest.SR_fitness(Xd, yd, True, "auto")
     torch.cuda.synchronize()
-    elapsed, call_ms = timed_steps(forest, Xd, yd, args.warmup, args.steps)
+    elapsed, call_ms, fitness = timed_steps(forest, Xd, yd, args.warmup, args.steps)
     all_nodes = sum_over_ranks(total_nodes)
+    dumped = dump_outputs(args.dump_outputs, fitness) if args.dump_outputs else None
+    del fitness
+
+    def headline_line():
+        """the fields of the line a plain run prints: the headline alone"""
+        out = {
+            "metric": "tree_evals_per_s",
+            "value": float(P) * DATAPOINTS * args.steps / elapsed,
+            "unit": "tree-evals/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1000.0,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic" if not share_gpu else "synthetic; FUNCTIONAL CHECK ONLY: ranks share a GPU over gloo",
+            "device_prewarm_calls": PREWARM,
+            "config": {
+                "workload": f"BASELINE north_star / configs[2] shape: SymbolicRegression synthetic 10-var, GLOBAL pop={P} x 1024 datapoints, "
+                            "max_tree_len=64, funcs + - * /, one tree_SR_fitness pass over every rank's shard per step",
+                "global_pop": P, "pop_per_gpu": pop, "datapoints": DATAPOINTS, "var_len": VAR_LEN, "max_tree_len": GP_LEN,
+                "mean_tree_len": all_nodes / P, "sharding": f"trees x{world} (contiguous shards, tree-index offset), no data-path collective in the step",
+                "ranks": world, "backend": backend,
+                # (the timed K steps follow PREWARM untimed passes -- the device's clock ramp --; --full also times the same W + K steps
+                # of a fresh process: cold_start.ms_per_step)
+                "device_prewarm_calls": PREWARM, "ms_per_step_after_prewarm": elapsed / args.steps * 1000.0,
+            },
+            "node_evals_per_s": float(all_nodes) * DATAPOINTS * args.steps / elapsed,
+        }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line()), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below ---------------------------------------------------------------------------------------
     # the same steps once more with per-stage events inside the call (compiler | interpreter | follow-ups): the duration of the
     # dominant kernel itself.  Kept out of the timed region above.
     _lib.check(_lib.lib.evogp_hip_debug_profile(1), "profile on")
@@ -311,7 +399,7 @@ def main():
     # through: same protocol, right behind the headline's
     for _ in range(3):
         reference_op(forest, Xd, yd)
-    ref_elapsed, ref_call_ms = timed_steps(forest, Xd, yd, args.warmup, args.steps, call=reference_op)
+    ref_elapsed, ref_call_ms, _ = timed_steps(forest, Xd, yd, args.warmup, args.steps, call=reference_op)
     torch.cuda.synchronize()
     ref_record_bytes = int(evogp_amd.program_buffer_bytes())
     ref_same = bool(torch.equal(reference_op(forest, Xd, yd).view(torch.int32), forest.SR_fitness(Xd, yd, True, "auto").view(torch.int32)))
@@ -382,7 +470,6 @@ def main():
             if emitted:
                 return
             emitted.append(True)
-        evals = float(P) * DATAPOINTS * args.steps
         kernel_s = stage_ms["interpreter"] / 1e3 if stage_ms["calls"] else call_ms / 1e3
         alg_bytes = 6.0 * total_nodes + 2.0 * pop + 4.0 * DATAPOINTS * (VAR_LEN + 1) + 4.0 * pop  # SURVEY.md §8d, this rank's launch
         achieved = alg_bytes / kernel_s / 1e9
@@ -400,38 +487,18 @@ def main():
                                     f"this is {source_sha()} / {pop}: not quoted")
             except Exception:
                 pass
-        out = {
-            "metric": "tree_evals_per_s",
-            "value": evals / elapsed,
-            "unit": "tree-evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1000.0,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic" if not share_gpu else "synthetic; FUNCTIONAL CHECK ONLY: ranks share a GPU over gloo",
-            "device_prewarm_calls": PREWARM,
-            "cold_start": {"ms_per_step": cold_elapsed / args.steps * 1e3,
-                           "what": "the same W warm-up + K timed steps run once before the untimed passes: a fresh process, device clocks still ramping"},
-            "config": {
-                "workload": f"BASELINE north_star / configs[2] shape: SymbolicRegression synthetic 10-var, GLOBAL pop={P} x 1024 datapoints, "
-                            "max_tree_len=64, funcs + - * /, one tree_SR_fitness pass over every rank's shard per step",
-                "global_pop": P, "pop_per_gpu": pop, "datapoints": DATAPOINTS, "var_len": VAR_LEN, "max_tree_len": GP_LEN,
-                "mean_tree_len": all_nodes / P, "sharding": f"trees x{world} (contiguous shards, tree-index offset), no data-path collective in the step",
-                "ranks": world, "backend": backend,
-                # (both numbers: the timed K steps follow PREWARM untimed passes -- the device's clock ramp --; the same W + K steps of a
-                # fresh process are cold_start.ms_per_step)
-                "device_prewarm_calls": PREWARM, "ms_per_step_after_prewarm": elapsed / args.steps * 1000.0, "ms_per_step_fresh_process": cold_elapsed / args.steps * 1e3,
-                # the same K steps through the reference's own operator (no function mask): what a drop-in under the reference's unchanged Python runs
-                "ms_per_step_reference_op": ref_elapsed / args.steps * 1000.0,
-                "reference_op": {"op": "torch.ops.evogp_cuda.tree_SR_fitness", "ms_per_step": ref_elapsed / args.steps * 1000.0, "call_ms_events": ref_call_ms,
-                                 "gap_vs_masked_call": ref_elapsed / elapsed - 1.0, "record_buffer_bytes": ref_record_bytes,
-                                 "fitness_words_equal_masked_call": ref_same},
-            },
-            "node_evals_per_s": float(all_nodes) * DATAPOINTS * args.steps / elapsed,
+        out = headline_line()
+        out["cold_start"] = {"ms_per_step": cold_elapsed / args.steps * 1e3,
+                             "what": "the same W warm-up + K timed steps run once before the untimed passes: a fresh process, device clocks still ramping"}
+        out["config"].update({
+            "ms_per_step_fresh_process": cold_elapsed / args.steps * 1e3,
+            # the same K steps through the reference's own operator (no function mask): what a drop-in under the reference's unchanged Python runs
+            "ms_per_step_reference_op": ref_elapsed / args.steps * 1000.0,
+            "reference_op": {"op": "torch.ops.evogp_cuda.tree_SR_fitness", "ms_per_step": ref_elapsed / args.steps * 1000.0, "call_ms_events": ref_call_ms,
+                             "gap_vs_masked_call": ref_elapsed / elapsed - 1.0, "record_buffer_bytes": ref_record_bytes,
+                             "fitness_words_equal_masked_call": ref_same},
+        })
+        out.update({
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic, "traffic_call": traffic_call, "traffic_note": traffic_note,
@@ -446,7 +513,7 @@ def main():
                         "kernel_ms: HIP events around the interpreter launch inside the call (a second pass of the same steps); "
                         "call_ms: event pair around the timed steps (compiler + interpreter + follow-up launches)",
             },
-        }
+        })
         out.update(extras)
         if with_cpu_baseline and not args.no_cpu_baseline and world == 1 and not args.headline_only:
             try:
@@ -562,10 +629,10 @@ def main():
         pop1 = args.pop_per_gpu
         forest1, _, _, _, _ = sr_inputs(rank * pop1, pop1, device)
         nodes1 = int(forest1.batch_subtree_size[:, 0].to(torch.int64).sum())
-        e1, call1_ms = timed_steps(forest1, Xd, yd, args.warmup, args.steps)
+        e1, call1_ms, _ = timed_steps(forest1, Xd, yd, args.warmup, args.steps)
         for _ in range(3):
             reference_op(forest1, Xd, yd)
-        e1_ref, _ = timed_steps(forest1, Xd, yd, args.warmup, args.steps, call=reference_op)
+        e1_ref, _, _ = timed_steps(forest1, Xd, yd, args.warmup, args.steps, call=reference_op)
         algo = GeneticProgramming(forest1, DefaultCrossover(), DefaultMutation(0.2, mdesc), DefaultSelection(0.3, elite_rate=0.01))
         gen_ms = []
         neg_inf = torch.full((pop1,), float("-inf"), dtype=torch.float32, device=device)

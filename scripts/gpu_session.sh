@@ -21,14 +21,14 @@ testsall)   # do not stop at the first failure
   timeout 2400 python -m pytest tests -m gpu -q > $OUT/${TAG}_01_pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/${TAG}_01_pytest_gpu.log
   tail -40 $OUT/${TAG}_01_pytest_gpu.log ;;
 bench)
-  timeout 900 python bench.py --steps 20 --warmup 3 > $OUT/${TAG}_02_bench.json 2> $OUT/${TAG}_02_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_02_bench.err
+  timeout 900 python bench.py --full --steps 20 --warmup 3 > $OUT/${TAG}_02_bench.json 2> $OUT/${TAG}_02_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_02_bench.err
   tail -3 $OUT/${TAG}_02_bench.err; cut -c1-1500 $OUT/${TAG}_02_bench.json ;;
 bench2)     # the N > 1 code path on this 1-GPU box: two ranks share the GPU over gloo (functional check, never a measurement)
-  EVOGP_BENCH_SHARE_GPU=1 timeout 600 python bench.py --gpus 2 --steps 3 --warmup 1 --global-pop 40000 --pop-per-gpu 20000 > $OUT/${TAG}_03_two_ranks_shared_gpu.log 2>&1
+  EVOGP_BENCH_SHARE_GPU=1 timeout 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --global-pop 40000 --pop-per-gpu 20000 > $OUT/${TAG}_03_two_ranks_shared_gpu.log 2>&1
   tail -2 $OUT/${TAG}_03_two_ranks_shared_gpu.log | cut -c1-600 ;;
 prof)
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o tr -- python $R/bench.py --steps 20 --warmup 3 --headline-only > $OUT/${TAG}_04_rocprof.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o tr -- python $R/bench.py --full --steps 20 --warmup 3 --headline-only > $OUT/${TAG}_04_rocprof.log 2>&1
   python $R/scripts/rocpd_summary.py $(find $OUT/prof_$TAG -name "*.db" | head -1) > $OUT/${TAG}_04_kernel_stats.md 2>&1
   rm -rf $OUT/prof_$TAG; cd $R
   tail -1 $OUT/${TAG}_04_rocprof.log | cut -c1-400; head -8 $OUT/${TAG}_04_kernel_stats.md | cut -c1-170 ;;
@@ -37,7 +37,7 @@ pmc)
   i=0
   for set in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU"; do
     i=$((i+1))
-    timeout 300 rocprofv3 --kernel-trace --pmc $set -d $OUT/pmc_$TAG$i -o pmc -- python $R/bench.py --steps 4 --warmup 1 --headline-only > $OUT/${TAG}_05_pmc$i.log 2>&1
+    timeout 300 rocprofv3 --kernel-trace --pmc $set -d $OUT/pmc_$TAG$i -o pmc -- python $R/bench.py --full --steps 4 --warmup 1 --headline-only > $OUT/${TAG}_05_pmc$i.log 2>&1
     python $R/scripts/rocpd_summary.py $(find $OUT/pmc_$TAG$i -name "*.db" | head -1) 2>&1 | grep -A400 "counter" | grep -i "counter\|---\|evogp" > $OUT/${TAG}_05_pmc$i.md
     rm -rf $OUT/pmc_$TAG$i
   done

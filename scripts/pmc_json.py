@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the three PMC passes of scripts/gpu_session.sh (FETCH_SIZE | WRITE_SIZE | SQ counters; bench.py --headline-only, so
+"""Turn the three PMC passes of scripts/gpu_session.sh (FETCH_SIZE | WRITE_SIZE | SQ counters; bench.py --full --headline-only, so
 every launch of the fitness kernels has the headline's shape) into profiles/pmc_latest.json.  The record carries the hash
 of the kernel sources and the trees per launch: bench.py quotes `traffic` only when both match what it runs.
 
@@ -40,7 +40,7 @@ def main():
     comp = next((k for k in t if "tc_compile_packed_kernel" in k), None) or next((k for k in t if "tc_compile_kernel" in k), None)
     out = {
         "what": "rocprofv3 --kernel-trace --pmc, one counter set per pass (FETCH_SIZE | WRITE_SIZE | SQ_*), command: python bench.py "
-                "--steps 4 --warmup 1 --headline-only; per-dispatch averages (scripts/rocpd_summary.py)",
+                "--full --steps 4 --warmup 1 --headline-only; per-dispatch averages (scripts/rocpd_summary.py)",
         "source_sha": bench.source_sha(),
         "pop_per_launch": line["config"]["pop_per_gpu"] if line else None,
         "files": [os.path.basename(p) for p in sys.argv[1:4]],

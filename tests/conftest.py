@@ -22,15 +22,12 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """The reference's own device code compiled for the host (oracle/_ref); skipped when absent."""
-    from oracle import build_ref
-    from oracle.pyoracle import Oracle, have_reference
+    """The reference's own device code compiled for the host (oracle/_ref), replayed from its recorded results
+    (tests/golden/reference_calls.json, written by tests/golden/make_reference_calls.py): its operators return the digest of the
+    reference's result for the given inputs (tests/reference_calls.py)."""
+    from reference_calls import RecordedReference
 
-    if build_ref.available():
-        build_ref.build()
-    if not have_reference():
-        pytest.skip("oracle/_ref/libevogp_ref.so not available (needs /root/reference at build time)")
-    return Oracle("reference")
+    return RecordedReference()
 
 
 @pytest.fixture

@@ -1,11 +1,12 @@
 """CPU: fuzz the plain-C oracle against the reference's own device code compiled for the host
-(oracle/_ref).  Skipped where /root/reference was never available (the GPU box uses the committed
-golden vectors instead)."""
+(oracle/_ref), as recorded in tests/golden/reference_calls.json (tests/reference_calls.py): every call below
+was made on the compiled reference with these same inputs, and its result is compared with the oracle's bit for bit."""
 import numpy as np
 import pytest
 
-from helpers import (ALLF, assert_forest_equal, avoid_middle_child_roots, bits, fbits, depth2leaf, middle_child_roots,
-                     random_crossover_indices, roulette_uniform)
+from helpers import (ALLF, avoid_middle_child_roots, depth2leaf, middle_child_roots, random_crossover_indices,
+                     roulette_uniform)
+from reference_calls import result_digest as digest
 
 
 @pytest.mark.parametrize("seed", range(120))
@@ -25,24 +26,23 @@ def test_fuzz_all_ops(oracle, reference, seed):
     op, cp = float(rng.uniform()), float(rng.uniform())
     pop = 200
     a = oracle.generate(pop, L, var_len, out_len, op, cp, keys, d2l, rou, cs)
-    b = reference.generate(pop, L, var_len, out_len, op, cp, keys, d2l, rou, cs)
-    assert_forest_equal(a, b, "generate", live_only=True)
+    assert reference.generate(pop, L, var_len, out_len, op, cp, keys, d2l, rou, cs) == digest("generate", a), "generate"
     X = rng.uniform(-3, 3, (pop, var_len)).astype(np.float32)
-    assert np.array_equal(fbits(oracle.evaluate(*a, X, out_len)), fbits(reference.evaluate(*a, X, out_len)))
+    assert reference.evaluate(*a, X, out_len) == digest("evaluate", oracle.evaluate(*a, X, out_len)), "evaluate"
     D = int(rng.choice([1, 7, 64, 100, 1025, 2048, 2500] if seed >= 24 else [1, 7, 64, 100]))   # beyond one 1024-row block: forward.cu:456-471
     Xd = rng.uniform(-3, 3, (D, var_len)).astype(np.float32)
     yd = rng.uniform(-3, 3, (D, out_len)).astype(np.float32)
     mse = bool(rng.integers(0, 2))
-    assert np.array_equal(fbits(oracle.sr_fitness(*a, Xd, yd, mse)), fbits(reference.sr_fitness(*a, Xd, yd, mse)))
+    assert reference.sr_fitness(*a, Xd, yd, mse) == digest("sr_fitness", oracle.sr_fitness(*a, Xd, yd, mse)), "sr_fitness"
     sizes = a[2][:, 0].astype(np.int64)
     idx = list(random_crossover_indices(rng, sizes, 400))
     idx[2] = avoid_middle_child_roots(a[1], a[2], idx[0], idx[2])       # undefined in the reference (helpers.middle_child_roots)
-    assert_forest_equal(oracle.crossover(*a, *idx), reference.crossover(*a, *idx), "crossover", live_only=True)
+    assert reference.crossover(*a, *idx) == digest("crossover", oracle.crossover(*a, *idx)), "crossover"
     new = oracle.generate(pop, L, var_len, out_len, op, cp, keys[::-1].copy(), depth2leaf(max(2, mlc - 2)), rou, cs)
     mi = (rng.integers(0, 1024, pop) % sizes).astype(np.int32)
     mi = avoid_middle_child_roots(a[1], a[2], np.arange(pop), mi)
     mi[:3] = [-1, 2000, 0]
-    assert_forest_equal(oracle.mutate(*a, mi, *new), reference.mutate(*a, mi, *new), "mutate", live_only=True)
+    assert reference.mutate(*a, mi, *new) == digest("mutate", oracle.mutate(*a, mi, *new)), "mutate"
 
 
 def test_sr_reduction_order_beyond_one_block(oracle, reference):
@@ -51,7 +51,7 @@ def test_sr_reduction_order_beyond_one_block(oracle, reference):
     a = oracle.generate(40, 64, 4, 1, 0.5, 0.5, [3, 4], depth2leaf(5), roulette_uniform([1, 2, 3]), [-1, 0.5, 2])
     X = rng.uniform(-2, 2, (2500, 4)).astype(np.float32)
     y = rng.uniform(-2, 2, (2500, 1)).astype(np.float32)
-    assert np.array_equal(fbits(oracle.sr_fitness(*a, X, y, True)), fbits(reference.sr_fitness(*a, X, y, True)))
+    assert reference.sr_fitness(*a, X, y, True) == digest("sr_fitness", oracle.sr_fitness(*a, X, y, True))
 
 
 @pytest.mark.parametrize("out_len,funcs", [(1, [1, 2, 3, 4]), (4, [0, 1, 2, 3, 4, 14, 18]), (10, [1, 2, 3, 4, 9, 10])])
@@ -62,23 +62,22 @@ def test_long_rows_and_multi_output(oracle, reference, out_len, funcs):
     d2l = depth2leaf(9, 0.05)
     rou = roulette_uniform(funcs)
     a = oracle.generate(pop, L, var_len, out_len, 0.4, 0.5, [9, out_len], d2l, rou, [-1.0, 0.5, 2.0])
-    b = reference.generate(pop, L, var_len, out_len, 0.4, 0.5, [9, out_len], d2l, rou, [-1.0, 0.5, 2.0])
-    assert_forest_equal(a, b, "generate", live_only=True)
+    assert reference.generate(pop, L, var_len, out_len, 0.4, 0.5, [9, out_len], d2l, rou, [-1.0, 0.5, 2.0]) == digest("generate", a), "generate"
     assert a[2][:, 0].max() > 300
     X = rng.uniform(-2, 2, (pop, var_len)).astype(np.float32)
-    assert np.array_equal(fbits(oracle.evaluate(*a, X, out_len)), fbits(reference.evaluate(*a, X, out_len)))
+    assert reference.evaluate(*a, X, out_len) == digest("evaluate", oracle.evaluate(*a, X, out_len)), "evaluate"
     for D in (64, 1025, 2048):
         Xd = rng.uniform(-2, 2, (D, var_len)).astype(np.float32)
         yd = rng.uniform(-2, 2, (D, out_len)).astype(np.float32)
         for mse in (True, False):
-            assert np.array_equal(fbits(oracle.sr_fitness(*a, Xd, yd, mse)), fbits(reference.sr_fitness(*a, Xd, yd, mse))), (D, mse)
+            assert reference.sr_fitness(*a, Xd, yd, mse) == digest("sr_fitness", oracle.sr_fitness(*a, Xd, yd, mse)), (D, mse)
     sizes = a[2][:, 0].astype(np.int64)
     idx = list(random_crossover_indices(rng, sizes, 300))
     idx[2] = avoid_middle_child_roots(a[1], a[2], idx[0], idx[2])
-    assert_forest_equal(oracle.crossover(*a, *idx), reference.crossover(*a, *idx), "crossover", live_only=True)
+    assert reference.crossover(*a, *idx) == digest("crossover", oracle.crossover(*a, *idx)), "crossover"
     new = oracle.generate(pop, L, var_len, out_len, 0.4, 0.5, [5, 5], depth2leaf(4), rou, [-1.0, 0.5, 2.0])
     mi = avoid_middle_child_roots(a[1], a[2], np.arange(pop), (rng.integers(0, 1024, pop) % sizes).astype(np.int32))
-    assert_forest_equal(oracle.mutate(*a, mi, *new), reference.mutate(*a, mi, *new), "mutate", live_only=True)
+    assert reference.mutate(*a, mi, *new) == digest("mutate", oracle.mutate(*a, mi, *new)), "mutate"
 
 
 def test_configs1_scale(oracle, reference):
@@ -88,15 +87,14 @@ def test_configs1_scale(oracle, reference):
 
     args = (100_000, 64, 10, 1, 0.5, 0.5, [42, 0], depth2leaf(6), roulette_uniform([1, 2, 3, 4]), [-1, 0, 1])
     a = oracle.generate(*args)
-    b = reference.generate(*args)
-    assert_forest_equal(a, b, "generate", live_only=True)
+    assert reference.generate(*args) == digest("generate", a), "generate"
     assert abs(float(a[2][:, 0].mean()) - 26.26) < 0.05
     X, y = c2_dataset()
     sub = tuple(x[:3000] for x in a)
-    assert np.array_equal(fbits(oracle.sr_fitness(*sub, X, y, True)), fbits(reference.sr_fitness(*sub, X, y, True)))
+    assert reference.sr_fitness(*sub, X, y, True) == digest("sr_fitness", oracle.sr_fitness(*sub, X, y, True)), "sr_fitness"
     rng = np.random.default_rng(3)
     idx = random_crossover_indices(rng, a[2][:, 0].astype(np.int64), 50_000)
-    assert_forest_equal(oracle.crossover(*a, *idx), reference.crossover(*a, *idx), "crossover", live_only=True)
+    assert reference.crossover(*a, *idx) == digest("crossover", oracle.crossover(*a, *idx)), "crossover"
 
 
 def test_middle_child_positions_are_the_intended_result_in_the_oracle(oracle):
