@@ -91,7 +91,7 @@ DIVR = ("SV", "VV", "CV")   # divisions by a variable through the launch's recip
 # address, two LDS reads
 NOPF_TWINS = tuple(f"{op}_{form}" for op in ("add", "sub", "mul") for form in FORMS) + ("push_c", "push_v") \
     + tuple(f"divip_{f}" for f in DIVIP) + tuple(f"divr_{f}" for f in DIVR)
-NHF = 37 + 2 * len(UNARY) + 8 + 2 + 4 + len(DIVIP) + 1 + 1 + len(DIVR) + len(NOPF_TWINS)  # handlers per flavour: ... + generic binary forms + generic unary S/V + if, acc, mo_begin, end_mo + in-place divisions + end_cls + swap + divisions by reciprocal columns
+NHF = 37 + 2 * len(UNARY) + 8 + 2 + 4 + len(DIVIP) + 1 + 1 + len(DIVR) + len(NOPF_TWINS) + 1  # handlers per flavour: ... + generic binary forms + generic unary S/V + if, acc, mo_begin, end_mo + in-place divisions + end_cls + swap + divisions by reciprocal columns + twins + nan_tree
 
 
 NOPF = False  # EVOGP_TC_GEN_NOPF=1: drop the operand prefetch (timing experiment, wrong results)
@@ -233,7 +233,8 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         hid[f"divr_{form}"] = nh + 14 + len(DIVIP) + 2 + i
     for i, name in enumerate(NOPF_TWINS):
         hid[name + "_np"] = nh + 14 + len(DIVIP) + 2 + len(DIVR) + i
-    assert NHF == nh + 14 + len(DIVIP) + 2 + len(DIVR) + len(NOPF_TWINS) and 2 * NHF * SLOT <= 65536
+    hid["nan_tree"] = nh + 14 + len(DIVIP) + 2 + len(DIVR) + len(NOPF_TWINS)
+    assert NHF == hid["nan_tree"] + 1 and 2 * NHF * SLOT <= 65536
     twin = [False]   # True while a no-prefetch twin is being generated (begin, entry, prefetch, wait_cur look at it)
 
     # cycle accounting (stats build only); counters live in the top operand-stack slot
@@ -1250,6 +1251,16 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         divip_stubs()
         divr_stubs()
         twin[0] = False
+        # NAN_TREE: the whole program of a tree the compiler proved NaN in every row (a NaN constant operand of + - * /, a literal x / 0:
+        # sr_tc.hip, compile_pack_arith).  The tree's result is what tree_done would make of its NaN sum -- THE quiet NaN in lane b of
+        # the batch's results, the tree counted as evaluated -- so pieces, the mean and the store treat it exactly as before
+        begin("nan_tree", fl)
+        a("s_set_gpr_idx_off")
+        a(f"s_mov_b32 s{T1}, 0x7fc00000")
+        a(f"s_mov_b32 m0, s{sB}")
+        a(f"s_bitset1_b64 s[{sOK}:{sOK + 1}], s{sB}")
+        a(f"v_writelane_b32 v7, s{T1}, m0")
+        a(f"s_branch {lab('next_tree')}")
     a(f".org {lab('hbase')}+{SLOT * 2 * NHF}")
 
     # In-place division bodies.  The gather forms above copy the operands into fixed banks because the division's temporaries

@@ -42,6 +42,10 @@ int evogp_hip_debug_long_compiler(int fast);
  * -1 = by the launch's trees per CU (DEFAULT: from 900 on; the environment variable EVOGP_TC_TWINS = 0 / 2 sets never / always before the
  * first call), 0 = never, 1 = always.  The fitness words do not depend on the choice (tests/test_gpu_tc_wide.py compares them bit for bit). */
 int evogp_hip_debug_twins(int mode);
+/* Whether the arithmetic line's packed compilers give a tree with a NaN constant operand of + - * / (a literal x / 0 among them) the one-word
+ * program NAN_TREE instead of its instructions: -1 = back to the default / the environment (EVOGP_TC_FOLD = 0 turns
+ * it off before the first call), 0 = off, 1 = on.  The fitness words do not depend on the choice (tests/test_gpu_fold.py). */
+int evogp_hip_debug_tc_fold(int mode);
 
 /* Handler histogram of the program records the most recent evogp_hip_sr_fitness call on the current device compiled:
  * device_hist[flavour * N + id] = number of program words with that handler among the first `pop` trees, N =
