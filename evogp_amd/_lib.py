@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # EVOGP_HIP_LIB: alternative build of the same engine (A/B benchmarking of compiler flags only)
 LIB_PATH = os.environ.get("EVOGP_HIP_LIB") or os.path.join(_HERE, "lib", "libevogp_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _vp = C.c_void_p
 _u = C.c_uint
@@ -52,6 +52,8 @@ PROTOTYPES = {
     "evogp_hip_set_sr_division": [C.c_int],
     "evogp_hip_get_sr_division": [],
     "evogp_hip_abi_version": [],
+    "evogp_hip_sr_gradient": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_const_step": [_u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them

@@ -63,4 +63,13 @@ constexpr int kCallScratchWords = kCallScratchChunkWords * kCallScratchChunks;
 unsigned *acquire_call_scratch(hipStream_t stream, unsigned **zero_for_next, hipError_t *err);
 void call_scratch_next_is_clean(hipStream_t stream);
 
+// Engine-owned device memory (evogp_hip_set_allocator: hipMalloc / hipFree or the caller's allocator), sr_tc.hip.
+hipError_t engine_alloc_shared(void **ptr, size_t bytes);
+void engine_free_shared(void *ptr);
+
+// Global tapes of the constant-gradient kernel (sr_grad.hip): does the engine hold any, and free those of device `dev` (the caller has
+// waited for the device; evogp_hip_release_workspaces).
+bool grad_workspaces_held();
+void release_grad_workspaces(int dev);
+
 } // namespace evogp

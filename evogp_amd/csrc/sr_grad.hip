@@ -1,0 +1,499 @@
+// sr_grad.hip — reverse-mode (adjoint) gradient of the symbolic-regression loss with respect to every constant node, and one
+// iteration of the per-tree constant descent that uses it (gfx950).
+//
+//   loss[t]    = (1/D) * sum_d sum_o err(y[d][o] - tree_t(X[d])_o)          err = square | abs  (what sr_fitness.hip returns)
+//   grad[t][i] = d loss[t] / d value[t][i]   for every CONST node i; exactly 0 at every other node and on the tail [len, gp_len)
+//
+// The forward semantics are run_general's (interp.hpp), both output modes; the derivative table is DESIGN.md's "Constant gradients".
+//
+// Work decomposition:
+//   * one workgroup owns one tree at a time (grid-stride over the population); wave 0 classifies it (classify_tree) and builds its
+//     OPERAND TABLE in LDS: for every function node the indices of the nodes whose pushed values it pops (a stack of node indices,
+//     walked once per tree in execution order -- the tree's structure is wave-uniform, so nothing of it is per row);
+//   * the W waves of the workgroup share the row tiles (64 rows each: wave w takes tiles w, w + W, ...).  Per tile a wave walks the
+//     tree in execution order (reverse prefix) writing every node's pushed value into a TAPE [node][lane], then in prefix order
+//     (parents before children) writing each operand's adjoint into a second [node][lane] array.  The adjoint slot of a CONST node
+//     is an accumulator instead (zeroed once per tree, only valid rows added), so after the last tile it holds the lane's sum over
+//     the wave's rows;
+//   * every CONST slot is reduced over the lanes with the fixed DPP butterfly (wave_sum), the waves' partials are added in wave
+//     order by one thread per node: no float atomics, bit-identical from run to run.
+//
+// The tapes live in LDS for rows of at most kGradLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in an engine-owned global
+// workspace (engine_alloc_shared) for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
+// column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.
+#include "interp.hpp"
+#include "launch.hpp"
+
+#include <mutex>
+#include <vector>
+
+namespace evogp {
+
+constexpr int kGradLdsLen = 64;      // rows up to this length keep their tapes in LDS
+constexpr int kGradMaxWaves = 4;     // waves per workgroup (row tiles of one tree)
+constexpr uint32_t kOpMask = 0xFFu;  // operand-table word: handler id in bits 0..7, "operand k is a CONST node" in bit 8 + k
+
+struct GradParams {
+    const float *value;
+    const int16_t *type;
+    const int16_t *size;
+    const float *X;  // [D][var_len]
+    const float *y;  // [D][out_len]
+    float *loss;     // [pop]
+    float *grad;     // [pop][gp_len]
+    float *tape;     // global tapes (rows longer than kGradLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
+    int pop, D, gp_len, var_len, out_len, use_mse;
+};
+
+__device__ inline float sign_of(float a) { return a > 0.0f ? 1.0f : a < 0.0f ? -1.0f : a == 0.0f ? 0.0f : a; }  // NaN stays NaN
+
+__device__ inline float binary_value(uint32_t op, float a, float b) {
+    if (op == H_ADD) return a + b;
+    if (op == H_SUB) return a - b;
+    if (op == H_MUL) return a * b;
+    if (op == H_DIV) return b == 0.0f ? __builtin_nanf("") : a / b;
+    return op_binary_other<false>(op, a, b);
+}
+
+// Partial adjoints of a binary node's operands: g is the adjoint of its result r = f(a, b).
+__device__ inline void binary_adjoint(uint32_t op, float a, float b, float r, float g, float &da, float &db) {
+    da = 0.0f; db = 0.0f;
+    switch (op) {
+    case H_ADD: da = g; db = g; break;
+    case H_SUB: da = g; db = -g; break;
+    case H_MUL: da = g * b; db = g * a; break;
+    case H_DIV: da = g / b; db = -g * r / b; break;  // (r is NaN when b == 0)
+    case H_BIN_OTHER + (F_LOOSE_DIV - F_LOOSE_DIV): {
+        const bool tiny = fabsf(b) <= kDelta;
+        const float d = tiny ? copysignf(kDelta, b) : b;
+        da = g / d;
+        db = tiny ? 0.0f : -g * r / d;
+        break;
+    }
+    case H_BIN_OTHER + (F_POW - F_LOOSE_DIV):
+        da = g * b * powf(a, b - 1.0f);
+        db = a > 0.0f ? g * r * logf(a) : 0.0f;
+        break;
+    case H_BIN_OTHER + (F_LOOSE_POW - F_LOOSE_DIV): {
+        const float m = fabsf(a);
+        da = (a == 0.0f && b == 0.0f) ? 0.0f : g * b * powf(m, b - 1.0f) * sign_of(a);
+        db = m > 0.0f ? g * r * logf(m) : 0.0f;
+        break;
+    }
+    case H_BIN_OTHER + (F_MAX - F_LOOSE_DIV): if (a >= b) da = g; else db = g; break;
+    case H_BIN_OTHER + (F_MIN - F_LOOSE_DIV): if (a <= b) da = g; else db = g; break;
+    default: break;  // LT GT LE GE, unknown ids: 0
+    }
+}
+
+__device__ inline float unary_adjoint(uint32_t op, float a, float r, float g) {
+    switch (op) {
+    case H_UN + (F_SIN - F_SIN): return g * cosf(a);
+    case H_UN + (F_COS - F_SIN): return -g * sinf(a);
+    case H_UN + (F_TAN - F_SIN): return g * (1.0f + r * r);
+    case H_UN + (F_SINH - F_SIN): return g * coshf(a);
+    case H_UN + (F_COSH - F_SIN): return g * sinhf(a);
+    case H_UN + (F_TANH - F_SIN): return g * (1.0f - r * r);
+    case H_UN + (F_LOG - F_SIN): return g / a;
+    case H_UN + (F_LOOSE_LOG - F_SIN): return a == 0.0f ? 0.0f : g / a;
+    case H_UN + (F_EXP - F_SIN): return g * r;
+    case H_UN + (F_INV - F_SIN): return a == 0.0f ? __builtin_nanf("") : -g * r * r;
+    case H_UN + (F_LOOSE_INV - F_SIN): return fabsf(a) <= kDelta ? 0.0f : -g * r * r;
+    case H_UN + (F_NEG - F_SIN): return -g;
+    case H_UN + (F_ABS - F_SIN): return g * sign_of(a);
+    case H_UN + (F_SQRT - F_SIN): return g * 0.5f / r;
+    case H_UN + (F_LOOSE_SQRT - F_SIN): return a == 0.0f ? 0.0f : g * 0.5f / r * sign_of(a);
+    default: return 0.0f;  // unknown ids
+    }
+}
+
+__device__ inline float grad_err(float diff, int use_mse) { return use_mse ? diff * diff : fabsf(diff); }
+
+// Dynamic LDS of one workgroup (16-byte aligned carve): op[L] kids[L] pay[L] stack[L] (u32), part[W][L], lpart[W], cls/len (2 words,
+// padded to 4), then, for LDS tapes, W x 2 x L x 64 floats.
+__host__ __device__ inline size_t grad_lds_head_words(int L, int W) { return (((size_t)4 * L + (size_t)W * L + W + 4) + 3) & ~(size_t)3; }
+
+template <bool MO>
+__global__ __launch_bounds__(kGradMaxWaves * 64) void sr_grad_kernel(GradParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t grad_lds[];
+    const int L = p.gp_len;
+    const int lane = threadIdx.x & 63;
+    const int w = uni((int)(threadIdx.x >> 6));
+    const int W = (int)(blockDim.x >> 6);
+    uint32_t *s_op = grad_lds, *s_kid = s_op + L, *s_pay = s_kid + L;
+    int *s_stk = (int *)(s_pay + L);
+    float *s_part = (float *)(s_stk + L);
+    float *s_lpart = s_part + (size_t)W * L;
+    int *s_meta = (int *)(s_lpart + W);
+    float *tape = p.tape ? p.tape + ((size_t)blockIdx.x * W + w) * 2 * L * kWave
+                         : (float *)(grad_lds + grad_lds_head_words(L, W)) + (size_t)w * 2 * L * kWave;
+    float *val = tape, *adj = tape + (size_t)L * kWave;
+    const int ntiles = (p.D + kWave - 1) / kWave;
+    const float inv_d = 1.0f / (float)p.D;
+
+    for (int t = blockIdx.x; t < p.pop; t += gridDim.x) {
+        const size_t row = (size_t)t * L;
+        // ---- wave 0: classify, decode, operand table ----
+        if (w == 0) {
+            int len = uni((int)p.size[row]);
+            len = len < 0 ? 0 : (len > L ? L : len);
+            const int cls = uni(classify_tree(p.type + row, p.value + row, len, MO, p.var_len, p.out_len, kMaxStack));
+            if (cls == TREE_OK) {
+                for (int i = lane; i < len; i += kWave) {
+                    const Decoded d = decode_node(p.type[row + i], p.value[row + i], MO, p.var_len, p.out_len);
+                    s_op[i] = d.op;
+                    s_pay[i] = d.pay;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                int h = 0;
+                for (int i = len - 1; i >= 0; --i) {
+                    const uint32_t op = (uint32_t)uni((int)s_op[i]);
+                    const int arity = op < H_ADD ? 0 : op < H_UN ? 2 : op < H_IF ? 1 : 3;
+                    uint32_t kid = 0, flags = 0;
+                    for (int k = 0; k < arity; ++k) {
+                        const int c = uni(s_stk[h - 1 - k]);
+                        kid |= (uint32_t)c << (10 * k);
+                        if ((uni((int)s_op[c]) & kOpMask) == H_CONST) flags |= 1u << (8 + k);
+                    }
+                    h -= arity;
+                    if (lane == 0) {
+                        s_stk[h] = i;
+                        s_kid[i] = kid;
+                        s_op[i] = op | flags;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    ++h;
+                }
+            }
+            if (lane == 0) { s_meta[0] = cls; s_meta[1] = len; }
+        }
+        __syncthreads();
+        const int cls = uni(s_meta[0]);
+        const int len = uni(s_meta[1]);
+        if (cls != TREE_OK) {  // malformed: NaN loss, zero row
+            for (int i = threadIdx.x; i < L; i += blockDim.x) p.grad[row + i] = 0.0f;
+            if (threadIdx.x == 0) p.loss[t] = __builtin_nanf("");
+            __syncthreads();
+            continue;
+        }
+        for (int i = 0; i < len; ++i)
+            if ((uni((int)s_op[i]) & kOpMask) == H_CONST) adj[i * kWave + lane] = 0.0f;
+
+        // adjoint of operand k of a node whose word is `opw`: stored, or added for a CONST operand (valid rows only)
+        auto put = [&](uint32_t opw, uint32_t kid, int k, float x, bool valid) {
+            const int c = (int)((kid >> (10 * k)) & 1023u);
+            float *q = adj + c * kWave + lane;
+            if (opw & (1u << (8 + k))) *q += valid ? x : 0.0f;
+            else *q = x;
+        };
+
+        float acc = 0.0f;
+        for (int tile = w; tile < ntiles; tile += W) {
+            const int d = tile * kWave + lane;
+            const bool valid = d < p.D;
+            const int dc = valid ? d : p.D - 1;
+            const float *xr = p.X + (size_t)dc * p.var_len;
+            v16f outs, gout;
+            if (MO) {
+#pragma unroll
+                for (int o = 0; o < kMaxOutRegs; ++o) outs[o] = 0.0f;
+            }
+            // ---- forward: execution order, every node's pushed value on the tape ----
+            for (int i = len - 1; i >= 0; --i) {
+                const uint32_t op = (uint32_t)uni((int)s_op[i]) & kOpMask;
+                float v;
+                if (op < H_ADD) {
+                    const uint32_t pay = (uint32_t)uni((int)s_pay[i]);
+                    v = op == H_CONST ? bits2f(pay) : xr[pay];
+                } else {
+                    const uint32_t kid = (uint32_t)uni((int)s_kid[i]);
+                    const float a = val[(kid & 1023u) * kWave + lane];
+                    float r, last;
+                    if (op < H_UN) {
+                        const float b = val[((kid >> 10) & 1023u) * kWave + lane];
+                        r = binary_value(op, a, b);
+                        last = b;
+                    } else if (op < H_IF) {
+                        r = op_unary<false>(op, a);
+                        last = a;
+                    } else {
+                        const float b = val[((kid >> 10) & 1023u) * kWave + lane], c = val[(kid >> 20) * kWave + lane];
+                        r = a > 0.0f ? b : c;
+                        last = c;
+                    }
+                    if (MO) {
+                        const uint32_t pay = (uint32_t)uni((int)s_pay[i]);
+                        if (pay != kNoOut) outs[pay] += r;
+                        v = last;
+                    } else {
+                        v = r;
+                    }
+                }
+                val[i * kWave + lane] = v;
+            }
+            // ---- loss and the adjoints of the outputs ----
+            float e = 0.0f, g0 = 0.0f;
+            if (!MO) {
+                const float pred = val[lane], yv = p.y[dc];
+                e = grad_err(yv - pred, p.use_mse);
+                const float diff = pred - yv;
+                g0 = valid ? (p.use_mse ? 2.0f * diff * inv_d : sign_of(diff) * inv_d) : 0.0f;
+            } else {
+                const float *yr = p.y + (size_t)dc * p.out_len;
+#pragma unroll
+                for (int o = 0; o < kMaxOutRegs; ++o) {
+                    gout[o] = 0.0f;
+                    if (o < p.out_len) {
+                        e += grad_err(yr[o] - outs[o], p.use_mse);
+                        const float diff = outs[o] - yr[o];
+                        gout[o] = valid ? (p.use_mse ? 2.0f * diff * inv_d : sign_of(diff) * inv_d) : 0.0f;
+                    }
+                }
+            }
+            acc += valid ? e : 0.0f;
+            // ---- reverse: prefix order, parents before children ----
+            {   // the root's pushed value: the prediction (single output) or nothing (multi-output: the outputs are the sums)
+                const uint32_t op0 = (uint32_t)uni((int)s_op[0]) & kOpMask;
+                const float x = MO ? 0.0f : g0;
+                if (op0 == H_CONST) adj[lane] += valid ? x : 0.0f;
+                else adj[lane] = x;
+            }
+            for (int i = 0; i < len; ++i) {
+                const uint32_t opw = (uint32_t)uni((int)s_op[i]);
+                const uint32_t op = opw & kOpMask;
+                if (op < H_ADD) continue;
+                const uint32_t kid = (uint32_t)uni((int)s_kid[i]);
+                const float g = adj[i * kWave + lane];
+                const float a = val[(kid & 1023u) * kWave + lane];
+                uint32_t pay = kNoOut;
+                if (MO) pay = (uint32_t)uni((int)s_pay[i]);
+                const bool through = !MO || pay != kNoOut;  // does the node's result r reach the loss?
+                float gr = g;
+                if (MO) gr = through ? gout[pay] : 0.0f;
+                if (op < H_UN) {
+                    const float b = val[((kid >> 10) & 1023u) * kWave + lane];
+                    float da = 0.0f, db = 0.0f;
+                    if (through) {
+                        const float r = MO ? binary_value(op, a, b) : val[i * kWave + lane];
+                        binary_adjoint(op, a, b, r, gr, da, db);
+                    }
+                    if (MO) db += g;  // the passed operand
+                    put(opw, kid, 0, da, valid);
+                    put(opw, kid, 1, db, valid);
+                } else if (op < H_IF) {
+                    float da = 0.0f;
+                    if (through) {
+                        const float r = MO ? op_unary<false>(op, a) : val[i * kWave + lane];
+                        da = unary_adjoint(op, a, r, gr);
+                    }
+                    if (MO) da += g;
+                    put(opw, kid, 0, da, valid);
+                } else {
+                    const bool take_b = a > 0.0f;
+                    float db = through && take_b ? gr : 0.0f, dcv = through && !take_b ? gr : 0.0f;
+                    if (MO) dcv += g;
+                    put(opw, kid, 0, 0.0f, valid);
+                    put(opw, kid, 1, db, valid);
+                    put(opw, kid, 2, dcv, valid);
+                }
+            }
+        }
+
+        // ---- reduce: lanes by the fixed butterfly, waves in wave order ----
+        for (int i = 0; i < len; ++i) {
+            if ((uni((int)s_op[i]) & kOpMask) != H_CONST) continue;
+            const float s = wave_sum(adj[i * kWave + lane]);
+            if (lane == 0) s_part[(size_t)w * L + i] = s;
+        }
+        {
+            const float s = wave_sum(acc);
+            if (lane == 0) s_lpart[w] = s;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < L; i += blockDim.x) {
+            float s = 0.0f;
+            if (i < len && (s_op[i] & kOpMask) == H_CONST)
+                for (int k = 0; k < W; ++k) s += s_part[(size_t)k * L + i];
+            p.grad[row + i] = s;
+        }
+        if (threadIdx.x == 0) {
+            float s = 0.0f;
+            for (int k = 0; k < W; ++k) s += s_lpart[k];
+            p.loss[t] = s / (float)p.D;
+        }
+        __syncthreads();  // the tables are rebuilt for the next tree
+    }
+}
+
+// ---- one iteration of the per-tree descent (evogp_hip_sr_const_step) ----------------------------------------------------------
+struct StepParams {
+    float *value;            // [pop][gp_len] current constants (only CONST words of the live prefix are written)
+    const int16_t *type;
+    const int16_t *size;
+    float *cand;             // [pop][gp_len] candidate forest (every word written when proposing)
+    float *loss;             // [pop] loss of the current forest
+    float *grad;             // [pop][gp_len] its gradient
+    const float *loss_cand;  // [pop] loss of the candidate forest (accepting)
+    const float *grad_cand;  // [pop][gp_len] its gradient
+    float *step;             // [pop] step length h_t
+    int pop, gp_len, multi, phase;
+};
+
+__device__ inline bool is_const_node(int type, bool multi) { return (multi ? (type & T_MASK) : type) == T_CONST; }
+
+__global__ __launch_bounds__(256) void sr_const_step_kernel(StepParams q) {
+    const int lane = threadIdx.x & 63;
+    const int t = uni((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    if (t >= q.pop) return;
+    const size_t row = (size_t)t * q.gp_len;
+    int len = uni((int)q.size[row]);
+    len = len < 0 ? 0 : (len > q.gp_len ? q.gp_len : len);
+    const bool multi = q.multi != 0;
+    if (q.phase & 1) {  // accept or reject the candidate whose gradient pass ran last
+        const float lc = q.loss_cand[t];
+        if (lc < q.loss[t]) {  // (NaN never accepts)
+            for (int i = lane; i < q.gp_len; i += kWave) {
+                if (i < len && is_const_node(q.type[row + i], multi)) q.value[row + i] = q.cand[row + i];
+                q.grad[row + i] = q.grad_cand[row + i];
+            }
+            if (lane == 0) { q.loss[t] = lc; q.step[t] = 2.0f * q.step[t]; }
+        } else if (lane == 0) {
+            q.step[t] = 0.5f * q.step[t];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (q.phase & 2) {  // propose c - h * g / |g|
+        float s = 0.0f;
+        for (int i = lane; i < q.gp_len; i += kWave) { const float g = q.grad[row + i]; s += g * g; }
+        const float norm = sqrtf(wave_sum(s));
+        const float l = q.loss[t], h = q.step[t];
+        const bool move = __builtin_isfinite(l) && l != 0.0f && __builtin_isfinite(norm) && norm != 0.0f;
+        for (int i = lane; i < q.gp_len; i += kWave) {
+            float v = q.value[row + i];
+            if (move && i < len && is_const_node(q.type[row + i], multi)) v = v - h * q.grad[row + i] / norm;
+            q.cand[row + i] = v;
+        }
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+// Global tapes of rows longer than kGradLdsLen: one buffer per stream (concurrent launches must not share one), grown outside stream
+// captures, never freed before evogp_hip_release_workspaces (a graph captured earlier may point at it).
+struct GradWorkspace { hipStream_t stream; void *buf; size_t bytes; };
+static std::mutex g_grad_mu;
+static std::vector<GradWorkspace> g_grad_ws[64];
+static std::vector<void *> g_grad_retired[64];
+
+static float *grad_workspace(hipStream_t stream, size_t bytes, int *rc) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(g_grad_mu);
+    auto &list = g_grad_ws[dev & 63];
+    GradWorkspace *ws = nullptr;
+    for (auto &e : list) if (e.stream == stream) ws = &e;
+    if (ws && ws->bytes >= bytes) return (float *)ws->buf;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        *rc = EVOGP_E_UNSUPPORTED;  // no allocation inside a capture: make one eager call of this shape on the stream first
+        return nullptr;
+    }
+    void *buf = nullptr;
+    hipError_t e = engine_alloc_shared(&buf, bytes);
+    if (e != hipSuccess || !buf) {
+        (void)hipGetLastError();
+        *rc = e != hipSuccess ? (int)e : (int)hipErrorOutOfMemory;
+        return nullptr;
+    }
+    if (ws) {
+        g_grad_retired[dev & 63].push_back(ws->buf);
+        ws->buf = buf;
+        ws->bytes = bytes;
+    } else {
+        list.push_back({stream, buf, bytes});
+    }
+    return (float *)buf;
+}
+
+bool grad_workspaces_held() {
+    std::lock_guard<std::mutex> lock(g_grad_mu);
+    for (int d = 0; d < 64; ++d) if (!g_grad_ws[d].empty() || !g_grad_retired[d].empty()) return true;
+    return false;
+}
+
+void release_grad_workspaces(int dev) {  // (the caller has waited for the device)
+    std::lock_guard<std::mutex> lock(g_grad_mu);
+    for (auto &e : g_grad_ws[dev & 63]) engine_free_shared(e.buf);
+    for (void *b : g_grad_retired[dev & 63]) engine_free_shared(b);
+    g_grad_ws[dev & 63].clear();
+    g_grad_retired[dev & 63].clear();
+}
+
+}  // namespace evogp
+
+using namespace evogp;
+
+extern "C" int evogp_hip_sr_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                     int use_mse, const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                     const float *labels, float *loss, float *grad, evogp_stream_t stream_) {
+    if (pop_size == 0 || data_points == 0 || gp_len == 0 || gp_len > (unsigned)kMaxStack || var_len == 0 || out_len == 0 ||
+        pop_size > 0x7FFFFFFFu || data_points > 0x7FFFFFFFu)
+        return EVOGP_E_BADARG;
+    if (!value || !type || !size || !variables || !labels || !loss || !grad) return EVOGP_E_NULLPTR;
+    if (out_len > (unsigned)kMaxOutRegs) return EVOGP_E_UNSUPPORTED;
+    const hipStream_t stream = (hipStream_t)stream_;
+    const DeviceInfo &dev = device_info();
+    GradParams p{};
+    p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.loss = loss; p.grad = grad;
+    p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len; p.out_len = (int)out_len;
+    p.use_mse = use_mse ? 1 : 0;
+    const int ntiles = (p.D + kWave - 1) / kWave;
+    const bool lds_tape = p.gp_len <= kGradLdsLen;
+    // Waves per workgroup: one when the population alone fills the chip, up to four (row tiles of one tree) when it does not.
+    const long fill = (long)dev.num_cus * 16;
+    int W = p.pop >= fill ? 1 : (ntiles < kGradMaxWaves ? ntiles : kGradMaxWaves);
+    size_t lds = grad_lds_head_words(p.gp_len, W) * 4;
+    long blocks;
+    if (lds_tape) {
+        lds += (size_t)W * 2 * p.gp_len * kWave * sizeof(float);
+        const long per_cu = (long)(dev.lds_per_cu / lds);
+        blocks = (long)dev.num_cus * (per_cu < 1 ? 1 : per_cu);
+    } else {
+        blocks = (long)dev.num_cus * 2 / W;  // 512 resident waves on a 256-CU device: 256 MiB of tapes at gp_len 1024
+    }
+    if (blocks > p.pop) blocks = p.pop;
+    if (!lds_tape) {
+        int rc = 0;
+        p.tape = grad_workspace(stream, (size_t)blocks * W * 2 * p.gp_len * kWave * sizeof(float), &rc);
+        if (!p.tape) return rc;
+    }
+    static std::once_flag attr_once;   // dynamic LDS beyond 64 KiB must be granted per kernel
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(attr_once, [] {
+        attr_err = hipFuncSetAttribute((const void *)sr_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (attr_err == hipSuccess)
+            attr_err = hipFuncSetAttribute((const void *)sr_grad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    if (attr_err != hipSuccess) return (int)attr_err;
+    if (p.out_len > 1) hipLaunchKernelGGL(sr_grad_kernel<true>, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
+    else hipLaunchKernelGGL(sr_grad_kernel<false>, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int evogp_hip_sr_const_step(unsigned pop_size, unsigned gp_len, unsigned out_len, int phase, float *value, const int16_t *type,
+                                       const int16_t *size, float *value_cand, float *loss, float *grad, const float *loss_cand,
+                                       const float *grad_cand, float *step, evogp_stream_t stream_) {
+    if (pop_size == 0 || gp_len == 0 || gp_len > (unsigned)kMaxStack || out_len == 0 || pop_size > 0x7FFFFFFFu || phase < 1 || phase > 3)
+        return EVOGP_E_BADARG;
+    if (!value || !type || !size || !value_cand || !loss || !grad || !step) return EVOGP_E_NULLPTR;
+    if ((phase & 1) && (!loss_cand || !grad_cand)) return EVOGP_E_NULLPTR;
+    StepParams q{};
+    q.value = value; q.type = type; q.size = size; q.cand = value_cand; q.loss = loss; q.grad = grad;
+    q.loss_cand = loss_cand; q.grad_cand = grad_cand; q.step = step;
+    q.pop = (int)pop_size; q.gp_len = (int)gp_len; q.multi = out_len > 1 ? 1 : 0; q.phase = phase;
+    const unsigned blocks = (pop_size + 3) / 4;
+    hipLaunchKernelGGL(sr_const_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, q);
+    return (int)hipGetLastError();
+}

@@ -233,6 +233,54 @@ Tensor tree_SR_fitness_masked(int64_t pop_size, int64_t data_points, int64_t gp_
 }
 
 // ---- extra ops (no counterpart in the reference) ------------------------------------------------------------------------
+// loss and d loss / d constant of every tree (include/evogp_hip.h evogp_hip_sr_gradient), validated like tree_SR_fitness
+std::tuple<Tensor, Tensor> tree_SR_gradient(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
+                                            const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                            const Tensor &labels) {
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    TORCH_CHECK(out_len > 0 && out_len <= 16, "out_len must be in range (0, 16], but got ", out_len);
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor loss = at::empty({pop_size}, value.options());
+    Tensor grad = at::empty({pop_size, gp_len}, value.options());
+    check_rc(evogp_hip_sr_gradient((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, use_mse ? 1 : 0,
+                                   value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), variables.data_ptr<float>(),
+                                   labels.data_ptr<float>(), loss.data_ptr<float>(), grad.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_gradient");
+    return {loss, grad};
+}
+
+// one iteration of the constant descent, in place (include/evogp_hip.h evogp_hip_sr_const_step); phase 2 ignores loss_cand / grad_cand
+void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tensor &type, const Tensor &size, Tensor value_cand, Tensor loss,
+                        Tensor grad, const Tensor &loss_cand, const Tensor &grad_cand, Tensor step) {
+    TORCH_CHECK(phase >= 1 && phase <= 3, "phase must be 1, 2 or 3, but got ", phase);
+    TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len);
+    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
+    const int64_t pop_size = value.size(0), gp_len = value.size(1);
+    check_sizes(pop_size, gp_len);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(value_cand, {pop_size, gp_len}, "value_cand", dev, at::kFloat);
+    check_tensor(loss, {pop_size}, "loss", dev, at::kFloat);
+    check_tensor(grad, {pop_size, gp_len}, "grad", dev, at::kFloat);
+    check_tensor(step, {pop_size}, "step", dev, at::kFloat);
+    if (phase & 1) {
+        check_tensor(loss_cand, {pop_size}, "loss_cand", dev, at::kFloat);
+        check_tensor(grad_cand, {pop_size, gp_len}, "grad_cand", dev, at::kFloat);
+    }
+    c10::DeviceGuard guard(dev);
+    check_rc(evogp_hip_sr_const_step((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_len, (int)phase, value.data_ptr<float>(),
+                                     type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), value_cand.data_ptr<float>(), loss.data_ptr<float>(),
+                                     grad.data_ptr<float>(), (phase & 1) ? loss_cand.data_ptr<float>() : nullptr,
+                                     (phase & 1) ? grad_cand.data_ptr<float>() : nullptr, step.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_const_step");
+}
+
 Tensor3 tree_generate_offset(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len,
                              double out_prob, double const_prob, const Tensor &keys, const Tensor &depth2leaf_probs,
                              const Tensor &roulette_funcs, const Tensor &const_samples, int64_t tree_index_offset) {
@@ -665,6 +713,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " -> (Tensor value, Tensor node_type, Tensor subtree_size)");
     m.def("tree_SR_fitness_masked(int pop_size, int data_points, int gp_len, int var_len, int out_len, bool use_mse, Tensor value,"
           " Tensor node_type, Tensor subtree_size, Tensor variables, Tensor labels, int kernel_type, int func_mask) -> Tensor");
+    m.def("tree_SR_gradient(int pop_size, int data_points, int gp_len, int var_len, int out_len, bool use_mse, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor grad)");
+    m.def("tree_SR_const_step(int phase, int out_len, Tensor(a!) value, Tensor node_type, Tensor subtree_size, Tensor(b!) value_cand,"
+          " Tensor(c!) loss, Tensor(d!) grad, Tensor loss_cand, Tensor grad_cand, Tensor(e!) step) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -688,4 +740,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("select_survivors", &select_survivors);
     m.impl("fitness_scores", &fitness_scores);
     m.impl("tournament_select", &tournament_select);
+    m.impl("tree_SR_gradient", &tree_SR_gradient);
+    m.impl("tree_SR_const_step", &tree_SR_const_step);
 }

@@ -38,6 +38,8 @@ class StandardPipeline(BasePipeline):
         before the whole generation is enqueued: the NaN scrub is a select instead of a boolean-mask assignment (which
         hides a host sync), and the fitness vector is brought to the host AFTER ``algorithm.step`` has queued the
         selection / breeding kernels, so the copy overlaps them instead of idling the GPU."""
+        if getattr(self.problem, "const_opt_steps", 0) > 0:   # Lamarckian constant tuning: the optimised trees are scored and bred
+            self.algorithm.forest = self.problem.optimize(self.algorithm.forest)
         forest = self.algorithm.forest  # step() builds a new forest; the best tree comes from this one
         scores = getattr(self.problem, "scores", None)
         if scores is not None:   # (a problem that hands over the scrubbed fitness itself: SymbolicRegression, one launch)

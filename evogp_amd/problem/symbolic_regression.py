@@ -18,9 +18,15 @@ _MODES = ["torch", "hybrid parallel", "data parallel", "tree parallel", "auto"]
 class SymbolicRegression(BaseProblem):
     def __init__(self, datapoints: Optional[Tensor] = None, labels: Optional[Tensor] = None,
                  func: Optional[Callable] = None, num_inputs: Optional[int] = None, num_data: Optional[int] = 100,
-                 lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto"):
+                 lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
+                 const_step_size: float = 0.1):
+        """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
+        gradient descent (``Forest.optimize_constants``), and StandardPipeline scores the optimised forest (Lamarckian)."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
+        assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
+        self.const_opt_steps = int(const_opt_steps)
+        self.const_step_size = float(const_step_size)
         if datapoints is not None and labels is not None:
             self.datapoints, self.labels = datapoints, labels
             return
@@ -60,6 +66,13 @@ class SymbolicRegression(BaseProblem):
             return torch.ops.evogp_hip.fitness_scores(err, True)
         f = self.evaluate(forest, use_MSE)
         return torch.where(torch.isnan(f), torch.full_like(f, float("-inf")), f)
+
+    def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:
+        """``forest`` with its constants tuned by ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest
+        itself when ``const_opt_steps`` is 0)."""
+        if self.const_opt_steps <= 0:
+            return forest
+        return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE)[0]
 
     @property
     def problem_dim(self):

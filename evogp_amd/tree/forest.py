@@ -6,7 +6,8 @@
 
 API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
-indexing, concatenation, iteration, pickling).  Every heavy method is one call into
+indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``optimize_constants`` (gradient descent on the constants,
+no counterpart in the reference).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -180,6 +181,47 @@ class Forest:
                                                     self.output_len, use_MSE, *self._tensors(),
                                                     inputs.contiguous().to(torch.float32),
                                                     labels.contiguous().to(torch.float32), _SR_MODES[execute_mode])
+
+    def _sr_data(self, inputs: Tensor, labels: Tensor):
+        inputs, labels = check_tensor(inputs, self.batch_node_value.device), check_tensor(labels, self.batch_node_value.device)
+        n = inputs.shape[0]
+        assert inputs.shape == (n, self.input_len), (
+            f"inputs shape should be ({n}, {self.input_len}), but got {inputs.shape}")
+        assert labels.shape == (n, self.output_len), (
+            f"outputs shape should be ({n}, {self.output_len}), but got {labels.shape}")
+        return inputs.contiguous().to(torch.float32), labels.contiguous().to(torch.float32)
+
+    def SR_gradient(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
+        """``(loss, grad)``: ``loss`` (pop,) is what ``SR_fitness`` returns, ``grad`` (pop, max_tree_len) is d loss / d value at every
+        constant node and exactly 0 elsewhere (one reverse-mode HIP pass, csrc/sr_grad.hip).  Malformed trees: NaN loss, zero row."""
+        inputs, labels = self._sr_data(inputs, labels)
+        return torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
+                                                    use_MSE, *self._tensors(), inputs, labels)
+
+    def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True):
+        """``(forest, loss)``: ``steps`` iterations of a per-tree gradient descent on the constants ("bold driver": a step of length
+        h along -grad / |grad| is kept only if it lowers the tree's loss, and h then doubles; otherwise h halves), all on the device
+        with no host synchronisation (2 launches per step).  Returns a new Forest (this one is untouched) whose trees differ from these
+        only in constant values, and the loss of each returned tree.  No tree's loss rises."""
+        assert steps >= 0, f"steps should be >= 0, but got {steps}"
+        inputs, labels = self._sr_data(inputs, labels)
+        n = inputs.shape[0]
+        value, ntype, size = self._tensors()
+        value = value.clone()
+        loss, grad = torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len, use_MSE,
+                                                          value, ntype, size, inputs, labels)
+        if steps > 0:
+            cand = torch.empty_like(value)
+            step = torch.full((self.pop_size,), float(step_size), dtype=torch.float32, device=value.device)
+            step_op = torch.ops.evogp_hip.tree_SR_const_step
+            step_op(2, self.output_len, value, ntype, size, cand, loss, grad, loss, grad, step)
+            for k in range(steps):
+                loss_c, grad_c = torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len,
+                                                                      use_MSE, cand, ntype, size, inputs, labels)
+                step_op(3 if k + 1 < steps else 1, self.output_len, value, ntype, size, cand, loss, grad, loss_c, grad_c, step)
+        forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
+                        func_mask=self.func_mask)
+        return forest, loss
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

@@ -96,6 +96,31 @@ int evogp_hip_sr_fitness(unsigned pop_size, unsigned data_points, unsigned gp_le
                          const float *variables, const float *labels, float *fitnesses,
                          unsigned kernel_type, evogp_stream_t stream);
 
+/* Gradient of the SR loss with respect to the constants (no counterpart in the reference).  loss: f32[pop_size], the quantity
+ * evogp_hip_sr_fitness returns, from this call's own forward pass; grad: f32[pop_size][gp_len], grad[t][i] = d loss[t] / d value[t][i]
+ * for every CONST node i of tree t, exactly 0.0f at every other node and on the tail [len, gp_len).  Forward semantics are those of
+ * evogp_hip_sr_fitness in both output modes; the derivative of every function, its edge cases included, is DESIGN.md's
+ * "Constant gradients" table.  A malformed tree gets a NaN loss and a zero row.  Sums run in a fixed order (bit-identical results
+ * from run to run).  out_len <= 16 (else EVOGP_E_UNSUPPORTED).  Rows of more than 64 nodes keep their tapes in an engine-owned
+ * buffer per stream (2 x gp_len x 256 B per resident wave, 256 MiB at gp_len 1024 on a 256-CU device), allocated by the first such
+ * call on the stream outside a stream capture (inside one: EVOGP_E_UNSUPPORTED) and freed by evogp_hip_release_workspaces. */
+int evogp_hip_sr_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                          int use_mse, const float *value, const int16_t *type, const int16_t *size,
+                          const float *variables, const float *labels, float *loss, float *grad, evogp_stream_t stream);
+
+/* One iteration of the per-tree constant descent ("bold driver") on the device, with no host synchronisation.  Per tree t:
+ * value / loss / grad hold the current constants, their loss and their gradient (evogp_hip_sr_gradient), step the step length h_t.
+ *   phase & 1  accept: if loss_cand[t] < loss[t] (a NaN never accepts) the CONST words of value_cand's live prefix are copied to
+ *              value, loss[t] = loss_cand[t], the grad row = the grad_cand row and h_t doubles; otherwise h_t halves.
+ *   phase & 2  propose (after the accept): value_cand row = value row with every CONST node c_i -> c_i - h_t * g_i / |g|_2, or the
+ *              value row unchanged when loss[t] or |g|_2 is not finite or is 0.
+ * Neither type nor size nor any non-constant word of value is written.  A descent of S steps: evogp_hip_sr_gradient on value,
+ * phase 2, then S times {evogp_hip_sr_gradient on value_cand -> loss_cand / grad_cand, phase 3 (the last one: phase 1)}.
+ * loss_cand / grad_cand may be NULL when phase is 2. */
+int evogp_hip_sr_const_step(unsigned pop_size, unsigned gp_len, unsigned out_len, int phase, float *value, const int16_t *type,
+                            const int16_t *size, float *value_cand, float *loss, float *grad, const float *loss_cand,
+                            const float *grad_cand, float *step, evogp_stream_t stream);
+
 /* evogp_hip_generate restricted to the trees n with (unsigned)active_word[n] < active_below (active_word == NULL: all of
  * them).  Rows of the other trees are not touched.  Used by the fused generation step: donors are only produced for
  * the offspring that will mutate. */
@@ -363,7 +388,8 @@ const char *evogp_hip_error_string(int code);
 int evogp_hip_set_sr_division(int mode);
 int evogp_hip_get_sr_division(void);
 
-/* ABI version of this header (5): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h). */
+/* ABI version of this header (6): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
+ * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
