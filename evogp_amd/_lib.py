@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # EVOGP_HIP_LIB: alternative build of the same engine (A/B benchmarking of compiler flags only)
 LIB_PATH = os.environ.get("EVOGP_HIP_LIB") or os.path.join(_HERE, "lib", "libevogp_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _vp = C.c_void_p
 _u = C.c_uint
@@ -54,6 +54,9 @@ PROTOTYPES = {
     "evogp_hip_abi_version": [],
     "evogp_hip_sr_gradient": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_const_step": [_u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_case_errors": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_lexicase_workspace_bytes": [_u, _u, _u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_lexicase_select": [_u, _u, _vp, _vp, _u, C.c_longlong, C.c_longlong, _vp, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them
@@ -74,6 +77,7 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_structural_mutate_given": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_insert_mutate_given": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_point_mutate_given": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_debug_lexicase": [_vp, _i],
 }
 
 

@@ -234,3 +234,132 @@ class TournamentSelection(_SelectorSelection):
             parents = c.gather(0, best).squeeze(0).to(torch.int32)
         elites = default_lists(fit, n_elite, max(n_elite, 1))[0] if n_elite > 0 else torch.empty(0, dtype=torch.int32, device=fit.device)
         return elites.contiguous(), parents.contiguous()
+
+
+# ---- epsilon-lexicase (La Cava, Spector & Danai 2016; La Cava, Helmuth, Spector & Moore 2019) ------------------------------------
+# Counter-word rows (csrc/evogp_defs.hpp counter_word, parallel.random_words) of a LexicaseSelection's own seed: 2^21 + 0..3 the
+# round keys of event k's case permutation, 2^21 + 4 the pick of event k (csrc/lexicase.hip), 2^21 + 5 the down-sampled rows.
+LEXICASE_ROW_SAMPLE = 2**21 + 5
+
+
+def lexicase_epsilon(errors: torch.Tensor) -> torch.Tensor:
+    """``(pop, n)`` errors of any strides -> ``(n,)`` float32: eps_c = lowmed(|e - lowmed(e)|) over the finite errors e of case c, the
+    median absolute deviation; 0 for a case without a finite error.  lowmed is the lower median, torch.nanmedian's convention once the
+    non-finite entries are NaN.  Runs on the errors' device with no host sync."""
+    x = errors.to(torch.float32)
+    x = torch.where(torch.isfinite(x), x, torch.full_like(x, float("nan")))
+    med = torch.nanmedian(x, dim=0).values
+    mad = torch.nanmedian((x - med[None, :]).abs(), dim=0).values
+    return torch.where(mad == mad, mad, torch.zeros_like(mad))
+
+
+def _counter_row(seed: int, generation: int, row: int, n: int, device) -> torch.Tensor:
+    """int64[n]: counter word ``row`` of items 0 .. n-1 under (seed, generation) -- ``parallel.random_words(seed, generation, 1, 0, n,
+    device, first_row=row)[0]`` computed without a host-to-device copy (the base is folded on the host), so nothing synchronises"""
+    from ..parallel import _mix64
+
+    m = (1 << 64) - 1
+
+    def mix(x):
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+        return x ^ (x >> 31)
+
+    start = (mix((seed * 1000003 + generation) & m) + (row << 40)) & m
+    start = start - (1 << 64) if start >= 1 << 63 else start          # the same 64 bits as a signed torch scalar
+    x = _mix64(torch.arange(n, dtype=torch.int64, device=device) + start)
+    return ((x >> 33) & 0x7FFFFFFF) % (2**31 - 1)
+
+
+class LexicaseSelection(BaseSelection):
+    """Semi-dynamic epsilon-lexicase selection over per-case errors (La Cava et al. 2016, 2019): every survivor slot is one event that
+    filters the population case by case, in an order of its own, keeping the trees within eps_c of the best error left on case c, and
+    draws the survivor from what is left (include/evogp_hip.h evogp_hip_lexicase_select has the exact contract; tests/lexicase_ref.py
+    restates it).  Elites are the best elite count by ``fitness``, as in the other selections.
+
+    ``case_errors``: by default ``forest.SR_case_errors(datapoints[rows], labels[rows], use_MSE)`` (absolute errors by default, as in
+    La Cava et al.); a callable ``case_errors(forest) -> (pop, n)`` tensor replaces it (e.g. 0/1 misclassification, with epsilon 0:
+    plain lexicase).  ``epsilon``: "auto" (``lexicase_epsilon``, the median absolute deviation per case), a float, or an ``(n,)``
+    tensor.  ``downsample_rate < 1``: down-sampled lexicase (Hernandez et al. 2019), every call uses max(1, round(rate * D)) rows, the
+    rows with the smallest counter words of this call (ties: lower row first).  The random numbers are counter words of a seed the
+    object draws once from torch's CPU generator (reproducible under torch.manual_seed) and of its own call counter.  Nothing in
+    ``__call__`` synchronises with the host.  GPU forests only (the ops have no CPU kernel); not for a sharded run, whose selection
+    sees no trees."""
+
+    def __init__(self, datapoints: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, epsilon="auto", use_MSE: bool = False,
+                 downsample_rate: float = 1.0, survivor_rate: float = 1.0, elite_rate: float = 0.0, survivor_cnt: Optional[int] = None,
+                 elite_cnt: Optional[int] = None, case_errors=None):
+        assert (datapoints is None) == (labels is None), "datapoints and labels should be given together"
+        assert case_errors is not None or datapoints is not None, "LexicaseSelection needs (datapoints, labels) or case_errors"
+        assert case_errors is None or callable(case_errors), "case_errors should be a callable forest -> (pop, n) tensor"
+        assert 0 < downsample_rate <= 1, "downsample_rate should be in (0, 1]"
+        assert 0 <= survivor_rate <= 1, "survivor_rate should be in [0, 1]"
+        assert 0 <= elite_rate <= 1, "elite_rate should be in [0, 1]"
+        if isinstance(epsilon, str):
+            assert epsilon == "auto", f"epsilon should be 'auto', a float or a tensor, but got {epsilon!r}"
+        elif not isinstance(epsilon, torch.Tensor):
+            epsilon = float(epsilon)
+            assert epsilon >= 0, f"epsilon should be >= 0, but got {epsilon}"
+        self.datapoints, self.labels = datapoints, labels
+        self.epsilon = epsilon
+        self.use_MSE = use_MSE
+        self.downsample_rate = downsample_rate
+        self.survivor_rate, self.survivor_cnt = survivor_rate, survivor_cnt
+        self.elite_rate, self.elite_cnt = elite_rate, elite_cnt
+        self.case_errors = case_errors
+        self.seed = int(torch.randint(0, 2**40, (1,)).item())
+        self.generation = 0
+        self._data = None
+
+    def counts(self, pop_size: int):
+        n_surv = self.survivor_cnt if self.survivor_cnt is not None else int(pop_size * self.survivor_rate)
+        n_elite = self.elite_cnt if self.elite_cnt is not None else int(pop_size * self.elite_rate)
+        return n_elite, n_surv
+
+    def rows(self, n_rows: int, device) -> Optional[torch.Tensor]:
+        """int64 row indices (ascending) of this call's down-sample, None for all rows"""
+        m = max(1, round(self.downsample_rate * n_rows))
+        if m >= n_rows:
+            return None
+        w = _counter_row(self.seed, self.generation, LEXICASE_ROW_SAMPLE, n_rows, device)
+        return torch.sort(torch.sort(w, stable=True).indices[:m]).values
+
+    def errors(self, forest: Forest) -> torch.Tensor:
+        """the ``(pop, n)`` errors this call selects on"""
+        dev = forest.batch_node_value.device
+        if self.case_errors is not None:
+            e = self.case_errors(forest)
+            assert e.dim() == 2 and e.shape[0] == forest.pop_size, (
+                f"case_errors should return a ({forest.pop_size}, n) tensor, but got {tuple(e.shape)}")
+            rows = self.rows(e.shape[1], e.device)
+            return e if rows is None else e[:, rows]
+        if self._data is None or self._data[0].device != dev:
+            self._data = (self.datapoints.to(dev), self.labels.to(dev))   # (once per device)
+        X, y = self._data
+        rows = self.rows(X.shape[0], dev)
+        if rows is not None:
+            X, y = X[rows], y[rows]
+        return forest.SR_case_errors(X, y, self.use_MSE)
+
+    def __call__(self, forest: Forest, fitness: torch.Tensor):
+        if not isinstance(forest, Forest):
+            raise TypeError("LexicaseSelection reads every tree's per-case errors: it cannot run in a sharded step, whose selection "
+                            "sees only the gathered fitness vector")
+        n_elite, n_surv = self.counts(forest.pop_size)
+        errors = self.errors(forest)
+        n = errors.shape[1]
+        if isinstance(self.epsilon, str):
+            eps = lexicase_epsilon(errors)
+        elif isinstance(self.epsilon, torch.Tensor):
+            eps = self.epsilon.to(device=errors.device, dtype=torch.float32).reshape(-1)
+            assert eps.shape == (n,), f"epsilon should have shape ({n},), but got {tuple(self.epsilon.shape)}"
+        else:
+            eps = torch.full((n,), self.epsilon, dtype=torch.float32, device=errors.device)
+        E = errors.t().to(torch.float32).contiguous()
+        survivors = torch.ops.evogp_hip.lexicase_select(E, eps.contiguous(), n_surv, self.seed, self.generation)
+        self.generation += 1
+        if n_elite > 0:
+            elites = torch.topk(_clean(fitness), n_elite, sorted=True).indices.to(torch.int32)
+        else:
+            elites = torch.empty(0, dtype=torch.int32, device=fitness.device)
+        return elites, survivors

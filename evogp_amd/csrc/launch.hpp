@@ -71,5 +71,8 @@ void engine_free_shared(void *ptr);
 // waited for the device; evogp_hip_release_workspaces).
 bool grad_workspaces_held();
 void release_grad_workspaces(int dev);
+// The prediction buffers of the per-case errors (lexicase.hip), the same way.
+bool case_workspaces_held();
+void release_case_workspaces(int dev);
 
 } // namespace evogp

@@ -1,0 +1,580 @@
+// lexicase.hip — per-case SR errors and epsilon-lexicase parent selection (gfx950; no counterpart in the reference).
+//
+// evogp_hip_sr_case_errors: the batch evaluation (sr_fitness.hip, the interpreters of evogp_hip_batch_evaluate) into an engine-owned
+// prediction buffer, then one epilogue kernel that reads the (pop, D, out) predictions and the labels and writes the CASE-MAJOR errors
+// errors[d][t] = (sum_o delta_o) / out_len through a 64 x 64 LDS tile (reads along d, writes along t, both coalesced).
+//
+// evogp_hip_lexicase_select: semi-dynamic epsilon-lexicase over case-major errors E[n][pop] (include/evogp_hip.h has the contract).
+// Five stages, all on the caller's stream, nothing synchronises with the host:
+//   1. hash      one thread per tree hashes its key row to 64 bits (a coalesced pass over E)
+//   2. classes   a stable radix sort of (hash, tree) pairs (rocPRIM), head marks, two scans: clone classes numbered in ascending order
+//                of their smallest tree, each with a representative, a member count and a member list in ascending tree order
+//   3. prep      one workgroup per case c: the pool an event starts from when its first case is c, as a list of class ids
+//   4. events    one wave per event: the pool in the wave's LDS share while it fits (kLexCap classes), else as a bit mask over the
+//                first-pool list in the wave's own slice of the workspace; each step gathers E[c][rep] for the classes still in
+//                the pool, takes the minimum and maximum (a step that removes nobody costs one pass) and compacts with ballots
+//   5. pick      winners[k] = member (word_k mod S) of the pool listed class by class, S = the members of the pool's classes
+// A hash collision merges two classes (probability about pop^2 / 2^65).
+#include "evogp_defs.hpp"
+#include "launch.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <mutex>
+#include <vector>
+
+namespace evogp {
+
+// ---- case errors ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void case_errors_kernel(const float *pred, const float *y, float *err, unsigned pop, unsigned D,
+                                                          unsigned out_len, int mse) {
+    __shared__ float tile[64][65];
+    const unsigned tx = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+    const unsigned t0 = blockIdx.x * 64u;
+    const float inv_scale = (float)out_len;
+    for (unsigned d0 = blockIdx.y * 64u; d0 < D; d0 += gridDim.y * 64u) {
+        for (unsigned tt = ty; tt < 64u; tt += 4u) {
+            const unsigned t = t0 + tt, d = d0 + tx;
+            if (t < pop && d < D) {
+                const float *pr = pred + ((size_t)t * D + d) * out_len;
+                const float *yr = y + (size_t)d * out_len;
+                float s = 0.0f;
+                for (unsigned o = 0; o < out_len; ++o) {
+                    const float diff = pr[o] - yr[o];
+                    s += mse ? diff * diff : fabsf(diff);
+                }
+                tile[tt][tx] = s / inv_scale;
+            }
+        }
+        __syncthreads();
+        for (unsigned dd = ty; dd < 64u; dd += 4u) {
+            const unsigned t = t0 + tx, d = d0 + dd;
+            if (t < pop && d < D) err[(size_t)d * pop + t] = tile[tx][dd];
+        }
+        __syncthreads();
+    }
+}
+
+// The prediction buffer of a stream: grown outside stream captures, never freed before evogp_hip_release_workspaces (a graph
+// captured earlier may point at it), as the gradient tapes of sr_grad.hip.
+struct CaseWorkspace { hipStream_t stream; void *buf; size_t bytes; };
+static std::mutex g_case_mu;
+static std::vector<CaseWorkspace> g_case_ws[64];
+static std::vector<void *> g_case_retired[64];
+
+static float *case_workspace(hipStream_t stream, size_t bytes, int *rc) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(g_case_mu);
+    auto &list = g_case_ws[dev & 63];
+    CaseWorkspace *ws = nullptr;
+    for (auto &e : list) if (e.stream == stream) ws = &e;
+    if (ws && ws->bytes >= bytes) return (float *)ws->buf;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        *rc = EVOGP_E_UNSUPPORTED;  // no allocation inside a capture: make one eager call of this shape on the stream first
+        return nullptr;
+    }
+    void *buf = nullptr;
+    hipError_t e = engine_alloc_shared(&buf, bytes);
+    if (e != hipSuccess || !buf) {
+        (void)hipGetLastError();
+        *rc = e != hipSuccess ? (int)e : (int)hipErrorOutOfMemory;
+        return nullptr;
+    }
+    if (ws) {
+        g_case_retired[dev & 63].push_back(ws->buf);
+        ws->buf = buf;
+        ws->bytes = bytes;
+    } else {
+        list.push_back({stream, buf, bytes});
+    }
+    return (float *)buf;
+}
+
+bool case_workspaces_held() {
+    std::lock_guard<std::mutex> lock(g_case_mu);
+    for (int d = 0; d < 64; ++d) if (!g_case_ws[d].empty() || !g_case_retired[d].empty()) return true;
+    return false;
+}
+
+void release_case_workspaces(int dev) {  // (the caller has waited for the device)
+    std::lock_guard<std::mutex> lock(g_case_mu);
+    for (auto &e : g_case_ws[dev & 63]) engine_free_shared(e.buf);
+    for (void *b : g_case_retired[dev & 63]) engine_free_shared(b);
+    g_case_ws[dev & 63].clear();
+    g_case_retired[dev & 63].clear();
+}
+
+// ---- lexicase selection --------------------------------------------------------------------------------------------------------
+constexpr unsigned kLexRowFeistel = (1u << 21);       // words 2^21 + r, r < 4: the round keys of event k's case permutation
+constexpr unsigned kLexRowPick = (1u << 21) + 4u;     // word 2^21 + 4: the pick of event k
+constexpr unsigned kLexCap = 2048;                    // classes a wave keeps in LDS (8 KiB)
+constexpr unsigned kLexWavesPerBlock = 4;
+constexpr unsigned kLexMaxWaves = 4096;               // 16 per CU of a 256-CU device
+
+// key(x): NaN -> +inf, -0 -> +0
+__device__ inline float lex_key(float x) { return x != x ? __builtin_inff() : (x == 0.0f ? 0.0f : x); }
+// order-preserving unsigned image of a key (keys are never NaN)
+__device__ inline unsigned lex_ord(float k) {
+    const unsigned u = __float_as_uint(k);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float lex_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
+// epsilon of a case: NaN and negative entries count as 0
+__device__ inline float lex_eps(float e) { return e > 0.0f ? e : 0.0f; }
+
+__device__ inline unsigned wave_min_u(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ inline unsigned wave_max_u(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ inline unsigned wave_sum_u(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+    return v;
+}
+__device__ inline unsigned lanes_below(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// perm_k(j): a 4-round Feistel network on 2 h bits (the smallest even width with 2^(2h) >= n), cycle-walked into [0, n)
+__device__ inline unsigned lex_perm(unsigned j, unsigned n, unsigned h, const unsigned *rk) {
+    if (n <= 1u) return 0u;
+    const unsigned mask = (1u << h) - 1u;
+    unsigned x = j;
+    do {
+        unsigned L = x >> h, R = x & mask;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned f = (unsigned)(mix64(((unsigned long long)rk[r] << 32) | R) >> 32) & mask;
+            const unsigned t = L ^ f;
+            L = R;
+            R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= n);
+    return x;
+}
+
+__global__ __launch_bounds__(256) void lex_hash_kernel(const float *E, unsigned n, unsigned pop, unsigned long long *hash, unsigned *idx) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= pop) return;
+    unsigned long long h = 0x243F6A8885A308D3ull;
+    for (unsigned c = 0; c < n; ++c) {
+        const unsigned bits = __float_as_uint(lex_key(E[(size_t)c * pop + i]));
+        h = mix64((h ^ bits) + 0x9E3779B97F4A7C15ull);
+    }
+    hash[i] = h;
+    idx[i] = i;
+}
+
+// over sorted positions s: head marks by tree (for the class numbering) and by position (for the segment starts)
+__global__ __launch_bounds__(256) void lex_heads_kernel(const unsigned long long *key, const unsigned *members, unsigned pop, unsigned *flag_t,
+                                                        unsigned *head_pos) {
+    const unsigned s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= pop) return;
+    const bool head = s == 0u || key[s] != key[s - 1u];
+    flag_t[members[s]] = head ? 1u : 0u;
+    head_pos[s] = head ? s : 0u;
+}
+
+// at the last position of every segment: the class's start, representative (its smallest tree) and member count
+__global__ __launch_bounds__(256) void lex_classes_kernel(const unsigned long long *key, const unsigned *members, const unsigned *seg,
+                                                          const unsigned *flag_t, const unsigned *cls_t, unsigned pop, unsigned *rep,
+                                                          unsigned *start, unsigned *count, unsigned *nclass) {
+    const unsigned s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= pop) return;
+    if (s == pop - 1u) *nclass = cls_t[pop - 1u] + flag_t[pop - 1u];
+    if (s + 1u < pop && key[s + 1u] == key[s]) return;
+    const unsigned st = seg[s], h = members[st], c = cls_t[h];
+    start[c] = st;
+    rep[c] = h;
+    count[c] = s - st + 1u;
+}
+
+struct LexPrep {
+    const float *E, *eps;
+    const unsigned *rep, *nclass;
+    unsigned *fp, *p1;
+    unsigned long long *counters;
+    unsigned n, pop;
+};
+
+// one workgroup per case c: m = min_i key(E[c][i]), then the classes with key <= m + eps[c] (the minimum always stays), ascending
+__global__ __launch_bounds__(1024) void lex_prep_kernel(LexPrep q) {
+    __shared__ unsigned s_w[16];
+    const unsigned c = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    const float *Ec = q.E + (size_t)c * q.pop;
+    unsigned lo = ~0u;
+    for (unsigned i = tid; i < q.pop; i += 1024u) lo = min(lo, lex_ord(lex_key(Ec[i])));
+    lo = wave_min_u(lo);
+    if (lane == 0) s_w[w] = lo;
+    __syncthreads();
+    lo = s_w[0];
+    for (int k = 1; k < 16; ++k) lo = min(lo, s_w[k]);
+    __syncthreads();
+    const float m = lex_unord(lo), thr = m + lex_eps(q.eps[c]);
+    const unsigned C = *q.nclass;
+    unsigned *dst = q.fp + (size_t)c * q.pop;
+    unsigned out = 0;
+    for (unsigned base = 0; base < C; base += 1024u) {
+        const unsigned cl = base + tid;
+        bool keep = false;
+        if (cl < C) {
+            const float k = lex_key(Ec[q.rep[cl]]);
+            keep = k <= thr || k == m;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_w[w] = (unsigned)__popcll(bal);
+        __syncthreads();
+        unsigned before = 0, all = 0;
+        for (unsigned k = 0; k < 16u; ++k) {
+            const unsigned v = s_w[k];
+            all += v;
+            before += k < w ? v : 0u;
+        }
+        if (keep) dst[out + before + lanes_below(bal)] = cl;
+        out += all;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        q.p1[c] = out;
+        if (q.counters) {
+            atomicAdd(q.counters + 2, (unsigned long long)out);
+            atomicMax(q.counters + 3, (unsigned long long)out);
+            atomicAdd(q.counters + 5, 1ull);
+            if (c == 0) atomicAdd(q.counters + 4, (unsigned long long)C);
+        }
+    }
+}
+
+struct LexEvents {
+    const float *E, *eps;
+    const unsigned *members, *rep, *start, *count, *fp, *p1;
+    unsigned *bits;
+    int *winners;
+    unsigned long long *counters;
+    unsigned long long base;
+    unsigned n, pop, n_events, h, words;
+};
+
+__global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
+    __shared__ unsigned s_list[kLexWavesPerBlock][kLexCap];
+    const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    unsigned *list = s_list[w];
+    const unsigned gw = blockIdx.x * kLexWavesPerBlock + w, nw = gridDim.x * kLexWavesPerBlock;
+    unsigned *bits = p.bits + (size_t)gw * p.words;
+    unsigned long long steps_total = 0;
+    for (unsigned k = gw; k < p.n_events; k += nw) {
+        unsigned rk[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rk[r] = counter_word(p.base, kLexRowFeistel + (unsigned)r, (unsigned long long)k);
+        const unsigned c0 = lex_perm(0u, p.n, p.h, rk);
+        const unsigned P1 = p.p1[c0];
+        const unsigned *fpl = p.fp + (size_t)c0 * p.pop;
+        const unsigned nwords = (P1 + 31u) >> 5;
+        bool inlist = P1 <= kLexCap;
+        unsigned cnt = P1;
+        if (inlist) {
+            for (unsigned i = lane; i < P1; i += 64u) list[i] = fpl[i];
+        } else {
+            for (unsigned wd = lane; wd < nwords; wd += 64u)
+                bits[wd] = (wd + 1u < nwords || (P1 & 31u) == 0u) ? ~0u : ((1u << (P1 & 31u)) - 1u);
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (unsigned j = 1; j < p.n && cnt > 1u; ++j) {
+            ++steps_total;
+            const unsigned c = lex_perm(j, p.n, p.h, rk);
+            const float *Ec = p.E + (size_t)c * p.pop;
+            unsigned lo = ~0u, hi = 0u;
+            if (inlist) {
+                for (unsigned i = lane; i < cnt; i += 64u) {
+                    const unsigned o = lex_ord(lex_key(Ec[p.rep[list[i]]]));
+                    lo = min(lo, o);
+                    hi = max(hi, o);
+                }
+            } else {
+                for (unsigned wd = lane; wd < nwords; wd += 64u) {
+                    unsigned b = bits[wd];
+                    while (b) {
+                        const unsigned q = (unsigned)__builtin_ctz(b);
+                        b &= b - 1u;
+                        const unsigned o = lex_ord(lex_key(Ec[p.rep[fpl[wd * 32u + q]]]));
+                        lo = min(lo, o);
+                        hi = max(hi, o);
+                    }
+                }
+            }
+            lo = wave_min_u(lo);
+            hi = wave_max_u(hi);
+            const float m = lex_unord(lo), M = lex_unord(hi), thr = m + lex_eps(p.eps[c]);
+            if (M <= thr) continue;   // nobody leaves the pool
+            if (inlist) {
+                unsigned out = 0;
+                for (unsigned base = 0; base < cnt; base += 64u) {
+                    const unsigned i = base + lane;
+                    bool keep = false;
+                    unsigned cl = 0;
+                    if (i < cnt) {
+                        cl = list[i];
+                        const float kk = lex_key(Ec[p.rep[cl]]);
+                        keep = kk <= thr || kk == m;
+                    }
+                    const unsigned long long bal = __ballot(keep);
+                    __builtin_amdgcn_wave_barrier();
+                    if (keep) list[out + lanes_below(bal)] = cl;
+                    __builtin_amdgcn_wave_barrier();
+                    out += (unsigned)__popcll(bal);
+                }
+                cnt = out;
+            } else {
+                unsigned mine = 0;
+                for (unsigned wd = lane; wd < nwords; wd += 64u) {
+                    unsigned b = bits[wd], nb = b;
+                    while (b) {
+                        const unsigned q = (unsigned)__builtin_ctz(b);
+                        b &= b - 1u;
+                        const float kk = lex_key(Ec[p.rep[fpl[wd * 32u + q]]]);
+                        if (!(kk <= thr || kk == m)) nb &= ~(1u << q);
+                    }
+                    bits[wd] = nb;
+                    mine += (unsigned)__popc(nb);
+                }
+                cnt = wave_sum_u(mine);
+                if (cnt <= kLexCap) {   // small enough for LDS: the list in ascending first-pool order, i.e. ascending class id
+                    unsigned out = 0;
+                    for (unsigned base = 0; base < nwords; base += 64u) {
+                        const unsigned wd = base + lane;
+                        unsigned b = wd < nwords ? bits[wd] : 0u;
+                        const int pc = __popc(b);
+                        const int incl = wave_scan_incl(pc);
+                        unsigned pos = out + (unsigned)(incl - pc);
+                        while (b) {
+                            const unsigned q = (unsigned)__builtin_ctz(b);
+                            b &= b - 1u;
+                            list[pos++] = fpl[wd * 32u + q];
+                        }
+                        out += (unsigned)__builtin_amdgcn_readlane(incl, 63);
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    inlist = true;
+                }
+            }
+        }
+        // the pick: member (word mod S) of the pool listed class by class
+        const unsigned word = counter_word(p.base, kLexRowPick, (unsigned long long)k);
+        unsigned winner = 0;
+        if (inlist) {
+            unsigned tot = 0;
+            for (unsigned i = lane; i < cnt; i += 64u) tot += p.count[list[i]];
+            const unsigned r = word % wave_sum_u(tot);
+            unsigned run = 0;
+            for (unsigned base = 0; base < cnt; base += 64u) {
+                const unsigned i = base + lane;
+                const unsigned cl = i < cnt ? list[i] : 0u, cc = i < cnt ? p.count[cl] : 0u;
+                const int incl = wave_scan_incl((int)cc);
+                const unsigned before = run + (unsigned)incl - cc;
+                const bool here = cc > 0u && r >= before && r < before + cc;
+                const unsigned long long bal = __ballot(here);
+                if (bal) {
+                    const unsigned src = (unsigned)__builtin_ctzll(bal);
+                    const unsigned v = here ? p.members[p.start[cl] + (r - before)] : 0u;
+                    winner = (unsigned)__shfl((int)v, (int)src, 64);
+                    break;
+                }
+                run += (unsigned)__builtin_amdgcn_readlane(incl, 63);
+            }
+        } else {
+            unsigned tot = 0;
+            for (unsigned wd = lane; wd < nwords; wd += 64u) {
+                unsigned b = bits[wd];
+                while (b) {
+                    const unsigned q = (unsigned)__builtin_ctz(b);
+                    b &= b - 1u;
+                    tot += p.count[fpl[wd * 32u + q]];
+                }
+            }
+            const unsigned r = word % wave_sum_u(tot);
+            unsigned run = 0;
+            for (unsigned base = 0; base < nwords; base += 64u) {
+                const unsigned wd = base + lane;
+                const unsigned b0 = wd < nwords ? bits[wd] : 0u;
+                unsigned cc = 0;
+                for (unsigned b = b0; b; b &= b - 1u) cc += p.count[fpl[wd * 32u + (unsigned)__builtin_ctz(b)]];
+                const int incl = wave_scan_incl((int)cc);
+                unsigned before = run + (unsigned)incl - cc;
+                const bool here = cc > 0u && r >= before && r < before + cc;
+                const unsigned long long bal = __ballot(here);
+                if (bal) {
+                    const unsigned src = (unsigned)__builtin_ctzll(bal);
+                    unsigned v = 0;
+                    if (here) {
+                        for (unsigned b = b0; b; b &= b - 1u) {
+                            const unsigned cl = fpl[wd * 32u + (unsigned)__builtin_ctz(b)], n_cl = p.count[cl];
+                            if (r < before + n_cl) { v = p.members[p.start[cl] + (r - before)]; break; }
+                            before += n_cl;
+                        }
+                    }
+                    winner = (unsigned)__shfl((int)v, (int)src, 64);
+                    break;
+                }
+                run += (unsigned)__builtin_amdgcn_readlane(incl, 63);
+            }
+        }
+        if (lane == 0) p.winners[k] = (int)winner;
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (p.counters && lane == 0 && gw < p.n_events) {
+        atomicAdd(p.counters + 0, steps_total);
+        atomicAdd(p.counters + 1, (unsigned long long)((p.n_events - gw + nw - 1u) / nw));
+    }
+}
+
+// ---- workspace ------------------------------------------------------------------------------------------------------------------
+struct LexLayout {
+    size_t keys_a, keys_b, vals_a, vals_b, flag_t, cls_t, head_pos, seg, rep, start, count, nclass, p1, fp, bits, temp, temp_bytes, total;
+    unsigned waves, words;
+};
+
+static size_t lex_align(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+static unsigned lex_waves(unsigned n, unsigned n_events) {
+    unsigned long long w = n_events < kLexMaxWaves ? n_events : kLexMaxWaves;
+    if (w > 32ull * n) w = 32ull * n;   // the bit-mask slices stay within E's bytes
+    if (w < 1) w = 1;
+    return (unsigned)((w + kLexWavesPerBlock - 1) / kLexWavesPerBlock * kLexWavesPerBlock);
+}
+
+static hipError_t lex_layout(unsigned n, unsigned pop, unsigned n_events, LexLayout *L) {
+    size_t t_sort = 0, t_excl = 0, t_incl = 0;
+    rocprim::double_buffer<unsigned long long> kb(nullptr, nullptr);
+    rocprim::double_buffer<unsigned> vb(nullptr, nullptr);
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, kb, vb, pop, 0, 64, (hipStream_t)0);
+    if (e != hipSuccess) return e;
+    e = rocprim::exclusive_scan(nullptr, t_excl, (const unsigned *)nullptr, (unsigned *)nullptr, 0u, (size_t)pop, rocprim::plus<unsigned>(), (hipStream_t)0);
+    if (e != hipSuccess) return e;
+    e = rocprim::inclusive_scan(nullptr, t_incl, (const unsigned *)nullptr, (unsigned *)nullptr, (size_t)pop, rocprim::maximum<unsigned>(), (hipStream_t)0);
+    if (e != hipSuccess) return e;
+    L->temp_bytes = t_sort > t_excl ? t_sort : t_excl;
+    if (t_incl > L->temp_bytes) L->temp_bytes = t_incl;
+    L->waves = lex_waves(n, n_events);
+    L->words = (pop + 31u) / 32u;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += lex_align(bytes); return o; };
+    L->keys_a = take((size_t)pop * 8); L->keys_b = take((size_t)pop * 8);
+    L->vals_a = take((size_t)pop * 4); L->vals_b = take((size_t)pop * 4);
+    L->flag_t = take((size_t)pop * 4); L->cls_t = take((size_t)pop * 4);
+    L->head_pos = take((size_t)pop * 4); L->seg = take((size_t)pop * 4);
+    L->rep = take((size_t)pop * 4); L->start = take((size_t)pop * 4); L->count = take((size_t)pop * 4);
+    L->nclass = take(4); L->p1 = take((size_t)n * 4);
+    L->fp = take((size_t)n * pop * 4);
+    L->bits = take((size_t)L->waves * L->words * 4);
+    L->temp = take(L->temp_bytes);
+    L->total = off;
+    return hipSuccess;
+}
+
+static unsigned long long *g_lex_counters = nullptr;
+static int g_lex_stop = 0;
+
+}  // namespace evogp
+
+using namespace evogp;
+
+extern "C" int evogp_hip_sr_case_errors(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len, int use_mse,
+                                        const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                        const float *labels, float *errors, evogp_stream_t stream_) {
+    if (pop_size == 0 || data_points == 0 || gp_len == 0 || gp_len > (unsigned)kMaxStack || var_len == 0 || out_len == 0 ||
+        pop_size > 0x7FFFFFFFu)
+        return EVOGP_E_BADARG;
+    if (!value || !type || !size || !variables || !labels || !errors) return EVOGP_E_NULLPTR;
+    if (out_len > 256u) return EVOGP_E_UNSUPPORTED;   // (the batch evaluation's limit, kGeneralOuts)
+    const hipStream_t stream = (hipStream_t)stream_;
+    int rc = EVOGP_OK;
+    float *pred = case_workspace(stream, (size_t)pop_size * data_points * out_len * sizeof(float), &rc);
+    if (!pred) return rc;
+    rc = evogp_hip_batch_evaluate(pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, pred, stream_);
+    if (rc != EVOGP_OK) return rc;
+    const unsigned gy = (data_points + 63u) / 64u;
+    hipLaunchKernelGGL(case_errors_kernel, dim3((pop_size + 63u) / 64u, gy < 65535u ? gy : 65535u), dim3(256), 0, stream, pred, labels, errors,
+                       pop_size, data_points, out_len, use_mse ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+extern "C" int evogp_hip_lexicase_workspace_bytes(unsigned n_cases, unsigned pop, unsigned n_events, unsigned long long *bytes) {
+    if (n_cases == 0 || pop == 0 || pop > 0x7FFFFFFFu) return EVOGP_E_BADARG;
+    if (!bytes) return EVOGP_E_NULLPTR;
+    LexLayout L;
+    const hipError_t e = lex_layout(n_cases, pop, n_events, &L);
+    if (e != hipSuccess) return (int)e;
+    *bytes = (unsigned long long)L.total;
+    return EVOGP_OK;
+}
+
+extern "C" int evogp_hip_lexicase_select(unsigned n_cases, unsigned pop, const float *errors, const float *eps, unsigned n_events, long long seed,
+                                         long long generation, int *winners, void *workspace, evogp_stream_t stream_) {
+    if (n_cases == 0 || pop == 0 || pop > 0x7FFFFFFFu || n_events > 0x7FFFFFFFu) return EVOGP_E_BADARG;
+    if (n_events == 0) return EVOGP_OK;
+    if (!errors || !eps || !winners || !workspace) return EVOGP_E_NULLPTR;
+    const hipStream_t stream = (hipStream_t)stream_;
+    LexLayout L;
+    hipError_t e = lex_layout(n_cases, pop, n_events, &L);
+    if (e != hipSuccess) return (int)e;
+    char *ws = (char *)workspace;
+    auto at = [&](size_t off) { return (void *)(ws + off); };
+    unsigned long long *keys_a = (unsigned long long *)at(L.keys_a), *keys_b = (unsigned long long *)at(L.keys_b);
+    unsigned *vals_a = (unsigned *)at(L.vals_a), *vals_b = (unsigned *)at(L.vals_b);
+    unsigned *flag_t = (unsigned *)at(L.flag_t), *cls_t = (unsigned *)at(L.cls_t), *head_pos = (unsigned *)at(L.head_pos), *seg = (unsigned *)at(L.seg);
+    unsigned *rep = (unsigned *)at(L.rep), *start = (unsigned *)at(L.start), *count = (unsigned *)at(L.count), *nclass = (unsigned *)at(L.nclass);
+    unsigned *p1 = (unsigned *)at(L.p1), *fp = (unsigned *)at(L.fp), *bits = (unsigned *)at(L.bits);
+    void *temp = at(L.temp);
+    const dim3 grid((pop + 255u) / 256u), block(256);
+
+    // 1-2. hash, sort, classes
+    hipLaunchKernelGGL(lex_hash_kernel, grid, block, 0, stream, errors, n_cases, pop, keys_a, vals_a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    rocprim::double_buffer<unsigned long long> kb(keys_a, keys_b);
+    rocprim::double_buffer<unsigned> vb(vals_a, vals_b);
+    size_t tb = L.temp_bytes;
+    if ((e = rocprim::radix_sort_pairs(temp, tb, kb, vb, pop, 0, 64, stream)) != hipSuccess) return (int)e;
+    const unsigned long long *key = kb.current();
+    const unsigned *members = vb.current();
+    hipLaunchKernelGGL(lex_heads_kernel, grid, block, 0, stream, key, members, pop, flag_t, head_pos);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    tb = L.temp_bytes;
+    if ((e = rocprim::exclusive_scan(temp, tb, (const unsigned *)flag_t, cls_t, 0u, (size_t)pop, rocprim::plus<unsigned>(), stream)) != hipSuccess)
+        return (int)e;
+    tb = L.temp_bytes;
+    if ((e = rocprim::inclusive_scan(temp, tb, (const unsigned *)head_pos, seg, (size_t)pop, rocprim::maximum<unsigned>(), stream)) != hipSuccess)
+        return (int)e;
+    hipLaunchKernelGGL(lex_classes_kernel, grid, block, 0, stream, key, members, seg, flag_t, cls_t, pop, rep, start, count, nclass);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (g_lex_stop == 1) return EVOGP_OK;
+
+    // 3. the first pool of every case
+    LexPrep q{errors, eps, rep, nclass, fp, p1, g_lex_counters, n_cases, pop};
+    hipLaunchKernelGGL(lex_prep_kernel, dim3(n_cases), dim3(1024), 0, stream, q);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (g_lex_stop == 2) return EVOGP_OK;
+
+    // 4-5. the events
+    unsigned b = 0;
+    while (b < 32u && (1ull << b) < n_cases) ++b;
+    if (b & 1u) ++b;
+    LexEvents ev{errors, eps, members, rep, start, count, fp, p1, bits, winners, g_lex_counters, counter_base(seed, generation), n_cases, pop,
+                 n_events, b / 2u, L.words};
+    hipLaunchKernelGGL(lex_events_kernel, dim3(L.waves / kLexWavesPerBlock), dim3(64 * kLexWavesPerBlock), 0, stream, ev);
+    return (int)hipGetLastError();
+}
+
+// Measurement hook (include/evogp_hip_debug.h)
+extern "C" int evogp_hip_debug_lexicase(unsigned long long *device_counters, int stop_after) {
+    if (stop_after < 0 || stop_after > 2) return EVOGP_E_BADARG;
+    g_lex_counters = device_counters;
+    g_lex_stop = stop_after;
+    return EVOGP_OK;
+}

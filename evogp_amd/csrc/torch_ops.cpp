@@ -281,6 +281,46 @@ void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tens
              "tree_SR_const_step");
 }
 
+// case-major per-case errors (D, pop) of every tree (include/evogp_hip.h evogp_hip_sr_case_errors), validated like tree_batch_evaluate
+Tensor tree_SR_case_errors(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
+                           const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(var_len > 0 && out_len > 0 && data_points > 0, "var_len, out_len and data_points must be positive");
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor errors = at::empty({data_points, pop_size}, value.options());
+    check_rc(evogp_hip_sr_case_errors((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                      use_mse ? 1 : 0, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
+                                      variables.data_ptr<float>(), labels.data_ptr<float>(), errors.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_case_errors");
+    return errors;
+}
+
+// int32[n_events]: the winners of n_events epsilon-lexicase events over case-major errors (n, pop) (evogp_hip_lexicase_select); the
+// workspace comes from torch's caching allocator
+Tensor lexicase_select(const Tensor &errors, const Tensor &eps, int64_t n_events, int64_t seed, int64_t generation) {
+    TORCH_CHECK(errors.is_cuda() && errors.is_contiguous() && errors.scalar_type() == at::kFloat && errors.dim() == 2,
+                "errors must be a contiguous float32 CUDA tensor of shape (n_cases, pop)");
+    const int64_t n = errors.size(0), pop = errors.size(1);
+    TORCH_CHECK(n > 0 && pop > 0 && pop <= 0x7FFFFFFF, "errors must hold at least one case and one tree, got shape ", errors.sizes());
+    TORCH_CHECK(n_events >= 0 && n_events <= 0x7FFFFFFF, "n_events must be in [0, 2^31), but got ", n_events);
+    const c10::Device dev = errors.device();
+    check_tensor(eps, {n}, "eps", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor winners = at::empty({n_events}, at::TensorOptions().dtype(at::kInt).device(dev));
+    if (n_events == 0) return winners;
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_lexicase_workspace_bytes((unsigned)n, (unsigned)pop, (unsigned)n_events, &bytes), "lexicase_select");
+    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check_rc(evogp_hip_lexicase_select((unsigned)n, (unsigned)pop, errors.data_ptr<float>(), eps.data_ptr<float>(), (unsigned)n_events, seed,
+                                       generation, winners.data_ptr<int>(), ws.data_ptr(), current_stream(dev)),
+             "lexicase_select");
+    return winners;
+}
+
 Tensor3 tree_generate_offset(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len,
                              double out_prob, double const_prob, const Tensor &keys, const Tensor &depth2leaf_probs,
                              const Tensor &roulette_funcs, const Tensor &const_samples, int64_t tree_index_offset) {
@@ -717,6 +757,9 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor grad)");
     m.def("tree_SR_const_step(int phase, int out_len, Tensor(a!) value, Tensor node_type, Tensor subtree_size, Tensor(b!) value_cand,"
           " Tensor(c!) loss, Tensor(d!) grad, Tensor loss_cand, Tensor grad_cand, Tensor(e!) step) -> ()");
+    m.def("tree_SR_case_errors(int pop_size, int data_points, int gp_len, int var_len, int out_len, bool use_mse, Tensor value,"
+          " Tensor node_type, Tensor subtree_size, Tensor variables, Tensor labels) -> Tensor");
+    m.def("lexicase_select(Tensor errors, Tensor eps, int n_events, int seed, int generation) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -742,4 +785,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tournament_select", &tournament_select);
     m.impl("tree_SR_gradient", &tree_SR_gradient);
     m.impl("tree_SR_const_step", &tree_SR_const_step);
+    m.impl("tree_SR_case_errors", &tree_SR_case_errors);
+    m.impl("lexicase_select", &lexicase_select);
 }

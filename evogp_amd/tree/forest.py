@@ -7,7 +7,7 @@
 API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
 indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``optimize_constants`` (gradient descent on the constants,
-no counterpart in the reference).  Every heavy method is one call into
+no counterpart in the reference) and ``SR_case_errors`` (per-case errors for lexicase selection).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -190,6 +190,17 @@ class Forest:
         assert labels.shape == (n, self.output_len), (
             f"outputs shape should be ({n}, {self.output_len}), but got {labels.shape}")
         return inputs.contiguous().to(torch.float32), labels.contiguous().to(torch.float32)
+
+    def SR_case_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True) -> Tensor:
+        """Per-case errors ``(pop, D)``: entry ``[t, d]`` is the squared (``use_MSE``) or absolute error of tree t on row d, averaged
+        over the outputs, in float32 (NaN stays NaN).  The predictions are ``batch_forward``'s, bit for bit.  The tensor is the transposed
+        view of a case-major ``(D, pop)`` one (strides ``(1, pop)``): one case across many trees is contiguous, which is how lexicase
+        selection reads it (csrc/lexicase.hip).  Its mean over the rows is what ``SR_fitness`` returns, up to the fitness path's order
+        of summation."""
+        inputs, labels = self._sr_data(inputs, labels)
+        errors = torch.ops.evogp_hip.tree_SR_case_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
+                                                         use_MSE, *self._tensors(), inputs, labels)
+        return errors.t()
 
     def SR_gradient(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(loss, grad)``: ``loss`` (pop,) is what ``SR_fitness`` returns, ``grad`` (pop, max_tree_len) is d loss / d value at every

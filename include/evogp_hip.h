@@ -275,6 +275,38 @@ int evogp_hip_select_alternating(unsigned n, unsigned n_elite, unsigned n_keep, 
 int evogp_hip_tournament_select(unsigned n, unsigned n_tournaments, unsigned t_size, long long seed, long long generation,
                                 const float *fitness, int *winners, evogp_stream_t stream);
 
+/* Per-case errors of symbolic regression (no counterpart in the reference), CASE-MAJOR:
+ *     errors[d][t] = (sum_o delta_o) / out_len   in float32, o ascending,   delta_o = (tree_t(X[d])_o - y[d][o])^2 (use_mse) or |...|
+ * with the predictions of evogp_hip_batch_evaluate (the same interpreters): the errors are bit-identical to this formula applied to
+ * Forest.batch_forward's outputs, and NaN stays NaN.  variables: f32[D][var_len], labels: f32[D][out_len], errors: f32[D][pop_size].
+ * Argument contract and limits of evogp_hip_batch_evaluate.  The (pop_size, D, out_len) predictions go to an engine-owned buffer per
+ * stream (pop_size x D x out_len x 4 bytes), allocated by the first call of that size on the stream outside a stream capture (inside
+ * one: EVOGP_E_UNSUPPORTED) and freed by evogp_hip_release_workspaces. */
+int evogp_hip_sr_case_errors(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                             int use_mse, const float *value, const int16_t *type, const int16_t *size,
+                             const float *variables, const float *labels, float *errors, evogp_stream_t stream);
+
+/* Semi-dynamic epsilon-lexicase parent selection (no counterpart in the reference; La Cava, Helmuth, Spector & Moore 2019) over
+ * case-major errors E f32[n_cases][pop]:
+ *     key(x) = +inf if x is NaN, +0 if x is -0, else x;  eps[c]: NaN or negative counts as 0
+ *     trees i and j are CLONES when key(E[c][i]) == key(E[c][j]) bitwise for every case c
+ *     event k:  pool = all trees;  for j = 0, 1, ..., n_cases - 1 while the pool holds more than one clone class:
+ *                   c = perm_k(j);  m = min over the pool of key(E[c][i]);
+ *                   pool = {i in pool : key(E[c][i]) <= m + eps[c] (float32 add) or key(E[c][i]) == m}
+ *               L = the pool class by class (classes in ascending order of their smallest tree, each in ascending tree order)
+ *               winners[k] = L[word_k % len(L)]
+ * ("or == m" only matters when m + eps[c] is NaN, m = -inf and eps = +inf: the minimum always stays.)  perm_k is a 4-round Feistel
+ * network on the smallest even bit width w with 2^w >= n_cases, cycle-walked into [0, n_cases), evaluated position by position; its
+ * round key r is counter word (2^21 + r, k) of (seed, generation) and word_k is counter word (2^21 + 4, k) (the words of
+ * evogp_hip_random_words; the tournament uses rows 16 + k, k < 2^20).  Clones are found by a 64-bit hash of the key rows: a collision
+ * (probability about pop^2 / 2^65) merges two classes.  The result is deterministic; nothing synchronises with the host.
+ * n_events may be 0 (nothing is launched).  workspace: evogp_hip_lexicase_workspace_bytes bytes of device memory owned by the caller
+ * (no zeroing needed), at most about 2 x 4 n_cases pop + 60 pop bytes plus the radix sort's scratch; the engine allocates nothing.
+ * evogp_hip_lexicase_workspace_bytes queries the sort's scratch size on the current device. */
+int evogp_hip_lexicase_workspace_bytes(unsigned n_cases, unsigned pop, unsigned n_events, unsigned long long *bytes);
+int evogp_hip_lexicase_select(unsigned n_cases, unsigned pop, const float *errors, const float *eps, unsigned n_events,
+                              long long seed, long long generation, int *winners, void *workspace, evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -388,8 +420,9 @@ const char *evogp_hip_error_string(int code);
 int evogp_hip_set_sr_division(int mode);
 int evogp_hip_get_sr_division(void);
 
-/* ABI version of this header (6): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
- * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step). */
+/* ABI version of this header (7): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
+ * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
+ * evogp_hip_lexicase_select). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus

@@ -84,6 +84,12 @@ int evogp_hip_debug_point_mutate_given(int pop_size, int gp_len, int mode, int m
                                        const float *roulette_ufuncs, const float *roulette_bfuncs, const float *roulette_tfuncs,
                                        const float *const_samples, float *value_res, evogp_stream_t stream);
 
+/* Measurement hook of evogp_hip_lexicase_select (scripts/bench_lexicase.py).  device_counters != NULL: later calls ADD to
+ * device_counters[0..5] = {steps over all events, events, sum over cases of the first-pool size, largest first pool, clone classes,
+ * cases} (NULL: no counting, the default).  stop_after 1 / 2: later calls return after the clone classes / after the first pools,
+ * winners unwritten (stage timing); 0: the whole call (default).  Nothing else changes. */
+int evogp_hip_debug_lexicase(unsigned long long *device_counters, int stop_after);
+
 #ifdef __cplusplus
 }
 #endif
