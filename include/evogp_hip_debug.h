@@ -42,9 +42,12 @@ int evogp_hip_debug_long_compiler(int fast);
  * -1 = by the launch's trees per CU (DEFAULT: from 900 on; the environment variable EVOGP_TC_TWINS = 0 / 2 sets never / always before the
  * first call), 0 = never, 1 = always.  The fitness words do not depend on the choice (tests/test_gpu_tc_wide.py compares them bit for bit). */
 int evogp_hip_debug_twins(int mode);
-/* Whether the arithmetic line's packed compilers give a tree with a NaN constant operand of + - * / (a literal x / 0 among them) the one-word
- * program NAN_TREE instead of its instructions: -1 = back to the default / the environment (EVOGP_TC_FOLD = 0 turns
- * it off before the first call), 0 = off, 1 = on.  The fitness words do not depend on the choice (tests/test_gpu_fold.py). */
+/* Which trees the arithmetic line's packed compiler proves NaN in every row and gives the one-word program NAN_TREE instead of their
+ * instructions: 0 = none; 1 = trees with a NaN constant operand of + - * /, a literal x / 0 among them (constants
+ * as the compiler's two folding rounds find them); 2 = also trees with a division whose divisor is proved +-0 or NaN in every row without
+ * being such a constant -- x / (y * 0), x / (y - y), x / ((1 - 1) * y): the Z rule, three rounds of upward propagation; -1 = back to the
+ * default / the environment (EVOGP_TC_FOLD = 0, 1 or 2 before the first call; unset: 2).  The fitness words do not depend on the choice
+ * (tests/test_gpu_fold.py: 1 against 0, tests/test_gpu_zero_or_nan.py: 2 against 0). */
 int evogp_hip_debug_tc_fold(int mode);
 
 /* Handler histogram of the program records the most recent evogp_hip_sr_fitness call on the current device compiled:
