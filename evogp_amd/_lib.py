@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # EVOGP_HIP_LIB: alternative build of the same engine (A/B benchmarking of compiler flags only)
 LIB_PATH = os.environ.get("EVOGP_HIP_LIB") or os.path.join(_HERE, "lib", "libevogp_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _vp = C.c_void_p
 _u = C.c_uint
@@ -57,6 +57,9 @@ PROTOTYPES = {
     "evogp_hip_sr_case_errors": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_lexicase_workspace_bytes": [_u, _u, _u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_lexicase_select": [_u, _u, _vp, _vp, _u, C.c_longlong, C.c_longlong, _vp, _vp, _vp],
+    "evogp_hip_pareto_rank_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_pareto_rank": [_u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_nsga2_select": [_u, _vp, _u, _u, _u, C.c_longlong, C.c_longlong, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them
@@ -78,6 +81,7 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_insert_mutate_given": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_point_mutate_given": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_lexicase": [_vp, _i],
+    "evogp_hip_debug_pareto_rank": [_i],
 }
 
 

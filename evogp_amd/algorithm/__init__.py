@@ -1,7 +1,7 @@
 """evogp_amd.algorithm — genetic operators (reference: src/evogp/algorithm/): the default set, the rank / roulette /
-tournament / truncation selections, epsilon-lexicase selection over per-case errors (no counterpart in the reference), the
-diversity and leaf-biased crossovers, the structural and point mutations."""
-from .selection import (BaseSelection, BaseSelector, DefaultSelection, LexicaseSelection, RankSelection, RankSelector, RouletteSelection,
+tournament / truncation selections, epsilon-lexicase selection over per-case errors and NSGA-II selection on (error, complexity) (no counterpart in
+the reference), the diversity and leaf-biased crossovers, the structural and point mutations."""
+from .selection import (BaseSelection, BaseSelector, DefaultSelection, LexicaseSelection, NSGA2Selection, RankSelection, RankSelector, RouletteSelection,
                         RouletteSelector, TournamentSelection, TournamentSelector, TruncationSelection, TruncationSelector, lexicase_epsilon)
 from .crossover import BaseCrossover, CombinedDefaultCrossover, DefaultCrossover, DiversityCrossover, LeafBiasedCrossover
 from .mutation import (BaseMutation, CombinedDefaultMutation, CombinedMutation, DefaultMutation, DeleteMutation, HoistMutation, InsertMutation,
@@ -9,7 +9,7 @@ from .mutation import (BaseMutation, CombinedDefaultMutation, CombinedMutation, 
 from .genetic_programming import GeneticProgramming, ParetoFront
 
 __all__ = ["BaseSelection", "DefaultSelection", "RankSelection", "RouletteSelection", "TournamentSelection",
-           "TruncationSelection", "LexicaseSelection", "lexicase_epsilon", "BaseSelector", "RankSelector", "RouletteSelector", "TournamentSelector",
+           "TruncationSelection", "LexicaseSelection", "lexicase_epsilon", "NSGA2Selection", "BaseSelector", "RankSelector", "RouletteSelector", "TournamentSelector",
            "TruncationSelector", "BaseCrossover", "DefaultCrossover", "DiversityCrossover", "LeafBiasedCrossover", "BaseMutation",
            "DefaultMutation", "HoistMutation", "InsertMutation", "DeleteMutation", "SinglePointMutation",
            "MultiPointMutation", "SingleConstMutation", "MultiConstMutation", "CombinedMutation", "CombinedDefaultCrossover",

@@ -363,3 +363,81 @@ class LexicaseSelection(BaseSelection):
         else:
             elites = torch.empty(0, dtype=torch.int32, device=fitness.device)
         return elites, survivors
+
+
+# ---- NSGA-II on (error, complexity) (Deb, Pratap, Agarwal & Meyarivan 2002) -------------------------------------------------------
+# Counter-word rows of an NSGA2Selection's own seed: 2^22 + k contender k of tournament i (csrc/nsga2.hip).
+class NSGA2Selection(BaseSelection):
+    """Two-objective selection: error (``-fitness``) against an integer complexity, tree size by default.  Every call ranks the whole
+    population on the device -- non-dominated fronts, crowding distance over the distinct points of a front, and the crowded-comparison
+    order (front ascending, distance descending, tree index ascending) -- and holds ``tournament_size``-ary tournaments on that order
+    (include/evogp_hip.h evogp_hip_pareto_rank / evogp_hip_nsga2_select have the exact contract; tests/nsga2_ref.py restates it).
+    Trees of NaN or infinite fitness are unranked: they come last and are never preferred.  Clones of a point carry distance 0, so a
+    collapsed population does not fill the mating pool with copies.
+
+    ``elites = order[:n_elite]``.  ``mating_pool="all"``: the contenders are drawn from the whole population.  ``"elites"``: from the
+    elites only, which is NSGA-II proper -- with ``elite_rate=0.5`` the elites are the environmental selection of P and Q (last
+    generation's survivors and their offspring) and the parents are drawn among them.  ``complexity``: None for the tree size
+    (``batch_subtree_size[:, 0]``, bounded by ``max_tree_len``), or a callable ``complexity(forest) -> integer tensor`` together with
+    ``max_complexity`` (<= 65535), the bound the kernels size their tables by: it is never read back from the device, and a tree whose
+    complexity lies outside ``[0, max_complexity]`` is unranked.  The random numbers are counter words of a seed the object draws once
+    from torch's CPU generator (reproducible under torch.manual_seed) and of its own call counter.  Nothing in ``__call__``
+    synchronises with the host.  GPU forests only (the ops have no CPU kernel); not for a sharded run, whose selection sees no trees."""
+
+    def __init__(self, tournament_size: int = 2, survivor_rate: float = 1.0, elite_rate: float = 0.0, survivor_cnt: Optional[int] = None,
+                 elite_cnt: Optional[int] = None, complexity=None, mating_pool: str = "all", max_complexity: Optional[int] = None):
+        assert 1 <= tournament_size <= 2**20, f"tournament_size should be in [1, 2^20], but got {tournament_size}"
+        assert 0 <= survivor_rate <= 1, "survivor_rate should be in [0, 1]"
+        assert 0 <= elite_rate <= 1, "elite_rate should be in [0, 1]"
+        assert mating_pool in ("all", "elites"), f"mating_pool should be 'all' or 'elites', but got {mating_pool!r}"
+        assert complexity is None or callable(complexity), "complexity should be a callable forest -> integer tensor"
+        assert (complexity is None) == (max_complexity is None), "complexity and max_complexity should be given together"
+        assert max_complexity is None or 0 <= max_complexity <= 65535, f"max_complexity should be in [0, 65535], but got {max_complexity}"
+        self.t_size = tournament_size
+        self.survivor_rate, self.survivor_cnt = survivor_rate, survivor_cnt
+        self.elite_rate, self.elite_cnt = elite_rate, elite_cnt
+        self.complexity, self.max_complexity = complexity, max_complexity
+        self.mating_pool = mating_pool
+        self.seed = int(torch.randint(0, 2**40, (1,)).item())
+        self.generation = 0
+
+    def counts(self, pop_size: int):
+        n_surv = self.survivor_cnt if self.survivor_cnt is not None else int(pop_size * self.survivor_rate)
+        n_elite = self.elite_cnt if self.elite_cnt is not None else int(pop_size * self.elite_rate)
+        return n_elite, n_surv
+
+    def objectives(self, forest: Forest, fitness: torch.Tensor):
+        """-> (err float32[pop], cx int32[pop], cx_bound): what the ranking sees"""
+        if not isinstance(forest, Forest):
+            raise TypeError("NSGA2Selection reads every tree's complexity: it cannot run in a sharded step, whose selection sees only "
+                            "the gathered fitness vector")
+        err = (-fitness.to(torch.float32)).contiguous()
+        if self.complexity is None:
+            cx, bound = forest.batch_subtree_size[:, 0], forest.max_tree_len
+        else:
+            cx, bound = self.complexity(forest), self.max_complexity
+            assert isinstance(cx, torch.Tensor) and cx.shape == (forest.pop_size,) and not cx.dtype.is_floating_point and \
+                cx.dtype != torch.bool, f"complexity should return an integer tensor of shape ({forest.pop_size},)"
+        assert err.shape == (forest.pop_size,), f"fitness shape should be ({forest.pop_size}, ), but got {tuple(fitness.shape)}"
+        return err, cx.to(device=err.device, dtype=torch.int32).contiguous(), bound
+
+    def rank(self, forest: Forest, fitness: torch.Tensor):
+        """-> (front int32, crowding float32, order int32); an unranked tree has front 0x7FFFFFFF and crowding 0"""
+        return torch.ops.evogp_hip.pareto_rank(*self.objectives(forest, fitness))
+
+    def pareto_set(self, forest: Forest, fitness: torch.Tensor) -> torch.Tensor:
+        """bool[pop] on the device (no host sync): one tree per distinct (error, complexity) point of the first front -- the
+        accuracy / complexity trade-off curve of the population"""
+        front, crowding, _ = self.rank(forest, fitness)
+        return (front == 0) & (crowding > 0)
+
+    def __call__(self, forest: Forest, fitness: torch.Tensor):
+        err, cx, bound = self.objectives(forest, fitness)
+        pop = forest.pop_size
+        n_elite, n_surv = self.counts(pop)
+        pool = pop if self.mating_pool == "all" else n_elite
+        assert 1 <= pool <= pop, f"mating_pool='elites' needs between 1 and {pop} elites, but got {n_elite}"
+        _, _, order = torch.ops.evogp_hip.pareto_rank(err, cx, bound)
+        survivors = torch.ops.evogp_hip.nsga2_select(order, pool, n_surv, self.t_size, self.seed, self.generation)
+        self.generation += 1
+        return order[:n_elite], survivors

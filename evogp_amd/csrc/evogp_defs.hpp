@@ -66,7 +66,8 @@ struct Taus88 {
 // word k of item i of generation g under `seed` = the splitmix64 finaliser of (mix(seed * 1000003 + g) + (k << 40) + i), reduced to
 // [0, 2^31 - 1) like torch.randint(0, 2^31 - 1): evogp_amd/parallel.py random_words is the same arithmetic in torch ops.  Rows in
 // use: 0-5 the six words of offspring i (breed.hip), 7 the two generation keys (i = 0, 1), 16 + k contender k of tournament i,
-// 2^21 + r (r < 4) the Feistel round keys and 2^21 + 4 the pick of lexicase event i (lexicase.hip), 2^21 + 5 the down-sampled rows.
+// 2^21 + r (r < 4) the Feistel round keys and 2^21 + 4 the pick of lexicase event i (lexicase.hip), 2^21 + 5 the down-sampled rows,
+// 2^22 + k contender k of NSGA-II tournament i (nsga2.hip).
 __host__ __device__ inline unsigned long long mix64(unsigned long long x) {
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;

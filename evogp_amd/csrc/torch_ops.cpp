@@ -321,6 +321,48 @@ Tensor lexicase_select(const Tensor &errors, const Tensor &eps, int64_t n_events
     return winners;
 }
 
+// (front int32, crowding float32, order int32) of a population on (err, cx) (evogp_hip_pareto_rank); the workspace comes from torch's
+// caching allocator
+Tensor3 pareto_rank(const Tensor &err, const Tensor &cx, int64_t cx_bound) {
+    TORCH_CHECK(err.is_cuda() && err.is_contiguous() && err.scalar_type() == at::kFloat && err.dim() == 1,
+                "err must be a contiguous float32 CUDA vector");
+    const int64_t pop = err.size(0);
+    TORCH_CHECK(pop > 0 && pop < 0x7FFFFFFF, "err must hold at least one tree, got shape ", err.sizes());
+    TORCH_CHECK(cx_bound >= 0 && cx_bound <= 65535, "cx_bound must be in [0, 65535], but got ", cx_bound);
+    const c10::Device dev = err.device();
+    check_tensor(cx, {pop}, "cx", dev, at::kInt);
+    c10::DeviceGuard guard(dev);
+    Tensor front = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor crowding = at::empty({pop}, err.options());
+    Tensor order = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_pareto_rank_workspace_bytes((unsigned)pop, &bytes), "pareto_rank");
+    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check_rc(evogp_hip_pareto_rank((unsigned)pop, (unsigned)cx_bound, err.data_ptr<float>(), cx.data_ptr<int>(), front.data_ptr<int>(),
+                                   crowding.data_ptr<float>(), order.data_ptr<int>(), ws.data_ptr(), current_stream(dev)),
+             "pareto_rank");
+    return {front, crowding, order};
+}
+
+// int32[n]: the winners of n crowded-comparison tournaments among the first `pool` trees of a pareto_rank order (evogp_hip_nsga2_select)
+Tensor nsga2_select(const Tensor &order, int64_t pool, int64_t n, int64_t t_size, int64_t seed, int64_t generation) {
+    TORCH_CHECK(order.is_cuda() && order.is_contiguous() && order.scalar_type() == at::kInt && order.dim() == 1 && order.size(0) > 0,
+                "order must be a non-empty contiguous int32 CUDA vector");
+    const int64_t pop = order.size(0);
+    TORCH_CHECK(pop < 0x7FFFFFFF, "order is too long: ", pop);
+    TORCH_CHECK(pool >= 1 && pool <= pop, "pool must be in [1, ", pop, "], but got ", pool);
+    TORCH_CHECK(t_size >= 1 && t_size <= (1 << 20), "t_size must be in [1, 2^20], but got ", t_size);
+    TORCH_CHECK(n >= 0 && n <= 0x7FFFFFFF, "n must be in [0, 2^31), but got ", n);
+    const c10::Device dev = order.device();
+    c10::DeviceGuard guard(dev);
+    Tensor winners = at::empty({n}, at::TensorOptions().dtype(at::kInt).device(dev));
+    if (n == 0) return winners;
+    check_rc(evogp_hip_nsga2_select((unsigned)pop, order.data_ptr<int>(), (unsigned)pool, (unsigned)n, (unsigned)t_size, seed, generation,
+                                    winners.data_ptr<int>(), current_stream(dev)),
+             "nsga2_select");
+    return winners;
+}
+
 Tensor3 tree_generate_offset(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len,
                              double out_prob, double const_prob, const Tensor &keys, const Tensor &depth2leaf_probs,
                              const Tensor &roulette_funcs, const Tensor &const_samples, int64_t tree_index_offset) {
@@ -760,6 +802,8 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_SR_case_errors(int pop_size, int data_points, int gp_len, int var_len, int out_len, bool use_mse, Tensor value,"
           " Tensor node_type, Tensor subtree_size, Tensor variables, Tensor labels) -> Tensor");
     m.def("lexicase_select(Tensor errors, Tensor eps, int n_events, int seed, int generation) -> Tensor");
+    m.def("pareto_rank(Tensor err, Tensor cx, int cx_bound) -> (Tensor front, Tensor crowding, Tensor order)");
+    m.def("nsga2_select(Tensor order, int pool, int n, int t_size, int seed, int generation) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -787,4 +831,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_const_step", &tree_SR_const_step);
     m.impl("tree_SR_case_errors", &tree_SR_case_errors);
     m.impl("lexicase_select", &lexicase_select);
+    m.impl("pareto_rank", &pareto_rank);
+    m.impl("nsga2_select", &nsga2_select);
 }

@@ -307,6 +307,36 @@ int evogp_hip_lexicase_workspace_bytes(unsigned n_cases, unsigned pop, unsigned 
 int evogp_hip_lexicase_select(unsigned n_cases, unsigned pop, const float *errors, const float *eps, unsigned n_events,
                               long long seed, long long generation, int *winners, void *workspace, evogp_stream_t stream);
 
+/* Pareto ranking of a population on two objectives, both "lower is better" (no counterpart in the reference; Deb, Pratap, Agarwal &
+ * Meyarivan 2002): err f32[pop] and an integer complexity cx i32[pop] meant to lie in [0, cx_bound].  cx_bound <= 65535 is a HOST-side
+ * bound (max_tree_len for tree size); the kernels size their bucket table by it.
+ *     key(e) = +inf if e is NaN, +0 if e is -0, else e.  A tree is RANKED iff its key is finite and 0 <= cx <= cx_bound; a tree
+ *         outside the bound cannot be reported without a host sync, so it is unranked like a NaN tree
+ *     ranked q DOMINATES ranked p iff key_q <= key_p and cx_q <= cx_p and at least one is strict
+ *     front[p] = 0 if no ranked tree dominates p, else 1 + the largest front among the trees that dominate p; unranked: 0x7FFFFFFF
+ *     trees with bitwise equal (key, cx) are one POINT, its representative the lowest tree index
+ *     crowding[p], over the distinct points of p's front sorted by cx ascending (their keys then descend strictly): +inf for the
+ *         first and the last point; point j in between:
+ *             (cx[j+1] - cx[j-1]) / (cx_last - cx_first) + (key[j-1] - key[j+1]) / (key_first - key_last)
+ *         every operand float32, every operation one IEEE float32 operation in the order written, a NaN result counts as +inf.
+ *         Only the representative carries the distance: its clones and the unranked trees get 0
+ *     order i32[pop]: all trees by front ascending, then crowding descending, then tree index ascending (the crowded-comparison
+ *         operator as a total order); the unranked trees come last, in index order
+ * The result is deterministic and bit-identical from run to run (integer atomic maxima only); nothing synchronises with the host and
+ * the number of launches is fixed.  workspace: evogp_hip_pareto_rank_workspace_bytes(pop) bytes of device memory owned by the caller
+ * (no zeroing needed), about 84 pop bytes plus the radix sort's scratch; the engine allocates nothing. */
+int evogp_hip_pareto_rank_workspace_bytes(unsigned pop, unsigned long long *bytes);
+int evogp_hip_pareto_rank(unsigned pop, unsigned cx_bound, const float *err, const int *cx, int *front, float *crowding, int *order,
+                          void *workspace, evogp_stream_t stream);
+
+/* NSGA-II's binary (t_size-ary) tournament on an order of evogp_hip_pareto_rank: tournament i draws t_size contenders with replacement
+ * from the first `pool` trees of the order and the best by crowded comparison wins,
+ *     winners[i] = order[min over k < t_size of (word(seed, generation, 2^22 + k, i) mod pool)]
+ * with the counter words of evogp_hip_random_words (rows 2^22 + k collide with neither the tournaments' 16 + k nor lexicase's
+ * 2^21 + 0..5).  1 <= pool <= pop, 1 <= t_size <= 2^20; n_tournaments may be 0 (nothing is launched).  winners: i32[n_tournaments]. */
+int evogp_hip_nsga2_select(unsigned pop, const int *order, unsigned pool, unsigned n_tournaments, unsigned t_size, long long seed,
+                           long long generation, int *winners, evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -420,9 +450,9 @@ const char *evogp_hip_error_string(int code);
 int evogp_hip_set_sr_division(int mode);
 int evogp_hip_get_sr_division(void);
 
-/* ABI version of this header (7): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
+/* ABI version of this header (8): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
- * evogp_hip_lexicase_select). */
+ * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus

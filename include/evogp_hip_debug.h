@@ -93,6 +93,11 @@ int evogp_hip_debug_point_mutate_given(int pop_size, int gp_len, int mode, int m
  * winners unwritten (stage timing); 0: the whole call (default).  Nothing else changes. */
 int evogp_hip_debug_lexicase(unsigned long long *device_counters, int stop_after);
 
+/* Measurement hook of evogp_hip_pareto_rank (scripts/bench_nsga2.py).  stop_after 1 .. 4: later calls return after the key order /
+ * after the bucket order / after the fronts / after the crowding distances, the later outputs unwritten (stage timing); 0: the whole
+ * call (default).  Nothing else changes. */
+int evogp_hip_debug_pareto_rank(int stop_after);
+
 #ifdef __cplusplus
 }
 #endif
