@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # EVOGP_HIP_LIB: alternative build of the same engine (A/B benchmarking of compiler flags only)
 LIB_PATH = os.environ.get("EVOGP_HIP_LIB") or os.path.join(_HERE, "lib", "libevogp_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _vp = C.c_void_p
 _u = C.c_uint
@@ -60,6 +60,8 @@ PROTOTYPES = {
     "evogp_hip_pareto_rank_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_pareto_rank": [_u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_nsga2_select": [_u, _vp, _u, _u, _u, C.c_longlong, C.c_longlong, _vp, _vp],
+    "evogp_hip_sr_subtree_errors": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_prune_rows": [_u, _u, _u, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them

@@ -21,7 +21,7 @@
 // The tapes live in LDS for rows of at most kGradLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in an engine-owned global
 // workspace (engine_alloc_shared) for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
 // column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.
-#include "interp.hpp"
+#include "sr_forward.hpp"
 #include "launch.hpp"
 
 #include <mutex>
@@ -31,7 +31,6 @@ namespace evogp {
 
 constexpr int kGradLdsLen = 64;      // rows up to this length keep their tapes in LDS
 constexpr int kGradMaxWaves = 4;     // waves per workgroup (row tiles of one tree)
-constexpr uint32_t kOpMask = 0xFFu;  // operand-table word: handler id in bits 0..7, "operand k is a CONST node" in bit 8 + k
 
 struct GradParams {
     const float *value;
@@ -44,16 +43,6 @@ struct GradParams {
     float *tape;     // global tapes (rows longer than kGradLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len, out_len, use_mse;
 };
-
-__device__ inline float sign_of(float a) { return a > 0.0f ? 1.0f : a < 0.0f ? -1.0f : a == 0.0f ? 0.0f : a; }  // NaN stays NaN
-
-__device__ inline float binary_value(uint32_t op, float a, float b) {
-    if (op == H_ADD) return a + b;
-    if (op == H_SUB) return a - b;
-    if (op == H_MUL) return a * b;
-    if (op == H_DIV) return b == 0.0f ? __builtin_nanf("") : a / b;
-    return op_binary_other<false>(op, a, b);
-}
 
 // Partial adjoints of a binary node's operands: g is the adjoint of its result r = f(a, b).
 __device__ inline void binary_adjoint(uint32_t op, float a, float b, float r, float g, float &da, float &db) {
@@ -107,8 +96,6 @@ __device__ inline float unary_adjoint(uint32_t op, float a, float r, float g) {
     }
 }
 
-__device__ inline float grad_err(float diff, int use_mse) { return use_mse ? diff * diff : fabsf(diff); }
-
 // Dynamic LDS of one workgroup (16-byte aligned carve): op[L] kids[L] pay[L] stack[L] (u32), part[W][L], lpart[W], cls/len (2 words,
 // padded to 4), then, for LDS tapes, W x 2 x L x 64 floats.
 __host__ __device__ inline size_t grad_lds_head_words(int L, int W) { return (((size_t)4 * L + (size_t)W * L + W + 4) + 3) & ~(size_t)3; }
@@ -138,35 +125,7 @@ __global__ __launch_bounds__(kGradMaxWaves * 64) void sr_grad_kernel(GradParams 
             int len = uni((int)p.size[row]);
             len = len < 0 ? 0 : (len > L ? L : len);
             const int cls = uni(classify_tree(p.type + row, p.value + row, len, MO, p.var_len, p.out_len, kMaxStack));
-            if (cls == TREE_OK) {
-                for (int i = lane; i < len; i += kWave) {
-                    const Decoded d = decode_node(p.type[row + i], p.value[row + i], MO, p.var_len, p.out_len);
-                    s_op[i] = d.op;
-                    s_pay[i] = d.pay;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                int h = 0;
-                for (int i = len - 1; i >= 0; --i) {
-                    const uint32_t op = (uint32_t)uni((int)s_op[i]);
-                    const int arity = op < H_ADD ? 0 : op < H_UN ? 2 : op < H_IF ? 1 : 3;
-                    uint32_t kid = 0, flags = 0;
-                    for (int k = 0; k < arity; ++k) {
-                        const int c = uni(s_stk[h - 1 - k]);
-                        kid |= (uint32_t)c << (10 * k);
-                        if ((uni((int)s_op[c]) & kOpMask) == H_CONST) flags |= 1u << (8 + k);
-                    }
-                    h -= arity;
-                    if (lane == 0) {
-                        s_stk[h] = i;
-                        s_kid[i] = kid;
-                        s_op[i] = op | flags;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    ++h;
-                }
-            }
+            if (cls == TREE_OK) build_operand_table<MO>(p.type, p.value, row, len, p.var_len, p.out_len, s_op, s_kid, s_pay, s_stk);
             if (lane == 0) { s_meta[0] = cls; s_meta[1] = len; }
         }
         __syncthreads();
@@ -387,7 +346,7 @@ static std::mutex g_grad_mu;
 static std::vector<GradWorkspace> g_grad_ws[64];
 static std::vector<void *> g_grad_retired[64];
 
-static float *grad_workspace(hipStream_t stream, size_t bytes, int *rc) {
+float *grad_workspace(hipStream_t stream, size_t bytes, int *rc) {  // (sr_forward.hpp: sr_subtree.hip shares it)
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lock(g_grad_mu);

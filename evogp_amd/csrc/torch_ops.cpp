@@ -255,6 +255,52 @@ std::tuple<Tensor, Tensor> tree_SR_gradient(int64_t pop_size, int64_t data_point
     return {loss, grad};
 }
 
+// the loss of every subtree as a model of its own and its value where it is constant over the rows (evogp_hip_sr_subtree_errors)
+std::tuple<Tensor, Tensor> tree_SR_subtree_errors(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                  bool use_mse, const Tensor &value, const Tensor &type, const Tensor &size,
+                                                  const Tensor &variables, const Tensor &labels) {
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    TORCH_CHECK(out_len == 1, "tree_SR_subtree_errors: single-output trees only (out_len must be 1), but got ", out_len);
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor node_err = at::empty({pop_size, gp_len}, value.options());
+    Tensor node_const = at::empty({pop_size, gp_len}, value.options());
+    check_rc(evogp_hip_sr_subtree_errors((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                         use_mse ? 1 : 0, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
+                                         variables.data_ptr<float>(), labels.data_ptr<float>(), node_err.data_ptr<float>(),
+                                         node_const.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_subtree_errors");
+    return {node_err, node_const};
+}
+
+// hoist the best subtree, fold the row-constant ones (evogp_hip_prune_rows): a new forest, the chosen roots and their losses
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tree_prune(int64_t out_len, bool hoist, bool fold, const Tensor &value, const Tensor &type,
+                                                              const Tensor &size, const Tensor &node_err, const Tensor &node_const) {
+    TORCH_CHECK(out_len == 1, "tree_prune: single-output trees only (out_len must be 1), but got ", out_len);
+    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
+    const int64_t pop_size = value.size(0), gp_len = value.size(1);
+    check_sizes(pop_size, gp_len);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(node_err, {pop_size, gp_len}, "node_err", dev, at::kFloat);
+    check_tensor(node_const, {pop_size, gp_len}, "node_const", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor out_value = at::empty_like(value), out_type = at::empty_like(type), out_size = at::empty_like(size);
+    Tensor root_pos = at::empty({pop_size}, value.options().dtype(at::kInt));
+    Tensor loss = at::empty({pop_size}, value.options());
+    check_rc(evogp_hip_prune_rows((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_len, hoist ? 1 : 0, fold ? 1 : 0, value.data_ptr<float>(),
+                                  type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), node_err.data_ptr<float>(), node_const.data_ptr<float>(),
+                                  out_value.data_ptr<float>(), out_type.data_ptr<int16_t>(), out_size.data_ptr<int16_t>(),
+                                  root_pos.data_ptr<int>(), loss.data_ptr<float>(), current_stream(dev)),
+             "tree_prune");
+    return {out_value, out_type, out_size, root_pos, loss};
+}
+
 // one iteration of the constant descent, in place (include/evogp_hip.h evogp_hip_sr_const_step); phase 2 ignores loss_cand / grad_cand
 void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tensor &type, const Tensor &size, Tensor value_cand, Tensor loss,
                         Tensor grad, const Tensor &loss_cand, const Tensor &grad_cand, Tensor step) {
@@ -804,6 +850,10 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("lexicase_select(Tensor errors, Tensor eps, int n_events, int seed, int generation) -> Tensor");
     m.def("pareto_rank(Tensor err, Tensor cx, int cx_bound) -> (Tensor front, Tensor crowding, Tensor order)");
     m.def("nsga2_select(Tensor order, int pool, int n, int t_size, int seed, int generation) -> Tensor");
+    m.def("tree_SR_subtree_errors(int pop_size, int data_points, int gp_len, int var_len, int out_len, bool use_mse, Tensor value,"
+          " Tensor node_type, Tensor subtree_size, Tensor X, Tensor y) -> (Tensor node_err, Tensor node_const)");
+    m.def("tree_prune(int out_len, bool hoist, bool fold, Tensor value, Tensor node_type, Tensor subtree_size, Tensor node_err,"
+          " Tensor node_const) -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor root_pos, Tensor loss)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -833,4 +883,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("lexicase_select", &lexicase_select);
     m.impl("pareto_rank", &pareto_rank);
     m.impl("nsga2_select", &nsga2_select);
+    m.impl("tree_SR_subtree_errors", &tree_SR_subtree_errors);
+    m.impl("tree_prune", &tree_prune);
 }

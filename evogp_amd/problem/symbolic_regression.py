@@ -19,14 +19,19 @@ class SymbolicRegression(BaseProblem):
     def __init__(self, datapoints: Optional[Tensor] = None, labels: Optional[Tensor] = None,
                  func: Optional[Callable] = None, num_inputs: Optional[int] = None, num_data: Optional[int] = 100,
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
-                 const_step_size: float = 0.1):
+                 const_step_size: float = 0.1, simplify_every: int = 0):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
-        gradient descent (``Forest.optimize_constants``), and StandardPipeline scores the optimised forest (Lamarckian)."""
+        gradient descent (``Forest.optimize_constants``), and StandardPipeline scores the optimised forest (Lamarckian).
+        ``simplify_every`` = k > 0 (single-output problems): every k-th call of ``optimize`` first rewrites the forest with
+        ``Forest.simplify`` (best subtree hoisted, row-constant subtrees folded), so the smaller trees are the ones scored and bred."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
         self.const_opt_steps = int(const_opt_steps)
         self.const_step_size = float(const_step_size)
+        assert simplify_every >= 0, f"simplify_every should be >= 0, but got {simplify_every}"
+        self.simplify_every = int(simplify_every)
+        self._optimize_calls = 0
         if datapoints is not None and labels is not None:
             self.datapoints, self.labels = datapoints, labels
             return
@@ -68,8 +73,12 @@ class SymbolicRegression(BaseProblem):
         return torch.where(torch.isnan(f), torch.full_like(f, float("-inf")), f)
 
     def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:
-        """``forest`` with its constants tuned by ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest
-        itself when ``const_opt_steps`` is 0)."""
+        """``forest`` simplified (``Forest.simplify``, on every ``simplify_every``-th call) and then with its constants tuned by
+        ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest itself when both are 0)."""
+        if self.simplify_every > 0:
+            self._optimize_calls += 1
+            if self._optimize_calls % self.simplify_every == 0:
+                forest = forest.simplify(self.datapoints, self.labels, use_MSE)[0]
         if self.const_opt_steps <= 0:
             return forest
         return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE)[0]

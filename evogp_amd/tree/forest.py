@@ -7,7 +7,8 @@
 API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
 indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``optimize_constants`` (gradient descent on the constants,
-no counterpart in the reference) and ``SR_case_errors`` (per-case errors for lexicase selection).  Every heavy method is one call into
+no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection) and ``SR_subtree_errors`` / ``simplify``
+(the loss of every subtree, and the rewrite into a smaller tree that is no worse).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -233,6 +234,37 @@ class Forest:
         forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
                         func_mask=self.func_mask)
         return forest, loss
+
+    def _single_output(self, what: str):
+        assert self.output_len == 1, f"{what} works on single-output trees only, but output_len is {self.output_len}"
+
+    def SR_subtree_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
+        """``(node_err, node_const)``, both (pop, max_tree_len): ``node_err[t, i]`` is the loss the subtree rooted at node i of tree t
+        would have as a model of its own (what ``SR_fitness`` returns for it as a row of its own; ``node_err[:, 0]`` is the tree's
+        loss), ``node_const[t, i]`` is the value of that subtree when it has one and the same float32 bit pattern on every row of
+        ``inputs`` and NaN otherwise (a NaN is never "constant").  Tail entries and malformed trees are NaN.  One forward pass per
+        tree over every row (csrc/sr_subtree.hip); single-output forests only."""
+        self._single_output("SR_subtree_errors")
+        inputs, labels = self._sr_data(inputs, labels)
+        return torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
+                                                          use_MSE, *self._tensors(), inputs, labels)
+
+    def simplify(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, hoist: bool = True, fold_constants: bool = True):
+        """``(forest, loss)``: every tree rewritten into a tree that is no larger and, on this dataset, no worse, in two launches with
+        no host synchronisation.  ``hoist``: the tree becomes its subtree of least finite error (then least size, then least index),
+        so a tree that is NaN as a whole but has a finite subtree is rescued.  ``fold_constants``: every function node whose subtree
+        takes one finite float32 value on every row becomes a CONST node of that value (the outermost such node wins); the rewritten
+        tree computes bit-identical values on every row of ``inputs``.  Returns a new Forest (this one is untouched) and the loss of
+        each returned tree (``node_err`` at the chosen root).  Simplifying the result again returns it unchanged."""
+        self._single_output("simplify")
+        inputs, labels = self._sr_data(inputs, labels)
+        value, ntype, size = self._tensors()
+        node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
+                                                                          self.output_len, use_MSE, value, ntype, size, inputs, labels)
+        value, ntype, size, _, loss = torch.ops.evogp_hip.tree_prune(self.output_len, bool(hoist), bool(fold_constants), value, ntype, size,
+                                                                     node_err, node_const)
+        # (a rewritten tree's functions are a subset of the old tree's)
+        return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), loss
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

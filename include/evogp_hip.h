@@ -121,6 +121,37 @@ int evogp_hip_sr_const_step(unsigned pop_size, unsigned gp_len, unsigned out_len
                             const int16_t *size, float *value_cand, float *loss, float *grad, const float *loss_cand,
                             const float *grad_cand, float *step, evogp_stream_t stream);
 
+/* The loss of every SUBTREE of every single-output tree as a model of its own, and whether the subtree is constant over the dataset
+ * (no counterpart in the reference).  Inputs as evogp_hip_sr_gradient with out_len == 1 (any other out_len:
+ * EVOGP_E_BADARG).  Both outputs f32[pop_size][gp_len]:
+ *   node_err[t][i]    (1 / D) * sum_d err(y[d] - v_i(X[d])) for i < len, v_i the value of the subtree rooted at node i: what
+ *                     evogp_hip_sr_fitness returns for that subtree as a row of its own (NaN and inf propagate as there);
+ *                     node_err[t][0] is the loss evogp_hip_sr_gradient returns, bit for bit;
+ *   node_const[t][i]  c when v_i(X[d]) has the bit pattern of c on every row d and c is not a NaN (so -0.0 and 0.0 differ, and a
+ *                     CONST leaf reports its value, a VAR leaf only that of a constant column); NaN otherwise.
+ * Tail entries [len, gp_len) and every entry of a malformed tree (the trees evogp_hip_sr_gradient gives a NaN loss) are NaN.  Sums run
+ * in a fixed order (bit-identical results from run to run).  Rows of more than 64 nodes use the per-stream tape buffer of
+ * evogp_hip_sr_gradient, under the same rules. */
+int evogp_hip_sr_subtree_errors(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                int use_mse, const float *value, const int16_t *type, const int16_t *size,
+                                const float *variables, const float *labels, float *node_err, float *node_const,
+                                evogp_stream_t stream);
+
+/* Rewrite every single-output tree into a tree that is no larger and, on the data node_err / node_const were computed from, no worse
+ * (out_len != 1: EVOGP_E_BADARG).  The rule reads only its inputs, in integer and fp32 comparisons (tests/subtree_ref.py restates it):
+ *   s(i)    = size[t][i] kept inside [1, len - i];  a node "folds" when `fold` is set, its type is neither VAR nor CONST and
+ *             node_const[t][i] is finite;
+ *   hoist   r = the node of [0, len) whose node_err is finite and least, then of least s, then of least index; 0 when `hoist` is
+ *             not set or no node has a finite error;
+ *   fold    inside [r, r + s(r)) every node strictly inside the span of a folding node is dropped (the outermost folding node wins) and
+ *             every folding node that is left becomes one CONST node of value node_const[t][i] and size 1;
+ *   output  the nodes that are left, in order from position 0; the size of a kept node = the number of nodes left in its old span;
+ *           [new_len, gp_len) is zero in all three arrays; root_pos[t] = r; loss[t] = node_err[t][r].
+ * A malformed tree's row is copied as it is, with root_pos 0 and a NaN loss.  The outputs must not alias the inputs. */
+int evogp_hip_prune_rows(unsigned pop_size, unsigned gp_len, unsigned out_len, int hoist, int fold, const float *value,
+                         const int16_t *type, const int16_t *size, const float *node_err, const float *node_const,
+                         float *out_value, int16_t *out_type, int16_t *out_size, int *root_pos, float *loss, evogp_stream_t stream);
+
 /* evogp_hip_generate restricted to the trees n with (unsigned)active_word[n] < active_below (active_word == NULL: all of
  * them).  Rows of the other trees are not touched.  Used by the fused generation step: donors are only produced for
  * the offspring that will mutate. */
@@ -450,9 +481,10 @@ const char *evogp_hip_error_string(int code);
 int evogp_hip_set_sr_division(int mode);
 int evogp_hip_get_sr_division(void);
 
-/* ABI version of this header (8): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
+/* ABI version of this header (9): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
- * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select). */
+ * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
+ * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
