@@ -62,6 +62,8 @@ PROTOTYPES = {
     "evogp_hip_nsga2_select": [_u, _vp, _u, _u, _u, C.c_longlong, C.c_longlong, _vp, _vp],
     "evogp_hip_sr_subtree_errors": [_u, _u, _u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_prune_rows": [_u, _u, _u, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_normal_eq": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_lm_step": [_u, _u, _u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them

@@ -1,4 +1,4 @@
-// sr_forward.hpp — what the tape kernels (sr_grad.hip, sr_subtree.hip) share: the value of a node from its operands' values, the
+// sr_forward.hpp — what the tape kernels (sr_grad.hip, sr_lm.hip, sr_subtree.hip) share: the value of a node from its operands' values, the
 // per-row error, and the OPERAND TABLE wave 0 of a workgroup builds for its tree (for every function node the indices of the nodes
 // whose pushed values it pops).  The forward semantics are run_general's (interp.hpp).
 #pragma once

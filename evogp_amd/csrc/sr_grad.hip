@@ -21,7 +21,7 @@
 // The tapes live in LDS for rows of at most kGradLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in an engine-owned global
 // workspace (engine_alloc_shared) for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
 // column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.
-#include "sr_forward.hpp"
+#include "sr_adjoint.hpp"
 #include "launch.hpp"
 
 #include <mutex>
@@ -43,58 +43,6 @@ struct GradParams {
     float *tape;     // global tapes (rows longer than kGradLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len, out_len, use_mse;
 };
-
-// Partial adjoints of a binary node's operands: g is the adjoint of its result r = f(a, b).
-__device__ inline void binary_adjoint(uint32_t op, float a, float b, float r, float g, float &da, float &db) {
-    da = 0.0f; db = 0.0f;
-    switch (op) {
-    case H_ADD: da = g; db = g; break;
-    case H_SUB: da = g; db = -g; break;
-    case H_MUL: da = g * b; db = g * a; break;
-    case H_DIV: da = g / b; db = -g * r / b; break;  // (r is NaN when b == 0)
-    case H_BIN_OTHER + (F_LOOSE_DIV - F_LOOSE_DIV): {
-        const bool tiny = fabsf(b) <= kDelta;
-        const float d = tiny ? copysignf(kDelta, b) : b;
-        da = g / d;
-        db = tiny ? 0.0f : -g * r / d;
-        break;
-    }
-    case H_BIN_OTHER + (F_POW - F_LOOSE_DIV):
-        da = g * b * powf(a, b - 1.0f);
-        db = a > 0.0f ? g * r * logf(a) : 0.0f;
-        break;
-    case H_BIN_OTHER + (F_LOOSE_POW - F_LOOSE_DIV): {
-        const float m = fabsf(a);
-        da = (a == 0.0f && b == 0.0f) ? 0.0f : g * b * powf(m, b - 1.0f) * sign_of(a);
-        db = m > 0.0f ? g * r * logf(m) : 0.0f;
-        break;
-    }
-    case H_BIN_OTHER + (F_MAX - F_LOOSE_DIV): if (a >= b) da = g; else db = g; break;
-    case H_BIN_OTHER + (F_MIN - F_LOOSE_DIV): if (a <= b) da = g; else db = g; break;
-    default: break;  // LT GT LE GE, unknown ids: 0
-    }
-}
-
-__device__ inline float unary_adjoint(uint32_t op, float a, float r, float g) {
-    switch (op) {
-    case H_UN + (F_SIN - F_SIN): return g * cosf(a);
-    case H_UN + (F_COS - F_SIN): return -g * sinf(a);
-    case H_UN + (F_TAN - F_SIN): return g * (1.0f + r * r);
-    case H_UN + (F_SINH - F_SIN): return g * coshf(a);
-    case H_UN + (F_COSH - F_SIN): return g * sinhf(a);
-    case H_UN + (F_TANH - F_SIN): return g * (1.0f - r * r);
-    case H_UN + (F_LOG - F_SIN): return g / a;
-    case H_UN + (F_LOOSE_LOG - F_SIN): return a == 0.0f ? 0.0f : g / a;
-    case H_UN + (F_EXP - F_SIN): return g * r;
-    case H_UN + (F_INV - F_SIN): return a == 0.0f ? __builtin_nanf("") : -g * r * r;
-    case H_UN + (F_LOOSE_INV - F_SIN): return fabsf(a) <= kDelta ? 0.0f : -g * r * r;
-    case H_UN + (F_NEG - F_SIN): return -g;
-    case H_UN + (F_ABS - F_SIN): return g * sign_of(a);
-    case H_UN + (F_SQRT - F_SIN): return g * 0.5f / r;
-    case H_UN + (F_LOOSE_SQRT - F_SIN): return a == 0.0f ? 0.0f : g * 0.5f / r * sign_of(a);
-    default: return 0.0f;  // unknown ids
-    }
-}
 
 // Dynamic LDS of one workgroup (16-byte aligned carve): op[L] kids[L] pay[L] stack[L] (u32), part[W][L], lpart[W], cls/len (2 words,
 // padded to 4), then, for LDS tapes, W x 2 x L x 64 floats.

@@ -327,6 +327,53 @@ void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tens
              "tree_SR_const_step");
 }
 
+// loss and Gauss-Newton normal equations of every single-output tree (include/evogp_hip.h evogp_hip_sr_normal_eq)
+std::tuple<Tensor, Tensor> tree_SR_normal_eq(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                             const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                             const Tensor &labels) {
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    TORCH_CHECK(out_len == 1, "tree_SR_normal_eq: single-output trees only (out_len must be 1), but got ", out_len);
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor loss = at::empty({pop_size}, value.options());
+    Tensor normal = at::empty({pop_size, (int64_t)EVOGP_LM_NORMAL_WORDS}, value.options());
+    check_rc(evogp_hip_sr_normal_eq((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                    value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), variables.data_ptr<float>(),
+                                    labels.data_ptr<float>(), loss.data_ptr<float>(), normal.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_normal_eq");
+    return {loss, normal};
+}
+
+// one Levenberg-Marquardt iteration on the constants, in place (include/evogp_hip.h evogp_hip_sr_lm_step); phase 2 ignores loss_cand / normal_cand
+void tree_SR_lm_step(int64_t phase, Tensor value, const Tensor &type, const Tensor &size, Tensor value_cand, Tensor loss, Tensor normal,
+                     const Tensor &loss_cand, const Tensor &normal_cand, Tensor damping) {
+    TORCH_CHECK(phase >= 1 && phase <= 3, "phase must be 1, 2 or 3, but got ", phase);
+    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
+    const int64_t pop_size = value.size(0), gp_len = value.size(1), words = EVOGP_LM_NORMAL_WORDS;
+    check_sizes(pop_size, gp_len);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(value_cand, {pop_size, gp_len}, "value_cand", dev, at::kFloat);
+    check_tensor(loss, {pop_size}, "loss", dev, at::kFloat);
+    check_tensor(normal, {pop_size, words}, "normal", dev, at::kFloat);
+    check_tensor(damping, {pop_size}, "damping", dev, at::kFloat);
+    if (phase & 1) {
+        check_tensor(loss_cand, {pop_size}, "loss_cand", dev, at::kFloat);
+        check_tensor(normal_cand, {pop_size, words}, "normal_cand", dev, at::kFloat);
+    }
+    c10::DeviceGuard guard(dev);
+    check_rc(evogp_hip_sr_lm_step((unsigned)pop_size, (unsigned)gp_len, 1u, (int)phase, value.data_ptr<float>(), type.data_ptr<int16_t>(),
+                                  size.data_ptr<int16_t>(), value_cand.data_ptr<float>(), loss.data_ptr<float>(), normal.data_ptr<float>(),
+                                  (phase & 1) ? loss_cand.data_ptr<float>() : nullptr, (phase & 1) ? normal_cand.data_ptr<float>() : nullptr,
+                                  damping.data_ptr<float>(), current_stream(dev)),
+             "tree_SR_lm_step");
+}
+
 // case-major per-case errors (D, pop) of every tree (include/evogp_hip.h evogp_hip_sr_case_errors), validated like tree_batch_evaluate
 Tensor tree_SR_case_errors(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                            const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
@@ -854,6 +901,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor node_type, Tensor subtree_size, Tensor X, Tensor y) -> (Tensor node_err, Tensor node_const)");
     m.def("tree_prune(int out_len, bool hoist, bool fold, Tensor value, Tensor node_type, Tensor subtree_size, Tensor node_err,"
           " Tensor node_const) -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor root_pos, Tensor loss)");
+    m.def("tree_SR_normal_eq(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor normal)");
+    m.def("tree_SR_lm_step(int phase, Tensor(a!) value, Tensor node_type, Tensor subtree_size, Tensor(b!) value_cand, Tensor(c!) loss,"
+          " Tensor(d!) normal, Tensor loss_cand, Tensor normal_cand, Tensor(e!) damping) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -885,4 +936,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("nsga2_select", &nsga2_select);
     m.impl("tree_SR_subtree_errors", &tree_SR_subtree_errors);
     m.impl("tree_prune", &tree_prune);
+    m.impl("tree_SR_normal_eq", &tree_SR_normal_eq);
+    m.impl("tree_SR_lm_step", &tree_SR_lm_step);
 }

@@ -6,8 +6,8 @@
 
 API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
-indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``optimize_constants`` (gradient descent on the constants,
-no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection) and ``SR_subtree_errors`` / ``simplify``
+indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
+descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection) and ``SR_subtree_errors`` / ``simplify``
 (the loss of every subtree, and the rewrite into a smaller tree that is no worse).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
@@ -32,6 +32,7 @@ from .tree import Tree
 from .utils import NType, check_tensor
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
+LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
 
 
@@ -210,12 +211,55 @@ class Forest:
         return torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
                                                     use_MSE, *self._tensors(), inputs, labels)
 
-    def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True):
-        """``(forest, loss)``: ``steps`` iterations of a per-tree gradient descent on the constants ("bold driver": a step of length
-        h along -grad / |grad| is kept only if it lowers the tree's loss, and h then doubles; otherwise h halves), all on the device
-        with no host synchronisation (2 launches per step).  Returns a new Forest (this one is untouched) whose trees differ from these
-        only in constant values, and the loss of each returned tree.  No tree's loss rises."""
+    def SR_normal_equations(self, inputs: Tensor, labels: Tensor):
+        """``(loss, A, b, const_index)`` of the Gauss-Newton model of the MSE loss in each tree's OPTIMISED constants: its first
+        ``min(nc, K)`` CONST nodes in prefix order, ``K = LM_MAX_CONSTS = 8`` (further constants are held fixed).  With ``J`` the per-row
+        Jacobian of the prediction in those constants and ``r = pred - y``: ``A = J^T J / D`` (pop, K, K), symmetric; ``b = J^T r / D``
+        (pop, K), half the gradient of the loss; ``loss`` (pop,) is ``SR_gradient``'s; ``const_index`` (pop, K) int64 is the node position
+        of each optimised constant, -1 where the tree has fewer.  Rows and columns of absent constants are exactly 0.  Malformed
+        trees: NaN loss, zero ``A`` and ``b``.  One HIP pass (csrc/sr_lm.hip); single-output forests only."""
+        self._single_output("SR_normal_equations")
+        inputs, labels = self._sr_data(inputs, labels)
+        value, ntype, size = self._tensors()
+        loss, normal = torch.ops.evogp_hip.tree_SR_normal_eq(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
+                                                             value, ntype, size, inputs, labels)
+        K = LM_MAX_CONSTS
+        iu = torch.triu_indices(K, K, device=normal.device)   # row-major upper triangle: the packed order
+        tri = normal[:, :iu.shape[1]]
+        A = normal.new_zeros((self.pop_size, K, K))
+        A[:, iu[0], iu[1]] = tri
+        A[:, iu[1], iu[0]] = tri
+        b = normal[:, iu.shape[1]:].clone()
+        L = self.max_tree_len
+        pos = torch.arange(L, device=value.device)[None, :]
+        is_c = (ntype == NType.CONST) & (pos < size[:, :1].clamp(0, L))
+        first = torch.where(is_c, pos, L).sort(dim=1).values[:, :K]
+        const_index = torch.where(first < L, first, -1)
+        if L < K:
+            const_index = torch.nn.functional.pad(const_index, (0, K - L), value=-1)
+        return loss, A, b, const_index
+
+    def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True,
+                           method: str = "descent", damping: float = 1e-3):
+        """``(forest, loss)``: ``steps`` iterations of a per-tree optimisation of the constants, all on the device with no host
+        synchronisation (2 launches per step).  Returns a new Forest (this one is untouched) whose trees differ from these only in
+        constant values, and the loss of each returned tree.  No tree's loss rises.
+
+        ``method="descent"``: gradient descent ("bold driver": a step of length h along -grad / |grad|, h starting at ``step_size``, is
+        kept only if it lowers the tree's loss, and h then doubles; otherwise h halves).  ``method="lm"`` (MSE, single-output forests):
+        Levenberg-Marquardt on the tree's first 8 constants in prefix order (further constants keep their values): the step solves
+        ``(A + lambda diag A) delta = -b`` on the normal equations of ``SR_normal_equations`` and is kept only if it lowers the loss;
+        lambda starts at ``damping``, falls tenfold after a kept step and rises tenfold after a rejected one.  A model that is linear
+        in its constants is solved in one to three steps."""
         assert steps >= 0, f"steps should be >= 0, but got {steps}"
+        if method not in ("descent", "lm"):
+            raise ValueError(f"method should be 'descent' or 'lm', but got {method!r}")
+        if method == "lm":
+            if not use_MSE:
+                raise ValueError("method='lm' minimises the mean squared error: use_MSE must be True")
+            if self.output_len != 1:
+                raise ValueError(f"method='lm' works on single-output trees only, but output_len is {self.output_len}")
+            return self._optimize_constants_lm(inputs, labels, steps, damping)
         inputs, labels = self._sr_data(inputs, labels)
         n = inputs.shape[0]
         value, ntype, size = self._tensors()
@@ -231,6 +275,24 @@ class Forest:
                 loss_c, grad_c = torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len,
                                                                       use_MSE, cand, ntype, size, inputs, labels)
                 step_op(3 if k + 1 < steps else 1, self.output_len, value, ntype, size, cand, loss, grad, loss_c, grad_c, step)
+        forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
+                        func_mask=self.func_mask)
+        return forest, loss
+
+    def _optimize_constants_lm(self, inputs: Tensor, labels: Tensor, steps: int, damping: float):
+        inputs, labels = self._sr_data(inputs, labels)
+        value, ntype, size = self._tensors()
+        value = value.clone()
+        shape = (self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len)
+        normal_eq, step_op = torch.ops.evogp_hip.tree_SR_normal_eq, torch.ops.evogp_hip.tree_SR_lm_step
+        loss, normal = normal_eq(*shape, value, ntype, size, inputs, labels)
+        if steps > 0:
+            cand = torch.empty_like(value)
+            lam = torch.full((self.pop_size,), float(damping), dtype=torch.float32, device=value.device)
+            step_op(2, value, ntype, size, cand, loss, normal, loss, normal, lam)
+            for k in range(steps):
+                loss_c, normal_c = normal_eq(*shape, cand, ntype, size, inputs, labels)
+                step_op(3 if k + 1 < steps else 1, value, ntype, size, cand, loss, normal, loss_c, normal_c, lam)
         forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
                         func_mask=self.func_mask)
         return forest, loss

@@ -41,6 +41,8 @@ extern "C" {
 #define EVOGP_MAX_STACK 1024      /* defs.h:5  — upper bound on gp_len                     */
 #define EVOGP_MAX_FULL_DEPTH 10   /* defs.h:5  — length of depth2leaf_probs                */
 #define EVOGP_NUM_FUNCS 29        /* defs.h:56 — Function::END, length of roulette_funcs   */
+#define EVOGP_LM_MAX_CONSTS 8     /* K: constants per tree evogp_hip_sr_normal_eq / evogp_hip_sr_lm_step optimise */
+#define EVOGP_LM_NORMAL_WORDS (EVOGP_LM_MAX_CONSTS * (EVOGP_LM_MAX_CONSTS + 1) / 2 + EVOGP_LM_MAX_CONSTS) /* 44: a row of `normal` */
 
 /* negative return codes (argument errors detected on the host before any launch) */
 #define EVOGP_E_BADARG (-1)       /* size/shape argument out of the range the reference's wrapper accepts */
@@ -120,6 +122,38 @@ int evogp_hip_sr_gradient(unsigned pop_size, unsigned data_points, unsigned gp_l
 int evogp_hip_sr_const_step(unsigned pop_size, unsigned gp_len, unsigned out_len, int phase, float *value, const int16_t *type,
                             const int16_t *size, float *value_cand, float *loss, float *grad, const float *loss_cand,
                             const float *grad_cand, float *step, evogp_stream_t stream);
+
+/* Gauss-Newton normal equations of the MSE loss in the constants of every single-output tree (no counterpart in the reference;
+ * DESIGN.md section 3.11).  Inputs as evogp_hip_sr_gradient with out_len == 1 (any other out_len: EVOGP_E_BADARG).  The OPTIMISED
+ * CONSTANTS of a tree are its first min(nc, K) CONST nodes in prefix order within the live prefix, K = EVOGP_LM_MAX_CONSTS = 8; any
+ * further constant is held fixed.  With J_j[d] = d pred[d] / d c_j (one reverse walk seeded with 1, the adjoint rules of the
+ * "Constant gradients" table) and r[d] = pred[d] - y[d]:
+ *   loss[t]    = (1 / D) * sum_d r[d]^2, summed in the order of evogp_hip_sr_gradient's loss;
+ *   normal[t]  = f32[44]: the 36 entries A_ij = (1 / D) * sum_d J_i[d] * J_j[d], i <= j < K, row-major (A_00 .. A_07, A_11 .. A_17,
+ *                ..., A_77), then the 8 entries b_i = (1 / D) * sum_d J_i[d] * r[d] (half the gradient of the loss).  Every entry
+ *                that involves an absent constant (index >= nc) is exactly 0.0f.
+ * A malformed tree gets a NaN loss and a zero row.  Sums run in a fixed order (bit-identical results from run to run).  Rows of more
+ * than 64 nodes use the per-stream tape buffer of evogp_hip_sr_gradient, under the same rules. */
+int evogp_hip_sr_normal_eq(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                           const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                           const float *labels, float *loss, float *normal, evogp_stream_t stream);
+
+/* One iteration of the per-tree Levenberg-Marquardt optimisation of the constants on the device, with no host synchronisation
+ * (out_len != 1: EVOGP_E_BADARG).  Per tree t: value / loss / normal hold the current constants, their loss and their normal
+ * equations (evogp_hip_sr_normal_eq), damping the factor lambda_t (f32[pop_size]).  phase as in evogp_hip_sr_const_step:
+ *   phase & 1  accept: if loss_cand[t] < loss[t] (a NaN never accepts) the optimised constants of value_cand are copied to value,
+ *              loss[t] = loss_cand[t], the normal row = the normal_cand row and lambda_t = max(lambda_t / 10, 1e-10); otherwise
+ *              lambda_t = min(10 * lambda_t, 1e10).
+ *   phase & 2  propose (after the accept): value_cand row = value row with the optimised constants c -> c + delta, where delta solves
+ *              (A + lambda_t * diag(A)) delta = -b over the constants with A_ii != 0 (Cholesky in float64; a constant with
+ *              A_ii == 0 has no influence and keeps its value).  The row is copied unchanged when loss[t] is not finite or is 0, an
+ *              entry of A or b among those constants is not finite, a pivot is <= 0, or some c + delta is not finite in float32.
+ * Neither type nor size nor any other word of value is written; every word of the value_cand row is.  An optimisation of S steps:
+ * evogp_hip_sr_normal_eq on value, phase 2, then S times {evogp_hip_sr_normal_eq on value_cand -> loss_cand / normal_cand, phase 3
+ * (the last one: phase 1)}.  loss_cand / normal_cand may be NULL when phase is 2. */
+int evogp_hip_sr_lm_step(unsigned pop_size, unsigned gp_len, unsigned out_len, int phase, float *value, const int16_t *type,
+                         const int16_t *size, float *value_cand, float *loss, float *normal, const float *loss_cand,
+                         const float *normal_cand, float *damping, evogp_stream_t stream);
 
 /* The loss of every SUBTREE of every single-output tree as a model of its own, and whether the subtree is constant over the dataset
  * (no counterpart in the reference).  Inputs as evogp_hip_sr_gradient with out_len == 1 (any other out_len:
@@ -484,7 +518,8 @@ int evogp_hip_get_sr_division(void);
 /* ABI version of this header (9): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
- * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows). */
+ * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step were added to 9 without a
+ * bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
