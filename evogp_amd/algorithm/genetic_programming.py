@@ -4,10 +4,11 @@ kept (``enable_pareto_front``); it is torch-level bookkeeping."""
 from __future__ import annotations
 
 import os
+from typing import Optional
 
 import torch
 
-from ..tree import Forest
+from ..tree import Forest, GenerateDescriptor
 from .crossover import BaseCrossover
 from .mutation import BaseMutation
 from .selection import BaseSelection
@@ -39,7 +40,17 @@ class ParetoFront:
 
 class GeneticProgramming:
     def __init__(self, initial_forest: Forest, crossover: BaseCrossover, mutation: BaseMutation,
-                 selection: BaseSelection, enable_pareto_front: bool = False):
+                 selection: BaseSelection, enable_pareto_front: bool = False,
+                 regenerate_duplicates: Optional[GenerateDescriptor] = None):
+        """``regenerate_duplicates`` (no counterpart in the reference): a descriptor from which ``step`` replaces every tree of the new
+        forest that is a structural duplicate of an earlier row (``Forest.duplicate_classes``) by a fresh random tree -- one round, so
+        a fresh tree may again equal another.  The elites are the first rows and a class keeps its first row, so an elite goes only when
+        an equal elite stands before it.  No host synchronisation."""
+        if regenerate_duplicates is not None:
+            d, f = regenerate_duplicates, initial_forest
+            assert (d.max_tree_len, d.input_len, d.output_len) == (f.max_tree_len, f.input_len, f.output_len), (
+                "regenerate_duplicates must describe trees of the forest's max_tree_len, input_len and output_len")
+        self.regenerate_duplicates = regenerate_duplicates
         self.forest = initial_forest
         self.pop_size = initial_forest.pop_size
         self.crossover = crossover
@@ -51,6 +62,30 @@ class GeneticProgramming:
             self.pareto_front = ParetoFront(f.max_tree_len, f.input_len, f.output_len, f.batch_node_value.device)
 
     def step(self, fitness: torch.Tensor) -> Forest:
+        self._breed(fitness)
+        descriptor = getattr(self, "regenerate_duplicates", None)
+        if descriptor is not None:
+            self._regenerate_duplicates(descriptor)
+        return self.forest
+
+    def _regenerate_duplicates(self, d: GenerateDescriptor) -> None:
+        """rows that are not the first of their class become fresh trees of ``d``: one masked generation launch and three selects"""
+        f = self.forest
+        _, is_first = f.duplicate_classes()
+        dev = is_first.device
+        word = torch.where(is_first, 2**31 - 1, 0).to(torch.int32)   # a tree is generated where (unsigned)word < 1
+        try:   # two 32-bit keys from torch's generator of the device, as Forest.random_generate draws them
+            keys = torch.randint(low=0, high=1000000, size=(2,), dtype=torch.uint32, device=dev)
+        except RuntimeError:  # back ends without a uint32 randint
+            keys = torch.randint(0, 1000000, (2,), device=dev).to(torch.uint32)
+        fresh = torch.ops.evogp_hip.tree_generate_masked(f.pop_size, f.max_tree_len, d.input_len, d.output_len, d.const_samples.shape[0],
+                                                         d.out_prob, d.const_prob, keys, d.depth2leaf_probs, d.roulette_funcs,
+                                                         d.const_samples, 0, word, 1)
+        keep = is_first[:, None]
+        value, ntype, size = (torch.where(keep, old, new) for old, new in zip(f._tensors(), fresh))
+        self.forest = Forest(f.input_len, f.output_len, value, ntype, size, func_mask=Forest.join_masks(f.func_mask, d.func_mask))
+
+    def _breed(self, fitness: torch.Tensor) -> Forest:
         assert self.forest is not None, "forest is not initialized"
         assert fitness.shape == (self.forest.pop_size,), (
             f"fitness shape should be ({self.forest.pop_size}, ), but got {fitness.shape}")

@@ -414,6 +414,44 @@ Tensor lexicase_select(const Tensor &errors, const Tensor &eps, int64_t n_events
     return winners;
 }
 
+// int64[pop]: the bits of the 64-bit structure hash of every tree (evogp_hip_tree_hash)
+Tensor tree_hash(const Tensor &value, const Tensor &type, const Tensor &size) {
+    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
+    const int64_t pop = value.size(0), gp_len = value.size(1);
+    check_sizes(pop, gp_len);
+    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
+    const c10::Device dev = value.device();
+    check_forest(pop, gp_len, value, type, size, dev);
+    c10::DeviceGuard guard(dev);
+    Tensor hash = at::empty({pop}, at::TensorOptions().dtype(at::kLong).device(dev));
+    check_rc(evogp_hip_tree_hash((unsigned)pop, (unsigned)gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
+                                 (unsigned long long *)hash.data_ptr<int64_t>(), current_stream(dev)),
+             "tree_hash");
+    return hash;
+}
+
+// int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
+// workspace comes from torch's caching allocator
+Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
+    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
+    const int64_t pop = value.size(0), gp_len = value.size(1);
+    check_sizes(pop, gp_len);
+    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
+    const c10::Device dev = value.device();
+    check_forest(pop, gp_len, value, type, size, dev);
+    check_tensor(hash, {pop}, "hash", dev, at::kLong);
+    c10::DeviceGuard guard(dev);
+    Tensor class_id = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_tree_classes_workspace_bytes((unsigned)pop, &bytes), "tree_classes");
+    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check_rc(evogp_hip_tree_classes((unsigned)pop, (unsigned)gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
+                                    (const unsigned long long *)hash.data_ptr<int64_t>(), class_id.data_ptr<int>(), ws.data_ptr(),
+                                    current_stream(dev)),
+             "tree_classes");
+    return class_id;
+}
+
 // (front int32, crowding float32, order int32) of a population on (err, cx) (evogp_hip_pareto_rank); the workspace comes from torch's
 // caching allocator
 Tensor3 pareto_rank(const Tensor &err, const Tensor &cx, int64_t cx_bound) {
@@ -905,6 +943,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor normal)");
     m.def("tree_SR_lm_step(int phase, Tensor(a!) value, Tensor node_type, Tensor subtree_size, Tensor(b!) value_cand, Tensor(c!) loss,"
           " Tensor(d!) normal, Tensor loss_cand, Tensor normal_cand, Tensor(e!) damping) -> ()");
+    m.def("tree_hash(Tensor value, Tensor node_type, Tensor subtree_size) -> Tensor");
+    m.def("tree_classes(Tensor value, Tensor node_type, Tensor subtree_size, Tensor hash) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -938,4 +978,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_prune", &tree_prune);
     m.impl("tree_SR_normal_eq", &tree_SR_normal_eq);
     m.impl("tree_SR_lm_step", &tree_SR_lm_step);
+    m.impl("tree_hash", &tree_hash);
+    m.impl("tree_classes", &tree_classes);
 }

@@ -19,12 +19,14 @@ class SymbolicRegression(BaseProblem):
     def __init__(self, datapoints: Optional[Tensor] = None, labels: Optional[Tensor] = None,
                  func: Optional[Callable] = None, num_inputs: Optional[int] = None, num_data: Optional[int] = 100,
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
-                 const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent"):
+                 const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
+                 dedup: bool = False):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
         ``simplify_every`` = k > 0 (single-output problems): every k-th call of ``optimize`` first rewrites the forest with
-        ``Forest.simplify`` (best subtree hoisted, row-constant subtrees folded), so the smaller trees are the ones scored and bred."""
+        ``Forest.simplify`` (best subtree hoisted, row-constant subtrees folded), so the smaller trees are the ones scored and bred.
+        ``dedup``: both run their dataset passes once per distinct tree (``Forest.duplicate_classes``); the results are the same."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -34,6 +36,7 @@ class SymbolicRegression(BaseProblem):
         self.const_opt_method = const_opt_method
         assert simplify_every >= 0, f"simplify_every should be >= 0, but got {simplify_every}"
         self.simplify_every = int(simplify_every)
+        self.dedup = bool(dedup)
         self._optimize_calls = 0
         if datapoints is not None and labels is not None:
             self.datapoints, self.labels = datapoints, labels
@@ -81,13 +84,14 @@ class SymbolicRegression(BaseProblem):
         if self.simplify_every > 0:
             self._optimize_calls += 1
             if self._optimize_calls % self.simplify_every == 0:
-                forest = forest.simplify(self.datapoints, self.labels, use_MSE)[0]
+                forest = forest.simplify(self.datapoints, self.labels, use_MSE, dedup=self.dedup)[0]
         if self.const_opt_steps <= 0:
             return forest
+        more = {"dedup": True} if self.dedup else {}
         if self.const_opt_method == "descent":
-            return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE)[0]
+            return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE, **more)[0]
         return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE,
-                                         method=self.const_opt_method)[0]
+                                         method=self.const_opt_method, **more)[0]
 
     @property
     def problem_dim(self):

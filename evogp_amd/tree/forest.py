@@ -6,7 +6,8 @@
 
 API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
-indexing, concatenation, iteration, pickling), plus ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
+indexing, concatenation, iteration, pickling), plus ``structure_hash`` / ``duplicate_classes`` / ``unique`` (structural duplicates,
+csrc/dedup.hip; ``optimize_constants`` and ``simplify`` take ``dedup=True`` to run their dataset passes once per distinct tree), ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
 descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection) and ``SR_subtree_errors`` / ``simplify``
 (the loss of every subtree, and the rewrite into a smaller tree that is no worse).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
@@ -239,8 +240,42 @@ class Forest:
             const_index = torch.nn.functional.pad(const_index, (0, K - L), value=-1)
         return loss, A, b, const_index
 
+    # ---- structural duplicates ---------------------------------------------------------------
+    def structure_hash(self) -> Tensor:
+        """(pop,) int64: the bits of a 64-bit hash of every tree's live prefix (node values by bit pattern, node types, length;
+        include/evogp_hip.h evogp_hip_tree_hash).  Equal trees have equal hashes; a row whose length is out of range has hash 0."""
+        return torch.ops.evogp_hip.tree_hash(*self._tensors())
+
+    def duplicate_classes(self):
+        """``(class_id, is_first)``: ``class_id`` (pop,) int32 is the smallest index of a tree equal to tree t -- same length and, over
+        the live prefix, the same value bits, type words and subtree sizes (so -0.0 differs from 0.0 and tail words do not count); a
+        row whose length is out of range is a class of its own.  ``is_first`` (pop,) bool marks the representatives
+        (``class_id[t] == t``).  Exact: hashes only choose which rows are compared.  No host synchronisation."""
+        value, ntype, size = self._tensors()
+        class_id = torch.ops.evogp_hip.tree_classes(value, ntype, size, torch.ops.evogp_hip.tree_hash(value, ntype, size))
+        return class_id, class_id == torch.arange(self.pop_size, dtype=torch.int32, device=class_id.device)
+
+    def unique(self):
+        """``(forest, inverse, counts)``, shaped like ``torch.unique``: the representatives of ``duplicate_classes`` in ascending index
+        order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` equal to tree t on its live prefix, and ``counts``
+        (int64) the number of trees per representative.  ONE host synchronisation (the number of representatives sizes the result)."""
+        class_id, is_first = self.duplicate_classes()
+        rank = torch.cumsum(is_first.to(torch.int64), 0) - 1
+        inverse = rank[class_id.to(torch.int64)]
+        reps = torch.nonzero(is_first).squeeze(1)   # (the host sync)
+        return self[reps], inverse, torch.bincount(inverse, minlength=reps.numel())
+
+    def _first_rows_only(self):
+        """``(forest, class_id)``: this forest with every row that is not the first of its class made an EMPTY tree (length 0; the
+        subtree-size tensor is the only one copied), which every tape kernel classifies as malformed and leaves at once"""
+        class_id, is_first = self.duplicate_classes()
+        value, ntype, size = self._tensors()
+        size = size.clone()
+        size[:, 0] = torch.where(is_first, size[:, 0], torch.zeros_like(size[:, 0]))
+        return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), class_id.to(torch.int64)
+
     def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True,
-                           method: str = "descent", damping: float = 1e-3):
+                           method: str = "descent", damping: float = 1e-3, dedup: bool = False):
         """``(forest, loss)``: ``steps`` iterations of a per-tree optimisation of the constants, all on the device with no host
         synchronisation (2 launches per step).  Returns a new Forest (this one is untouched) whose trees differ from these only in
         constant values, and the loss of each returned tree.  No tree's loss rises.
@@ -250,10 +285,24 @@ class Forest:
         Levenberg-Marquardt on the tree's first 8 constants in prefix order (further constants keep their values): the step solves
         ``(A + lambda diag A) delta = -b`` on the normal equations of ``SR_normal_equations`` and is kept only if it lowers the loss;
         lambda starts at ``damping``, falls tenfold after a kept step and rises tenfold after a rejected one.  A model that is linear
-        in its constants is solved in one to three steps."""
+        in its constants is solved in one to three steps.
+
+        ``dedup=True``: the same result, bit for bit, with the dataset passes run once per DISTINCT tree (``duplicate_classes``): the
+        launches see the other rows as empty trees, and every row then takes the tuned constants and the loss of its class's first
+        row.  No host synchronisation is added."""
         assert steps >= 0, f"steps should be >= 0, but got {steps}"
         if method not in ("descent", "lm"):
             raise ValueError(f"method should be 'descent' or 'lm', but got {method!r}")
+        if dedup:
+            firsts, class_id = self._first_rows_only()
+            tuned, loss = firsts.optimize_constants(inputs, labels, steps, step_size, use_MSE, method, damping)
+            # constants live in the prefix, which the rows of a class share; every row keeps its own tail words
+            L = self.max_tree_len
+            live = torch.arange(L, device=class_id.device)[None, :] < self.batch_subtree_size[:, :1]
+            value = torch.where(live, tuned.batch_node_value[class_id], tuned.batch_node_value)
+            forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
+                            func_mask=self.func_mask)
+            return forest, loss[class_id]
         if method == "lm":
             if not use_MSE:
                 raise ValueError("method='lm' minimises the mean squared error: use_MSE must be True")
@@ -311,18 +360,29 @@ class Forest:
         return torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
                                                           use_MSE, *self._tensors(), inputs, labels)
 
-    def simplify(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, hoist: bool = True, fold_constants: bool = True):
+    def simplify(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, hoist: bool = True, fold_constants: bool = True,
+                 dedup: bool = False):
         """``(forest, loss)``: every tree rewritten into a tree that is no larger and, on this dataset, no worse, in two launches with
         no host synchronisation.  ``hoist``: the tree becomes its subtree of least finite error (then least size, then least index),
         so a tree that is NaN as a whole but has a finite subtree is rescued.  ``fold_constants``: every function node whose subtree
         takes one finite float32 value on every row becomes a CONST node of that value (the outermost such node wins); the rewritten
         tree computes bit-identical values on every row of ``inputs``.  Returns a new Forest (this one is untouched) and the loss of
-        each returned tree (``node_err`` at the chosen root).  Simplifying the result again returns it unchanged."""
+        each returned tree (``node_err`` at the chosen root).  Simplifying the result again returns it unchanged.
+
+        ``dedup=True``: the same result, bit for bit, with the pass over the dataset run once per DISTINCT tree
+        (``duplicate_classes``): the other rows enter it as empty trees and take the subtree errors of their class's first row before
+        the rewrite, which runs on every row.  No host synchronisation is added."""
         self._single_output("simplify")
         inputs, labels = self._sr_data(inputs, labels)
         value, ntype, size = self._tensors()
-        node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
-                                                                          self.output_len, use_MSE, value, ntype, size, inputs, labels)
+        if dedup:
+            firsts, class_id = self._first_rows_only()
+            node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
+                                                                              self.output_len, use_MSE, *firsts._tensors(), inputs, labels)
+            node_err, node_const = node_err[class_id], node_const[class_id]
+        else:
+            node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
+                                                                              self.output_len, use_MSE, value, ntype, size, inputs, labels)
         value, ntype, size, _, loss = torch.ops.evogp_hip.tree_prune(self.output_len, bool(hoist), bool(fold_constants), value, ntype, size,
                                                                      node_err, node_const)
         # (a rewritten tree's functions are a subset of the old tree's)

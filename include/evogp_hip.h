@@ -402,6 +402,24 @@ int evogp_hip_pareto_rank(unsigned pop, unsigned cx_bound, const float *err, con
 int evogp_hip_nsga2_select(unsigned pop, const int *order, unsigned pool, unsigned n_tournaments, unsigned t_size, long long seed,
                            long long generation, int *winners, evogp_stream_t stream);
 
+/* Structural duplicates of a forest (no counterpart in the reference).  n = size[t][0]; a row with n < 1 or n > gp_len is OUT OF RANGE: a
+ * class of its own, hash 0.  Two in-range rows are EQUAL when their n are equal and, for every i < n, the fp32 bit pattern of value[i],
+ * the 16 bits of type[i] and size[i] are equal (-0.0 != 0.0, NaNs compare by bits, the OUT flag counts; words at i >= n are never read).
+ *     hash(t) = mix64((sum_{i<n} mix64(w_i ^ ((i + 1) * 0x9E3779B97F4A7C15))) + n),  w_i = (uint64)(uint16)type[i] << 32 | bits(value[i])
+ * mod 2^64, mix64 the splitmix64 finaliser of evogp_hip_random_words.  evogp_hip_tree_hash writes hash_out u64[pop].
+ * evogp_hip_tree_classes writes class_id_out i32[pop]: class_id[t] = the SMALLEST tree index whose row equals row t (so class_id[t] <= t
+ * and class_id[class_id[t]] == class_id[t]).  hash_in u64[pop] only decides which rows are compared -- equality alone decides a class --
+ * and may be any array in which equal rows carry equal words (evogp_hip_tree_hash's, normally): the result does not depend on it.
+ * Rows are compared inside a run of equal hash words, each with the rows before it in ascending tree order: without a collision the
+ * first comparison decides, a run of r distinct colliding rows costs O(r^2) comparisons.  Deterministic, no atomics, nothing
+ * synchronises with the host.  workspace: evogp_hip_tree_classes_workspace_bytes(pop) bytes of device memory owned by the caller (no
+ * zeroing needed), about 32 pop bytes plus the radix sort's scratch; the engine allocates nothing. */
+int evogp_hip_tree_hash(unsigned pop, unsigned gp_len, const float *value, const int16_t *type, const int16_t *size,
+                        unsigned long long *hash_out, evogp_stream_t stream);
+int evogp_hip_tree_classes_workspace_bytes(unsigned pop, unsigned long long *bytes);
+int evogp_hip_tree_classes(unsigned pop, unsigned gp_len, const float *value, const int16_t *type, const int16_t *size,
+                           const unsigned long long *hash_in, int *class_id_out, void *workspace, evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -518,8 +536,9 @@ int evogp_hip_get_sr_division(void);
 /* ABI version of this header (9): bumped when a signature changes or an entry point is added (5: the debug hooks moved to evogp_hip_debug.h;
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
- * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step were added to 9 without a
- * bump: purely additive, no existing signature or behaviour changed). */
+ * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
+ * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes were added to 9 without a bump: purely additive, no existing
+ * signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
