@@ -173,3 +173,72 @@ def test_gpu_cases_keep_half_of_their_trees_on_the_reference_alone(oracle):
         value, type_, size, X, y = lm_cases.make_case(funcs, gp_len, D, pop)
         stable = lm_cases.comparable(oracle, value, type_, size, X, y)[3]
         assert stable.mean() >= 0.5, (funcs, gp_len, D, pop, int(stable.sum()))
+
+
+# ---- the edge cells of the adjoint table, as the normal equations state them ---------------------------------------------------------
+D9 = float(np.float32(1e-9))
+NAN, INF = np.nan, np.inf
+# (prefix nodes of f over CONST operands, loss, J per constant): one row, label 0, so A_ij = J_i J_j and b_i = J_i pred
+EDGE_TREES = [
+    ([(R.F_LOOSE_DIV, B, 3), (3.0, C, 1), (5e-10, C, 1)], (3 / D9) ** 2, [1 / D9, 0.0]),       # |b| <= delta: d = delta, db = 0
+    ([(R.F_LOOSE_DIV, B, 3), (3.0, C, 1), (-0.0, C, 1)], (3 / D9) ** 2, [-1 / D9, 0.0]),       # the sign of the zero
+    ([(R.F_LOOSE_DIV, B, 3), (3.0, C, 1), (D9, C, 1)], (3 / D9) ** 2, [1 / D9, 0.0]),          # <=, not <
+    ([(R.F_DIV, B, 3), (1.0, C, 1), (0.0, C, 1)], NAN, [INF, NAN]),
+    ([(R.F_MAX, B, 3), (1.0, C, 1), (1.0, C, 1)], 1.0, [1.0, 0.0]),                            # ties go to a
+    ([(R.F_MIN, B, 3), (0.0, C, 1), (-0.0, C, 1)], 0.0, [1.0, 0.0]),
+    ([(R.F_IF, T, 4), (0.0, C, 1), (2.0, C, 1), (3.0, C, 1)], 9.0, [0.0, 0.0, 1.0]),           # the condition gets nothing
+    ([(R.F_IF, T, 4), (1e-45, C, 1), (2.0, C, 1), (3.0, C, 1)], 4.0, [0.0, 1.0, 0.0]),
+    ([(R.F_LT, B, 3), (1.0, C, 1), (2.0, C, 1)], 1.0, [0.0, 0.0]),
+    ([(40.0, B, 3), (1.0, C, 1), (2.0, C, 1)], 0.0, [0.0, 0.0]),                               # an unknown binary id
+    ([(99.0, U, 2), (1.0, C, 1)], 0.0, [0.0]),                                                 # an unknown unary id
+    ([(R.F_INV, U, 2), (0.0, C, 1)], NAN, [NAN]),
+    ([(R.F_LOOSE_INV, U, 2), (1e-10, C, 1)], (1 / D9) ** 2, [0.0]),
+    ([(R.F_LOG, U, 2), (-2.0, C, 1)], NAN, [-0.5]),
+    ([(R.F_LOOSE_LOG, U, 2), (0.0, C, 1)], 1e18, [0.0]),
+    ([(R.F_LOOSE_LOG, U, 2), (-2.0, C, 1)], np.log(2.0) ** 2, [-0.5]),
+    ([(R.F_POW, B, 3), (-2.0, C, 1), (3.0, C, 1)], 64.0, [12.0, 0.0]),                         # a < 0: nothing to the exponent
+    ([(R.F_POW, B, 3), (0.0, C, 1), (0.0, C, 1)], 1.0, [NAN, 0.0]),                            # 0 * pow(0, -1): the formula as written
+    ([(R.F_LOOSE_POW, B, 3), (0.0, C, 1), (0.0, C, 1)], 0.0, [0.0, 0.0]),
+    ([(R.F_LOOSE_POW, B, 3), (-2.0, C, 1), (3.0, C, 1)], 64.0, [-12.0, 8 * np.log(2.0)]),      # sign a; db is 0 only at |a| = 0
+    ([(R.F_ABS, U, 2), (0.0, C, 1)], 0.0, [0.0]),
+    ([(R.F_ABS, U, 2), (-3.0, C, 1)], 9.0, [-1.0]),
+    ([(R.F_SQRT, U, 2), (0.0, C, 1)], 0.0, [INF]),
+    ([(R.F_SQRT, U, 2), (-4.0, C, 1)], NAN, [NAN]),
+    ([(R.F_LOOSE_SQRT, U, 2), (0.0, C, 1)], 0.0, [0.0]),
+    ([(R.F_LOOSE_SQRT, U, 2), (-4.0, C, 1)], 4.0, [-0.25]),
+]
+
+
+@pytest.mark.parametrize("case", range(len(EDGE_TREES)))
+def test_normal_equations_at_the_edge_cells_of_the_adjoint_table(case):
+    nodes, want_loss, J = EDGE_TREES[case]
+    value, type_, size = _row(nodes)
+    with np.errstate(all="ignore"):
+        loss, normal, _ = LM.tree_normal_eq(value, type_, size, np.zeros((1, 1), np.float32), np.zeros((1, 1), np.float32))
+        pred, Jg, cidx = LM.tree_jacobian(value, type_, size, np.zeros((1, 1), np.float32))
+        A, b = LM.unpack(normal)
+        nc = len(J)
+        J = np.array(J)
+        np.testing.assert_allclose(loss, want_loss, rtol=1e-12)
+        np.testing.assert_allclose(Jg[0, :nc], J, rtol=1e-12)
+        np.testing.assert_allclose(A[:nc, :nc], np.outer(J, J), rtol=1e-12)   # a 0 of the table is a zero row and column, a NaN a NaN one
+        np.testing.assert_allclose(b[:nc], J * pred[0], rtol=1e-12)
+    assert np.all(A[nc:] == 0) and np.all(A[:, nc:] == 0) and np.all(b[nc:] == 0) and np.all(Jg[0, nc:] == 0)   # absent constants
+    for j in range(nc):
+        if J[j] == 0 and np.isfinite(J).all() and np.isfinite(pred[0]):
+            assert np.all(A[j] == 0) and np.all(A[:, j] == 0) and b[j] == 0
+
+
+def test_step_at_the_edge_cells():
+    """a constant the table gives 0 is dropped and keeps its value while the other moves; a NaN cell stops the tree"""
+    z = np.zeros((1, 1), np.float32)
+    value, type_, size = _row([(R.F_LOOSE_DIV, B, 3), (3.0, C, 1), (5e-10, C, 1)])
+    _, normal, _ = LM.tree_normal_eq(value, type_, size, z, z)
+    new = LM.solve_step(normal, 1e-3, 1.0, [3.0, 5e-10])
+    assert new is not None and new[1] == np.float32(5e-10) and new[0] != np.float32(3.0)
+    for nodes, consts in (([(R.F_DIV, B, 3), (1.0, C, 1), (0.0, C, 1)], [1.0, 0.0]), ([(R.F_INV, U, 2), (0.0, C, 1)], [0.0]),
+                          ([(R.F_POW, B, 3), (0.0, C, 1), (0.0, C, 1)], [0.0, 0.0])):
+        value, type_, size = _row(nodes)
+        with np.errstate(all="ignore"):
+            _, normal, _ = LM.tree_normal_eq(value, type_, size, z, z)
+        assert LM.solve_step(normal, 1e-3, 1.0, consts) is None
