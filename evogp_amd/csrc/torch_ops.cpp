@@ -278,6 +278,50 @@ std::tuple<Tensor, Tensor> tree_SR_subtree_errors(int64_t pop_size, int64_t data
     return {node_err, node_const};
 }
 
+// the loss and the coefficients of every tree under linear scaling (evogp_hip_sr_linear_scaling): loss (pop,), coef (pop, 2) = intercept, slope
+std::tuple<Tensor, Tensor> tree_SR_linear_scaling(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                  const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                  const Tensor &labels) {
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    TORCH_CHECK(out_len == 1, "tree_SR_linear_scaling: single-output trees only (out_len must be 1), but got ", out_len);
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor loss = at::empty({pop_size}, value.options());
+    Tensor coef = at::empty({pop_size, 2}, value.options());
+    check_rc(evogp_hip_sr_linear_scaling((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                         value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
+                                         variables.data_ptr<float>(), labels.data_ptr<float>(), loss.data_ptr<float>(), coef.data_ptr<float>(),
+                                         current_stream(dev)),
+             "tree_SR_linear_scaling");
+    return {loss, coef};
+}
+
+// every row T as ADD(MUL(T, slope), intercept) in rows of out_gp_len words (evogp_hip_wrap_linear); applied (pop,) uint8
+std::tuple<Tensor, Tensor, Tensor, Tensor> tree_wrap_linear(int64_t out_gp_len, const Tensor &value, const Tensor &type, const Tensor &size,
+                                                            const Tensor &coef) {
+    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
+    const int64_t pop_size = value.size(0), gp_len = value.size(1);
+    check_sizes(pop_size, gp_len);
+    TORCH_CHECK(out_gp_len >= gp_len && out_gp_len <= kMaxStack, "out_gp_len must be in range [", gp_len, ", ", kMaxStack, "], but got ", out_gp_len);
+    const c10::Device dev = value.device();
+    check_forest(pop_size, gp_len, value, type, size, dev);
+    check_tensor(coef, {pop_size, 2}, "coef", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor3 out = empty_forest(pop_size, out_gp_len, dev);
+    Tensor applied = at::empty({pop_size}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check_rc(evogp_hip_wrap_linear((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(),
+                                   size.data_ptr<int16_t>(), coef.data_ptr<float>(), std::get<0>(out).data_ptr<float>(),
+                                   std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(), applied.data_ptr<uint8_t>(),
+                                   current_stream(dev)),
+             "tree_wrap_linear");
+    return {std::get<0>(out), std::get<1>(out), std::get<2>(out), applied};
+}
+
 // hoist the best subtree, fold the row-constant ones (evogp_hip_prune_rows): a new forest, the chosen roots and their losses
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tree_prune(int64_t out_len, bool hoist, bool fold, const Tensor &value, const Tensor &type,
                                                               const Tensor &size, const Tensor &node_err, const Tensor &node_const) {
@@ -945,6 +989,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor(d!) normal, Tensor loss_cand, Tensor normal_cand, Tensor(e!) damping) -> ()");
     m.def("tree_hash(Tensor value, Tensor node_type, Tensor subtree_size) -> Tensor");
     m.def("tree_classes(Tensor value, Tensor node_type, Tensor subtree_size, Tensor hash) -> Tensor");
+    m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
+    m.def("tree_wrap_linear(int out_gp_len, Tensor value, Tensor node_type, Tensor subtree_size, Tensor coef)"
+          " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -980,4 +1028,6 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_lm_step", &tree_SR_lm_step);
     m.impl("tree_hash", &tree_hash);
     m.impl("tree_classes", &tree_classes);
+    m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
+    m.impl("tree_wrap_linear", &tree_wrap_linear);
 }

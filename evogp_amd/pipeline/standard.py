@@ -53,7 +53,11 @@ class StandardPipeline(BasePipeline):
         best = int(torch.argmax(host))
         if host[best] > self.best_fitness:
             self.best_fitness = host[best]
-            self.best_tree = forest[best]
+            if getattr(self.problem, "linear_scaling", False):
+                # the reported tree is the model whose error the fitness states: the tree with its slope and intercept written in
+                self.best_tree = self.problem.scaled(forest[best:best + 1], dedup=False)[0]   # (one tree: nothing to deduplicate)
+            else:
+                self.best_tree = forest[best]
         return host
 
     def run(self):

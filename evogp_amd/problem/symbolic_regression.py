@@ -20,13 +20,17 @@ class SymbolicRegression(BaseProblem):
                  func: Optional[Callable] = None, num_inputs: Optional[int] = None, num_data: Optional[int] = 100,
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
-                 dedup: bool = False):
+                 dedup: bool = False, linear_scaling: bool = False):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
         ``simplify_every`` = k > 0 (single-output problems): every k-th call of ``optimize`` first rewrites the forest with
         ``Forest.simplify`` (best subtree hoisted, row-constant subtrees folded), so the smaller trees are the ones scored and bred.
-        ``dedup``: both run their dataset passes once per distinct tree (``Forest.duplicate_classes``); the results are the same."""
+        ``dedup``: both run their dataset passes once per distinct tree (``Forest.duplicate_classes``); the results are the same.
+        ``linear_scaling`` (Keijzer 2003; MSE, single-output problems): a tree T is scored by the error of ``a + b * T(x)`` with the
+        least-squares ``a, b`` (``Forest.SR_scaled_fitness``, which honours ``dedup``), so evolution searches for the shape and the
+        closed form supplies scale and offset; ``scaled(forest)`` returns the trees with their coefficients written in, and
+        StandardPipeline reports its best tree that way.  ``optimize`` is untouched: simplification and constant tuning run first."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -38,12 +42,15 @@ class SymbolicRegression(BaseProblem):
         self.simplify_every = int(simplify_every)
         self.dedup = bool(dedup)
         self._optimize_calls = 0
+        self.linear_scaling = bool(linear_scaling)
         if datapoints is not None and labels is not None:
             self.datapoints, self.labels = datapoints, labels
-            return
-        assert func is not None and num_inputs is not None, (
-            "func and num_inputs, must be provided when datapoints and labels are not provided")
-        self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
+        else:
+            assert func is not None and num_inputs is not None, (
+                "func and num_inputs, must be provided when datapoints and labels are not provided")
+            self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
+        if self.linear_scaling and (self.labels.dim() != 2 or self.labels.shape[1] != 1):
+            raise ValueError(f"linear_scaling works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
 
     @staticmethod
     def generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds):
@@ -61,7 +68,45 @@ class SymbolicRegression(BaseProblem):
             outputs = outputs[:, None]
         return inputs, outputs
 
+    def scaled_fitness(self, forest: Forest, dedup: Optional[bool] = None):
+        """``(loss, slope, intercept)`` of every tree under linear scaling on this problem's data: ``Forest.SR_scaled_fitness``, or
+        under ``execute_mode="torch"`` the same definition from ``batch_forward``'s predictions in float64 torch.  ``dedup``: None takes
+        the problem's setting"""
+        if self.execute_mode != "torch":
+            return forest.SR_scaled_fitness(self.datapoints, self.labels, dedup=self.dedup if dedup is None else bool(dedup))
+        p = forest.batch_forward(self.datapoints)[:, :, 0]   # (pop, D) float32
+        D = p.shape[1]
+        y = self.labels.to(p.device)[:, 0].to(torch.float64)
+        ybar = y.mean()
+        v = y - ybar
+        syy = (v * v).sum()
+        pd = p.to(torch.float64)
+        mean = pd.sum(1) / D
+        var = (pd * pd).sum(1) / D - mean * mean
+        cov = (pd * v[None, :]).sum(1) / D
+        flat = (p.min(1).values == p.max(1).values) | (var <= 0) | (D == 1)
+        b = torch.where(flat, torch.zeros_like(var), cov / var)
+        a = torch.where(flat, ybar.expand_as(var), ybar - b * mean)
+        loss = torch.where(flat, (syy / D).expand_as(var), torch.clamp(syy / D - b * cov, min=0.0))
+        loss, a, b = loss.to(torch.float32), a.to(torch.float32), b.to(torch.float32)
+        bad = ~torch.isfinite(p).all(1) | ~torch.isfinite(a) | ~torch.isfinite(b)
+        nan = torch.full_like(loss, float("nan"))
+        return torch.where(bad, nan, loss), torch.where(bad, nan, b), torch.where(bad, nan, a)
+
+    def scaled(self, forest: Forest, dedup: Optional[bool] = None) -> Forest:
+        """``forest`` with every tree T rewritten as ``intercept + slope * T`` for its own least-squares coefficients on this problem's
+        data (``Forest.apply_scaling`` with ``grow=True``: rows four words longer, at most 1024)"""
+        _, slope, intercept = self.scaled_fitness(forest, dedup)
+        return forest.apply_scaling(slope, intercept, grow=True)[0]
+
+    def _check_scaling(self, use_MSE: bool):
+        if not use_MSE:
+            raise ValueError("linear_scaling minimises the mean squared error: use_MSE must be True")
+
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
+        if self.linear_scaling:
+            self._check_scaling(use_MSE)
+            return -self.scaled_fitness(forest)[0]
         if self.execute_mode == "torch":
             pred = forest.batch_forward(self.datapoints)  # (pop, D, out)
             err = pred - self.labels[None, :, :]
@@ -72,7 +117,11 @@ class SymbolicRegression(BaseProblem):
     def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
         on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
-        if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
+        if self.linear_scaling:
+            self._check_scaling(use_MSE)
+            if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
+                return torch.ops.evogp_hip.fitness_scores(self.scaled_fitness(forest)[0], True)
+        elif self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
             err = forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
             return torch.ops.evogp_hip.fitness_scores(err, True)
         f = self.evaluate(forest, use_MSE)

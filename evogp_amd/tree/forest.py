@@ -8,8 +8,9 @@ API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_gener
 ``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
 indexing, concatenation, iteration, pickling), plus ``structure_hash`` / ``duplicate_classes`` / ``unique`` (structural duplicates,
 csrc/dedup.hip; ``optimize_constants`` and ``simplify`` take ``dedup=True`` to run their dataset passes once per distinct tree), ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
-descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection) and ``SR_subtree_errors`` / ``simplify``
-(the loss of every subtree, and the rewrite into a smaller tree that is no worse).  Every heavy method is one call into
+descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection), ``SR_subtree_errors`` / ``simplify``
+(the loss of every subtree, and the rewrite into a smaller tree that is no worse) and ``SR_scaled_fitness`` / ``apply_scaling`` (linear
+scaling: the loss under the least-squares slope and intercept, and the tree that carries them).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -34,6 +35,7 @@ from .utils import NType, check_tensor
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
+_WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
 
 
@@ -387,6 +389,44 @@ class Forest:
                                                                      node_err, node_const)
         # (a rewritten tree's functions are a subset of the old tree's)
         return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), loss
+
+    # ---- linear scaling ------------------------------------------------------------------------
+    def SR_scaled_fitness(self, inputs: Tensor, labels: Tensor, dedup: bool = False):
+        """``(loss, slope, intercept)``, each (pop,) float32: the mean squared error of ``intercept + slope * tree(x)`` with the
+        least-squares coefficients of every tree (linear scaling, Keijzer 2003), from three float64 sums per tree taken inside the
+        evaluation kernel (csrc/sr_scale.hip): the ``(pop, D)`` predictions are never stored.  A tree that is constant over the rows
+        (decided exactly, on the minimum and maximum prediction) gets slope 0, intercept mean(y) and the variance of the labels; a
+        malformed tree or one with a non-finite prediction gets NaN in all three.  Deterministic from run to run, no host
+        synchronisation; single-output forests, MSE only.
+
+        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``), the other rows entering it
+        as empty trees and taking the result of their class's first row."""
+        self._single_output("SR_scaled_fitness")
+        inputs, labels = self._sr_data(inputs, labels)
+        source, class_id = self._first_rows_only() if dedup else (self, None)
+        loss, coef = torch.ops.evogp_hip.tree_SR_linear_scaling(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
+                                                                self.output_len, *source._tensors(), inputs, labels)
+        if dedup:
+            loss, coef = loss[class_id], coef[class_id]
+        return loss, coef[:, 1], coef[:, 0]
+
+    def apply_scaling(self, slope: Tensor, intercept: Tensor, grow: bool = False):
+        """``(forest, applied)``: every tree T rewritten as ``ADD(MUL(T, slope), intercept)`` -- four more nodes -- so that the tree
+        itself computes the scaled model (``fl(fl(T * slope) + intercept)`` in float32).  ``applied`` (pop,) bool is False for the rows
+        left as they were: the wrapped tree does not fit the row, a coefficient is not finite, or the tree is malformed.
+        ``grow=True``: the result has ``max_tree_len = min(L + 4, 1024)``, so every finite tree of a forest with ``L <= 1020`` fits.
+        One launch, no host synchronisation; single-output forests only."""
+        self._single_output("apply_scaling")
+        dev = self.batch_node_value.device
+        slope, intercept = check_tensor(slope, dev), check_tensor(intercept, dev)
+        assert slope.shape == (self.pop_size,) and intercept.shape == (self.pop_size,), (
+            f"slope and intercept shapes should be ({self.pop_size}, ), but got {tuple(slope.shape)} and {tuple(intercept.shape)}")
+        coef = torch.stack([intercept.to(torch.float32), slope.to(torch.float32)], dim=1).contiguous()
+        out_len = min(self.max_tree_len + 4, _utils.MAX_STACK) if grow else self.max_tree_len
+        value, ntype, size, applied = torch.ops.evogp_hip.tree_wrap_linear(out_len, *self._tensors(), coef)
+        mask = self.func_mask
+        return (Forest(self.input_len, self.output_len, value, ntype, size, func_mask=(mask | _WRAP_FUNCS) if mask else 0),
+                applied.to(torch.bool))
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

@@ -457,6 +457,32 @@ int evogp_hip_evaluate_prepared(unsigned pop_size, unsigned gp_len, unsigned var
                                 const void *workspace, int with_fallback,
                                 const float *variables, float *results, evogp_stream_t stream);
 
+/* Linear scaling (Keijzer 2003; no counterpart in the reference): the mean squared error of  a + b * T(x)  with the least-squares
+ * a, b of every single-output tree T, from three float64 sums per tree taken in the evaluation kernel's epilogue (csrc/sr_scale.hip):
+ * no (pop, D) prediction matrix exists.  With p_d the float32 prediction on row d (the bits evogp_hip_batch_evaluate stores),
+ * ybar the float64 mean of the labels, v_d = (double)y_d - ybar, Syy = sum v_d^2, and per tree Sp = sum p_d, Spp = sum p_d^2,
+ * Spv = sum p_d v_d (float64), var = Spp/D - (Sp/D)^2, cov = Spv/D:
+ *   malformed tree, or a p_d that is not finite      loss = intercept = slope = NaN
+ *   min_d p_d == max_d p_d, or var <= 0, or D == 1   slope = 0, intercept = ybar, loss = Syy/D
+ *   otherwise                                        slope = cov/var, intercept = ybar - slope*Sp/D, loss = max(0, Syy/D - slope*cov),
+ *                                                    in float64, rounded once to float32; all three NaN if a rounded coefficient is not finite
+ * coef is (pop, 2): intercept, slope.  Sums have a fixed order (lane partials over the wave's row tiles in ascending order, the 64
+ * lanes by a fixed butterfly, the waves in ascending order): the output is bit-identical from run to run and does not depend on the
+ * other rows of the forest.  ybar and Syy come from a one-workgroup kernel in front and stay on the device: nothing synchronises with
+ * the host, and the call can be captured into a HIP graph once one eager call on the stream has been made.
+ * Any gp_len <= 1024, var_len and data_points; out_len != 1 returns EVOGP_E_UNSUPPORTED. */
+int evogp_hip_sr_linear_scaling(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                const float *labels, float *loss, float *coef, evogp_stream_t stream);
+
+/* Row t (length len) becomes the prefix tree ADD(MUL(T, slope), intercept): word 0 = ADD (size len + 4), word 1 = MUL (size len + 2: the tree and the slope),
+ * words 2 .. len + 1 the old tree, then CONST slope and CONST intercept, zero tail words, applied[t] = 1.  The output rows have
+ * out_gp_len >= gp_len words.  A row whose len + 4 exceeds out_gp_len, whose coefficients are not both finite or which is malformed
+ * is copied unchanged (tail words beyond gp_len zero) with applied[t] = 0.  coef is (pop, 2): intercept, slope.  Not in place. */
+int evogp_hip_wrap_linear(unsigned pop_size, unsigned gp_len, unsigned out_gp_len, const float *value, const int16_t *type,
+                          const int16_t *size, const float *coef, float *out_value, int16_t *out_type, int16_t *out_size,
+                          unsigned char *applied, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -537,8 +563,8 @@ int evogp_hip_get_sr_division(void);
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
- * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes were added to 9 without a bump: purely additive, no existing
- * signature or behaviour changed). */
+ * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear
+ * were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
