@@ -474,6 +474,30 @@ Tensor tree_hash(const Tensor &value, const Tensor &type, const Tensor &size) {
     return hash;
 }
 
+// (lo float32, hi float32, flags uint8), each (pop, gp_len): the interval of every subtree over the box [lower, upper] (evogp_hip_tree_intervals)
+std::tuple<Tensor, Tensor, Tensor> tree_intervals(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &lower,
+                                                  const Tensor &upper) {
+    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
+    const int64_t pop = value.size(0), gp_len = value.size(1);
+    check_sizes(pop, gp_len);
+    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
+    const c10::Device dev = value.device();
+    check_forest(pop, gp_len, value, type, size, dev);
+    TORCH_CHECK(lower.dim() == 1 && lower.size(0) > 0, "lower must be a (var_len,) tensor with var_len > 0");
+    const int64_t var_len = lower.size(0);
+    check_tensor(lower, {var_len}, "lower", dev, at::kFloat);
+    check_tensor(upper, {var_len}, "upper", dev, at::kFloat);
+    c10::DeviceGuard guard(dev);
+    Tensor lo = at::empty({pop, gp_len}, value.options());
+    Tensor hi = at::empty({pop, gp_len}, value.options());
+    Tensor flags = at::empty({pop, gp_len}, at::TensorOptions().dtype(at::kByte).device(dev));
+    check_rc(evogp_hip_tree_intervals((unsigned)pop, (unsigned)gp_len, (unsigned)var_len, value.data_ptr<float>(), type.data_ptr<int16_t>(),
+                                      size.data_ptr<int16_t>(), lower.data_ptr<float>(), upper.data_ptr<float>(), lo.data_ptr<float>(),
+                                      hi.data_ptr<float>(), flags.data_ptr<uint8_t>(), current_stream(dev)),
+             "tree_intervals");
+    return {lo, hi, flags};
+}
+
 // int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
 // workspace comes from torch's caching allocator
 Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
@@ -993,6 +1017,7 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_wrap_linear(int out_gp_len, Tensor value, Tensor node_type, Tensor subtree_size, Tensor coef)"
           " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
+    m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -1030,4 +1055,5 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_classes", &tree_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_wrap_linear", &tree_wrap_linear);
+    m.impl("tree_intervals", &tree_intervals);
 }

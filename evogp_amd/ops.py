@@ -34,3 +34,10 @@ if not os.path.exists(TORCH_LIB_PATH):
         f"{TORCH_LIB_PATH} is missing: build the engine first (python -c 'import __graft_entry__ as g; g.build()'  or  "
         "make -C evogp_amd/csrc).  evogp_amd has no Python or CPU fallback for its operators.")
 torch.ops.load_library(TORCH_LIB_PATH)
+
+
+def tree_intervals(value, node_type, subtree_size, lower, upper):
+    """``(lo, hi, flags)``, each (pop, gp_len): ``torch.ops.evogp_hip.tree_intervals`` (csrc/sr_interval.hip), the interval of every
+    subtree of every single-output tree over the box ``lower[v] <= x[v] <= upper[v]`` (float32 ``(var_len,)`` tensors on the forest's
+    device); flags bit 0 = the subtree may be a NaN, bit 1 = the row is malformed"""
+    return torch.ops.evogp_hip.tree_intervals(value, node_type, subtree_size, lower, upper)

@@ -20,7 +20,8 @@ class SymbolicRegression(BaseProblem):
                  func: Optional[Callable] = None, num_inputs: Optional[int] = None, num_data: Optional[int] = 100,
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
-                 dedup: bool = False, linear_scaling: bool = False):
+                 dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
+                 input_margin: float = 0.0):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -30,7 +31,12 @@ class SymbolicRegression(BaseProblem):
         ``linear_scaling`` (Keijzer 2003; MSE, single-output problems): a tree T is scored by the error of ``a + b * T(x)`` with the
         least-squares ``a, b`` (``Forest.SR_scaled_fitness``, which honours ``dedup``), so evolution searches for the shape and the
         closed form supplies scale and offset; ``scaled(forest)`` returns the trees with their coefficients written in, and
-        StandardPipeline reports its best tree that way.  ``optimize`` is untouched: simplification and constant tuning run first."""
+        StandardPipeline reports its best tree that way.  ``optimize`` is untouched: simplification and constant tuning run first.
+        ``interval_check`` (Keijzer 2003; single-output problems): a tree that interval arithmetic cannot show to be defined and finite
+        on the whole box of admissible inputs (``Forest.safe_mask``) gets NaN from ``evaluate`` and -inf from ``scores``, whatever
+        loss it has on the rows; the others keep their values bit for bit.  The box is fixed at construction: ``input_bounds="data"``
+        takes the per-column minimum and maximum of ``datapoints``, each side moved outward by ``input_margin`` times the column's
+        range; or pass a ``(lower, upper)`` pair of floats or ``(num_inputs,)`` tensors."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -51,6 +57,35 @@ class SymbolicRegression(BaseProblem):
             self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
         if self.linear_scaling and (self.labels.dim() != 2 or self.labels.shape[1] != 1):
             raise ValueError(f"linear_scaling works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+        self.interval_check = bool(interval_check)
+        if self.interval_check:
+            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+                raise ValueError(f"interval_check works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+            self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
+
+    def _input_box(self, input_bounds, margin: float):
+        """the box of admissible inputs as two float32 ``(num_inputs,)`` tensors"""
+        if isinstance(input_bounds, str):
+            if input_bounds != "data":
+                raise ValueError(f"input_bounds should be 'data' or a (lower, upper) pair, but got {input_bounds!r}")
+            x = self.datapoints.detach().to(torch.float32)
+            lower, upper = x.min(dim=0).values, x.max(dim=0).values
+        else:
+            lower, upper = input_bounds
+            n = self.datapoints.shape[1]
+            lower, upper = (torch.full((n,), float(b)) if isinstance(b, (int, float)) else torch.as_tensor(b, dtype=torch.float32).reshape(-1)
+                            for b in (lower, upper))
+        if margin != 0.0:
+            pad = margin * (upper - lower)
+            lower, upper = lower - pad, upper + pad
+        return lower.cpu(), upper.cpu()   # (Forest.SR_intervals checks the bounds on the host)
+
+    def safe_mask(self, forest: Forest) -> Tensor:
+        """(pop,) bool: ``Forest.safe_mask`` on this problem's box"""
+        return forest.safe_mask(self.input_lower, self.input_upper)
+
+    def _masked(self, forest: Forest, fitness: Tensor, fill: float) -> Tensor:
+        return torch.where(self.safe_mask(forest).to(fitness.device), fitness, torch.full_like(fitness, fill))
 
     @staticmethod
     def generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds):
@@ -104,6 +139,16 @@ class SymbolicRegression(BaseProblem):
             raise ValueError("linear_scaling minimises the mean squared error: use_MSE must be True")
 
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
+        fitness = self._evaluate(forest, use_MSE)
+        return self._masked(forest, fitness, float("nan")) if self.interval_check else fitness
+
+    def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
+        """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
+        on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
+        fitness = self._scores(forest, use_MSE)
+        return self._masked(forest, fitness, float("-inf")) if self.interval_check else fitness
+
+    def _evaluate(self, forest: Forest, use_MSE: bool) -> Tensor:
         if self.linear_scaling:
             self._check_scaling(use_MSE)
             return -self.scaled_fitness(forest)[0]
@@ -114,9 +159,7 @@ class SymbolicRegression(BaseProblem):
             return -torch.mean(err**2 if use_MSE else err.abs(), dim=(1, 2))
         return -forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
 
-    def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
-        """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
-        on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
+    def _scores(self, forest: Forest, use_MSE: bool) -> Tensor:
         if self.linear_scaling:
             self._check_scaling(use_MSE)
             if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
@@ -124,7 +167,7 @@ class SymbolicRegression(BaseProblem):
         elif self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
             err = forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
             return torch.ops.evogp_hip.fitness_scores(err, True)
-        f = self.evaluate(forest, use_MSE)
+        f = self._evaluate(forest, use_MSE)
         return torch.where(torch.isnan(f), torch.full_like(f, float("-inf")), f)
 
     def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:

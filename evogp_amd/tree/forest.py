@@ -10,7 +10,8 @@ indexing, concatenation, iteration, pickling), plus ``structure_hash`` / ``dupli
 csrc/dedup.hip; ``optimize_constants`` and ``simplify`` take ``dedup=True`` to run their dataset passes once per distinct tree), ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
 descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection), ``SR_subtree_errors`` / ``simplify``
 (the loss of every subtree, and the rewrite into a smaller tree that is no worse) and ``SR_scaled_fitness`` / ``apply_scaling`` (linear
-scaling: the loss under the least-squares slope and intercept, and the tree that carries them).  Every heavy method is one call into
+scaling: the loss under the least-squares slope and intercept, and the tree that carries them) and ``SR_intervals`` / ``safe_mask`` (interval
+arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -427,6 +428,45 @@ class Forest:
         mask = self.func_mask
         return (Forest(self.input_len, self.output_len, value, ntype, size, func_mask=(mask | _WRAP_FUNCS) if mask else 0),
                 applied.to(torch.bool))
+
+    # ---- interval arithmetic --------------------------------------------------------------------
+    def _box(self, lower, upper):
+        """the box as two float32 ``(input_len,)`` tensors on the forest's device, checked on the host"""
+        dev = self.batch_node_value.device
+
+        def side(b, name):
+            if isinstance(b, (int, float)):
+                return torch.full((self.input_len,), float(b), dtype=torch.float32)
+            b = torch.as_tensor(b).detach().to("cpu", torch.float32).reshape(-1)
+            if b.shape[0] != self.input_len:
+                raise ValueError(f"{name} should hold {self.input_len} bounds, but got {b.shape[0]}")
+            return b
+
+        lower, upper = side(lower, "lower"), side(upper, "upper")
+        if not bool(torch.isfinite(lower).all() and torch.isfinite(upper).all()):
+            raise ValueError("the bounds of the box must be finite")
+        if bool((lower > upper).any()):
+            raise ValueError("lower must not exceed upper")
+        return lower.contiguous().to(dev), upper.contiguous().to(dev)
+
+    def SR_intervals(self, lower, upper):
+        """``(lo, hi, flags)``, each (pop, max_tree_len): for every node of every tree a float32 interval and a flag byte that bound
+        the float32 value its subtree takes on ANY input of the box ``lower[v] <= x[v] <= upper[v]`` -- not only on the rows of a
+        dataset (interval arithmetic, Keijzer 2003; csrc/sr_interval.hip, one lane per tree, no dataset, no host synchronisation
+        beyond the check of the bounds).  ``flags`` bit 0 (1): the value may be a NaN; bit 1 (2): the row is malformed (all its live
+        nodes then hold NaN bounds).  Words past a tree's length are 0.  ``lower`` / ``upper``: floats or ``(input_len,)`` tensors,
+        finite, ``lower <= upper`` (``ValueError`` otherwise); single-output forests only."""
+        if self.output_len != 1:
+            raise ValueError(f"SR_intervals works on single-output trees only, but output_len is {self.output_len}")
+        lower, upper = self._box(lower, upper)
+        return torch.ops.evogp_hip.tree_intervals(*self._tensors(), lower, upper)
+
+    def safe_mask(self, lower, upper, max_abs: float = float("inf")) -> Tensor:
+        """(pop,) bool: the tree is defined and bounded on the whole box -- its root can not be a NaN, both root bounds are finite and
+        neither exceeds ``max_abs`` in magnitude (``SR_intervals``)"""
+        lo, hi, flags = self.SR_intervals(lower, upper)
+        lo, hi = lo[:, 0], hi[:, 0]
+        return (flags[:, 0] == 0) & torch.isfinite(lo) & torch.isfinite(hi) & (torch.maximum(lo.abs(), hi.abs()) <= max_abs)
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

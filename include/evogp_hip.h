@@ -420,6 +420,26 @@ int evogp_hip_tree_classes_workspace_bytes(unsigned pop, unsigned long long *byt
 int evogp_hip_tree_classes(unsigned pop, unsigned gp_len, const float *value, const int16_t *type, const int16_t *size,
                            const unsigned long long *hash_in, int *class_id_out, void *workspace, evogp_stream_t stream);
 
+/* Interval arithmetic over single-output trees (Keijzer 2003; no counterpart in the reference; csrc/sr_interval.hip).  For every node i
+ * of the live prefix (n = size[t][0] clamped to [0, gp_len]) of every tree: lo[t][i], hi[t][i] (float32 in [-inf, +inf]) and flags[t][i]
+ * (bit 0 EVOGP_ITV_MAY_NAN, bit 1 EVOGP_ITV_MALFORMED) such that for ANY float32 input x with lower[v] <= x[v] <= upper[v] the float32
+ * value V the interpreters compute for the subtree rooted at i is either a NaN with MAY_NAN set or satisfies lo <= V <= hi.  The
+ * bounds are on the values as computed in fp32: + - * neg abs max min sqrt take their endpoints from the same correctly rounded
+ * operations on the operands' endpoints (exact: rounding is monotone), the divisions move the quotients of the endpoints one ulp
+ * outward, the library functions move their own results at the relevant endpoints outward by 2 E + 1 ulps (E the documented bound:
+ * sin cos 4, tan 5, sinh cosh tanh 5, log exp 3, pow 16); the extrema of sin / cos and the poles of tan are placed in float64.  The
+ * complete rule set is the numpy restatement tests/interval_ref.py, which the kernel follows operation by operation.
+ * A row whose type words fail the stack discipline, or one of whose live size words is not the size of its subtree, has lo = hi = NaN
+ * and flags = 3 on every live word (on word 0 when it has none).  Words past the live prefix are 0, 0, 0.
+ * lower / upper: float32[var_len] on the device, finite, lower <= upper (the caller checks).  One lane per tree, no dataset, no
+ * workspace, no atomics, nothing synchronises with the host; bit-identical from run to run.  Any gp_len <= 1024 and var_len >= 1.
+ * lo, hi, flags must not alias the inputs. */
+#define EVOGP_ITV_MAY_NAN 1
+#define EVOGP_ITV_MALFORMED 2
+int evogp_hip_tree_intervals(unsigned pop, unsigned gp_len, unsigned var_len, const float *value, const int16_t *type,
+                             const int16_t *size, const float *lower, const float *upper, float *lo, float *hi, unsigned char *flags,
+                             evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -563,7 +583,7 @@ int evogp_hip_get_sr_division(void);
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
- * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear
+ * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals
  * were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
