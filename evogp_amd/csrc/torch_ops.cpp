@@ -498,6 +498,38 @@ std::tuple<Tensor, Tensor, Tensor> tree_intervals(const Tensor &value, const Ten
     return {lo, hi, flags};
 }
 
+// (vlo, vhi float32, vflags uint8), each (pop, gp_len): enclosures of the real value of every subtree over the box [lower, upper]; (dlo, dhi
+// float32, dflags uint8), each (K, pop, gp_len): bounds on its partial derivative in variable wrt[k] (evogp_hip_tree_derivative_intervals)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_derivative_intervals(const Tensor &value, const Tensor &type, const Tensor &size,
+                                                                                   const Tensor &lower, const Tensor &upper, const Tensor &wrt) {
+    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
+    const int64_t pop = value.size(0), gp_len = value.size(1);
+    check_sizes(pop, gp_len);
+    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
+    const c10::Device dev = value.device();
+    check_forest(pop, gp_len, value, type, size, dev);
+    TORCH_CHECK(lower.dim() == 1 && lower.size(0) > 0, "lower must be a (var_len,) tensor with var_len > 0");
+    const int64_t var_len = lower.size(0);
+    check_tensor(lower, {var_len}, "lower", dev, at::kFloat);
+    check_tensor(upper, {var_len}, "upper", dev, at::kFloat);
+    TORCH_CHECK(wrt.dim() == 1 && wrt.size(0) > 0 && wrt.size(0) <= 65535, "wrt must be a (K,) tensor with 1 <= K <= 65535");
+    const int64_t K = wrt.size(0);
+    check_tensor(wrt, {K}, "wrt", dev, at::kInt);
+    c10::DeviceGuard guard(dev);
+    const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
+    Tensor vlo = at::empty({pop, gp_len}, value.options()), vhi = at::empty({pop, gp_len}, value.options());
+    Tensor vflags = at::empty({pop, gp_len}, bytes);
+    Tensor dlo = at::empty({K, pop, gp_len}, value.options()), dhi = at::empty({K, pop, gp_len}, value.options());
+    Tensor dflags = at::empty({K, pop, gp_len}, bytes);
+    check_rc(evogp_hip_tree_derivative_intervals((unsigned)pop, (unsigned)gp_len, (unsigned)var_len, value.data_ptr<float>(),
+                                                 type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), lower.data_ptr<float>(),
+                                                 upper.data_ptr<float>(), (unsigned)K, wrt.data_ptr<int>(), vlo.data_ptr<float>(),
+                                                 vhi.data_ptr<float>(), vflags.data_ptr<uint8_t>(), dlo.data_ptr<float>(), dhi.data_ptr<float>(),
+                                                 dflags.data_ptr<uint8_t>(), current_stream(dev)),
+             "tree_derivative_intervals");
+    return {vlo, vhi, vflags, dlo, dhi, dflags};
+}
+
 // int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
 // workspace comes from torch's caching allocator
 Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
@@ -1018,6 +1050,7 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_wrap_linear(int out_gp_len, Tensor value, Tensor node_type, Tensor subtree_size, Tensor coef)"
           " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
     m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
+    m.def("tree_derivative_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper, Tensor wrt) -> (Tensor vlo, Tensor vhi, Tensor vflags, Tensor dlo, Tensor dhi, Tensor dflags)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -1056,4 +1089,5 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_wrap_linear", &tree_wrap_linear);
     m.impl("tree_intervals", &tree_intervals);
+    m.impl("tree_derivative_intervals", &tree_derivative_intervals);
 }

@@ -41,3 +41,11 @@ def tree_intervals(value, node_type, subtree_size, lower, upper):
     subtree of every single-output tree over the box ``lower[v] <= x[v] <= upper[v]`` (float32 ``(var_len,)`` tensors on the forest's
     device); flags bit 0 = the subtree may be a NaN, bit 1 = the row is malformed"""
     return torch.ops.evogp_hip.tree_intervals(value, node_type, subtree_size, lower, upper)
+
+
+def tree_derivative_intervals(value, node_type, subtree_size, lower, upper, wrt):
+    """``(vlo, vhi, vflags, dlo, dhi, dflags)``: ``torch.ops.evogp_hip.tree_derivative_intervals`` (csrc/sr_deriv.hip).  The first three,
+    each (pop, gp_len), enclose the real value of every subtree over the box; the last three, each (K, pop, gp_len), bound its partial
+    derivative in variable ``wrt[k]`` (int32 ``(K,)`` tensor on the forest's device, each entry in [0, var_len)); dflags bit 0 = the
+    subtree may be discontinuous in that variable, bit 1 = the row is malformed, bit 2 = the variable occurs in it"""
+    return torch.ops.evogp_hip.tree_derivative_intervals(value, node_type, subtree_size, lower, upper, wrt)

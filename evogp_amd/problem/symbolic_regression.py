@@ -21,7 +21,7 @@ class SymbolicRegression(BaseProblem):
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
                  dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
-                 input_margin: float = 0.0):
+                 input_margin: float = 0.0, monotonic=None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -36,7 +36,13 @@ class SymbolicRegression(BaseProblem):
         on the whole box of admissible inputs (``Forest.safe_mask``) gets NaN from ``evaluate`` and -inf from ``scores``, whatever
         loss it has on the rows; the others keep their values bit for bit.  The box is fixed at construction: ``input_bounds="data"``
         takes the per-column minimum and maximum of ``datapoints``, each side moved outward by ``input_margin`` times the column's
-        range; or pass a ``(lower, upper)`` pair of floats or ``(num_inputs,)`` tensors."""
+        range; or pass a ``(lower, upper)`` pair of floats or ``(num_inputs,)`` tensors.
+        ``monotonic`` (shape constraints, Kronberger et al. 2022; single-output problems): ``{variable: +1 | -1 | (dmin, dmax)}``.  A
+        tree passes when it is safe on the box (``monotonic`` implies the check of ``interval_check``, on the same box) and interval
+        arithmetic over its partial derivatives proves it nondecreasing (+1) or nonincreasing (-1) in the variable, or its derivative
+        within [dmin, dmax], on the whole box (``Forest.monotone_mask``); the others get NaN / -inf as above.  With
+        ``linear_scaling`` the constraint is on the tree's shape and the fitted slope may flip it, so under a +-1 constraint
+        ``scaled_fitness`` gives a NaN loss to a tree whose slope is negative; a (dmin, dmax) pair bounds the unscaled tree."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -62,6 +68,26 @@ class SymbolicRegression(BaseProblem):
             if self.labels.dim() != 2 or self.labels.shape[1] != 1:
                 raise ValueError(f"interval_check works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
             self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
+        self.monotonic = None
+        if monotonic is not None:
+            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+                raise ValueError(f"monotonic works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+            self.monotonic = {}
+            for v, c in dict(monotonic).items():
+                if not isinstance(v, int) or not 0 <= v < self.datapoints.shape[1]:
+                    raise ValueError(f"monotonic names variable {v!r}, but the inputs are 0 .. {self.datapoints.shape[1] - 1}")
+                if isinstance(c, (tuple, list)) and len(c) == 2 and float(c[0]) <= float(c[1]):
+                    self.monotonic[v] = (float(c[0]), float(c[1]))
+                elif not isinstance(c, (tuple, list)) and c in (1, -1):
+                    self.monotonic[v] = int(c)
+                else:
+                    raise ValueError(f"a monotonic constraint must be +1, -1 or a (dmin, dmax) pair, but variable {v} has {c!r}")
+            if not self.monotonic:
+                raise ValueError("monotonic must constrain at least one variable")
+            if not self.interval_check:
+                self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
+        self._sign_constrained = self.monotonic is not None and any(isinstance(c, int) for c in self.monotonic.values())
+        self._box_check = self.interval_check or self.monotonic is not None
 
     def _input_box(self, input_bounds, margin: float):
         """the box of admissible inputs as two float32 ``(num_inputs,)`` tensors"""
@@ -84,8 +110,15 @@ class SymbolicRegression(BaseProblem):
         """(pop,) bool: ``Forest.safe_mask`` on this problem's box"""
         return forest.safe_mask(self.input_lower, self.input_upper)
 
+    def monotone_mask(self, forest: Forest) -> Tensor:
+        """(pop,) bool: ``Forest.monotone_mask`` on this problem's box with its ``monotonic`` constraints"""
+        if self.monotonic is None:
+            raise ValueError("this problem has no monotonic constraints")
+        return forest.monotone_mask(self.input_lower, self.input_upper, self.monotonic)
+
     def _masked(self, forest: Forest, fitness: Tensor, fill: float) -> Tensor:
-        return torch.where(self.safe_mask(forest).to(fitness.device), fitness, torch.full_like(fitness, fill))
+        mask = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
+        return torch.where(mask.to(fitness.device), fitness, torch.full_like(fitness, fill))
 
     @staticmethod
     def generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds):
@@ -108,7 +141,8 @@ class SymbolicRegression(BaseProblem):
         under ``execute_mode="torch"`` the same definition from ``batch_forward``'s predictions in float64 torch.  ``dedup``: None takes
         the problem's setting"""
         if self.execute_mode != "torch":
-            return forest.SR_scaled_fitness(self.datapoints, self.labels, dedup=self.dedup if dedup is None else bool(dedup))
+            return self._slope_checked(*forest.SR_scaled_fitness(self.datapoints, self.labels,
+                                                                 dedup=self.dedup if dedup is None else bool(dedup)))
         p = forest.batch_forward(self.datapoints)[:, :, 0]   # (pop, D) float32
         D = p.shape[1]
         y = self.labels.to(p.device)[:, 0].to(torch.float64)
@@ -126,7 +160,13 @@ class SymbolicRegression(BaseProblem):
         loss, a, b = loss.to(torch.float32), a.to(torch.float32), b.to(torch.float32)
         bad = ~torch.isfinite(p).all(1) | ~torch.isfinite(a) | ~torch.isfinite(b)
         nan = torch.full_like(loss, float("nan"))
-        return torch.where(bad, nan, loss), torch.where(bad, nan, b), torch.where(bad, nan, a)
+        return self._slope_checked(torch.where(bad, nan, loss), torch.where(bad, nan, b), torch.where(bad, nan, a))
+
+    def _slope_checked(self, loss: Tensor, slope: Tensor, intercept: Tensor):
+        """under a +-1 ``monotonic`` constraint a negative slope turns the proven direction round: such a tree fails (NaN loss)"""
+        if self._sign_constrained:
+            loss = torch.where(slope < 0, torch.full_like(loss, float("nan")), loss)
+        return loss, slope, intercept
 
     def scaled(self, forest: Forest, dedup: Optional[bool] = None) -> Forest:
         """``forest`` with every tree T rewritten as ``intercept + slope * T`` for its own least-squares coefficients on this problem's
@@ -140,13 +180,13 @@ class SymbolicRegression(BaseProblem):
 
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         fitness = self._evaluate(forest, use_MSE)
-        return self._masked(forest, fitness, float("nan")) if self.interval_check else fitness
+        return self._masked(forest, fitness, float("nan")) if self._box_check else fitness
 
     def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
         on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
         fitness = self._scores(forest, use_MSE)
-        return self._masked(forest, fitness, float("-inf")) if self.interval_check else fitness
+        return self._masked(forest, fitness, float("-inf")) if self._box_check else fitness
 
     def _evaluate(self, forest: Forest, use_MSE: bool) -> Tensor:
         if self.linear_scaling:

@@ -11,7 +11,8 @@ csrc/dedup.hip; ``optimize_constants`` and ``simplify`` take ``dedup=True`` to r
 descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection), ``SR_subtree_errors`` / ``simplify``
 (the loss of every subtree, and the rewrite into a smaller tree that is no worse) and ``SR_scaled_fitness`` / ``apply_scaling`` (linear
 scaling: the loss under the least-squares slope and intercept, and the tree that carries them) and ``SR_intervals`` / ``safe_mask`` (interval
-arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it).  Every heavy method is one call into
+arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it) and
+``SR_derivative_intervals`` / ``monotone_mask`` (bounds of every subtree's partial derivatives over the box, and the trees proven monotone).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -467,6 +468,62 @@ class Forest:
         lo, hi, flags = self.SR_intervals(lower, upper)
         lo, hi = lo[:, 0], hi[:, 0]
         return (flags[:, 0] == 0) & torch.isfinite(lo) & torch.isfinite(hi) & (torch.maximum(lo.abs(), hi.abs()) <= max_abs)
+
+    # ---- derivative bounds --------------------------------------------------------------------
+    def _wrt(self, wrt):
+        """the requested variables as a host list of ints, checked"""
+        if wrt is None:
+            return list(range(self.input_len))
+        idx = [wrt] if isinstance(wrt, int) else [int(v) for v in torch.as_tensor(wrt).reshape(-1).tolist()]
+        if not idx:
+            raise ValueError("wrt must name at least one variable")
+        for v in idx:
+            if not 0 <= v < self.input_len:
+                raise ValueError(f"wrt holds variable {v}, but the trees have variables 0 .. {self.input_len - 1}")
+        return idx
+
+    def _derivative_op(self, lower, upper, idx):
+        if self.output_len != 1:
+            raise ValueError(f"derivative bounds work on single-output trees only, but output_len is {self.output_len}")
+        lower, upper = self._box(lower, upper)
+        wrt = torch.tensor(idx, dtype=torch.int32).to(self.batch_node_value.device)
+        return torch.ops.evogp_hip.tree_derivative_intervals(*self._tensors(), lower, upper, wrt)
+
+    def SR_derivative_intervals(self, lower, upper, wrt=None):
+        """``(dlo, dhi, dflags)``, each (K, pop, max_tree_len): for every node of every tree and every variable ``wrt[k]`` (default: all
+        of them; a repeated index gives equal slices) a float32 interval that bounds the partial derivative of its subtree in that
+        variable at every real input of the box ``lower[v] <= x[v] <= upper[v]`` where the subtree is defined and differentiable
+        (interval arithmetic over forward-mode derivatives, Kronberger et al. 2022; csrc/sr_deriv.hip, one lane per (tree, variable),
+        no dataset, no host synchronisation beyond the checks).  ``dflags`` bit 0 (1): the subtree may be discontinuous in the
+        variable; bit 1 (2): the row is malformed (NaN bounds); bit 2 (4): the variable occurs in a branch that can be taken (a
+        subtree without it has exactly [0, 0]).  Where bit 0 is clear and the subtree is safe (``SR_intervals``), ``dlo >= 0`` proves
+        it nondecreasing and ``dhi <= 0`` nonincreasing.  The box is checked as in ``SR_intervals``; ``ValueError`` for an index
+        outside [0, input_len), an empty ``wrt`` or a multi-output forest."""
+        return tuple(self._derivative_op(lower, upper, self._wrt(wrt))[3:])
+
+    def monotone_mask(self, lower, upper, constraints, max_abs: float = float("inf")) -> Tensor:
+        """(pop,) bool: the tree is safe on the box (``safe_mask``'s rule on the enclosure of its real value) and obeys every
+        constraint of ``{variable: +1 | -1 | (dmin, dmax)}``: the bounds of its partial derivative in that variable lie within
+        [0, +inf], [-inf, 0] or [dmin, dmax] and it is known to be continuous in it.  One call of the op."""
+        idx, want = [], []
+        for v, c in dict(constraints).items():
+            if isinstance(c, (tuple, list)):
+                dmin, dmax = float(c[0]), float(c[1])
+                if not dmin <= dmax:
+                    raise ValueError(f"the derivative bounds of variable {v} must satisfy dmin <= dmax, but got {c!r}")
+            elif c in (1, -1):
+                dmin, dmax = (0.0, float("inf")) if c == 1 else (float("-inf"), 0.0)
+            else:
+                raise ValueError(f"a constraint must be +1, -1 or a (dmin, dmax) pair, but variable {v} has {c!r}")
+            idx.append(v)
+            want.append((dmin, dmax))
+        idx = self._wrt(idx)
+        vlo, vhi, vfl, dlo, dhi, dfl = self._derivative_op(lower, upper, idx)
+        vlo, vhi = vlo[:, 0], vhi[:, 0]
+        ok = (vfl[:, 0] == 0) & torch.isfinite(vlo) & torch.isfinite(vhi) & (torch.maximum(vlo.abs(), vhi.abs()) <= max_abs)
+        for k, (dmin, dmax) in enumerate(want):
+            ok = ok & ((dfl[k, :, 0] & 3) == 0) & (dlo[k, :, 0] >= dmin) & (dhi[k, :, 0] <= dmax)
+        return ok
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

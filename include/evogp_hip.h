@@ -440,6 +440,34 @@ int evogp_hip_tree_intervals(unsigned pop, unsigned gp_len, unsigned var_len, co
                              const int16_t *size, const float *lower, const float *upper, float *lo, float *hi, unsigned char *flags,
                              evogp_stream_t stream);
 
+/* Interval bounds on the partial derivatives of single-output trees (shape constraints, Kronberger et al. 2022; no counterpart in the
+ * reference; csrc/sr_deriv.hip).  Two quantities for every node i of the live prefix of every tree, over the box lower[v] <= x[v] <= upper[v].
+ * R(i) = [vlo[t][i], vhi[t][i]] with vflags[t][i] (EVOGP_ITV_*): an enclosure of the REAL value of the subtree rooted at i: the rules of
+ * evogp_hip_tree_intervals with the round-to-nearest endpoints of + - * sqrt loose_sqrt moved one ulp outward (not where the operation
+ * is exact: an endpoint sum with a zero term, a point-zero or point-one operand of *, a zero endpoint of * that is no underflow, the
+ * square root of 0); it contains the interval evogp_hip_tree_intervals
+ * gives, so it bounds the fp32 value too.
+ * D_v(i) = [dlo[k][t][i], dhi[k][t][i]] with dflags[k][t][i] for v = wrt[k]:  (a) at every real x of the box at which every node of the
+ * subtree has a defined finite real value and the subtree is differentiable in x_v, d subtree_i / d x_v lies in [dlo, dhi];  (b) if
+ * EVOGP_DRV_JUMP is clear and vflags[t][i] is 0, the subtree is continuous in x_v on the box, so dlo >= 0 means nondecreasing in x_v and
+ * dhi <= 0 nonincreasing.  EVOGP_DRV_DEPENDS: x_v occurs in a branch that can be taken; a subtree without it has exactly [0, 0] and
+ * flags 0.  The rules are forward-mode differentiation in outward-rounded interval arithmetic (the 0 x inf corner is 0, an unbounded
+ * derivative is [-inf, +inf]); pow and loose_pow give [-inf, +inf] wherever they depend on x_v.  The complete rule set is the numpy
+ * restatement tests/derivative_ref.py, which the kernels follow operation by operation.
+ * A malformed row (evogp_hip_tree_intervals's rule) has vlo = vhi = NaN, vflags = 3 and dlo = dhi = NaN, dflags = EVOGP_DRV_MALFORMED on
+ * every live word (on word 0 when it has none).  Words past the live prefix are 0 in all six outputs.
+ * lower / upper: float32[var_len] on the device, finite, lower <= upper; wrt: int32[n_wrt] on the device, each in [0, var_len) (the caller
+ * checks both); 1 <= n_wrt <= 65535; a repeated index gives equal slices.  vlo, vhi, vflags: [pop][gp_len]; dlo, dhi, dflags:
+ * [n_wrt][pop][gp_len].  Two launches (one lane per tree, then one lane per (tree, k)), no dataset, no workspace, no atomics, nothing
+ * synchronises with the host; bit-identical from run to run.  The outputs must not alias the inputs or one another. */
+#define EVOGP_DRV_JUMP 1
+#define EVOGP_DRV_MALFORMED 2
+#define EVOGP_DRV_DEPENDS 4
+int evogp_hip_tree_derivative_intervals(unsigned pop, unsigned gp_len, unsigned var_len, const float *value, const int16_t *type,
+                                        const int16_t *size, const float *lower, const float *upper, unsigned n_wrt, const int *wrt,
+                                        float *vlo, float *vhi, unsigned char *vflags, float *dlo, float *dhi, unsigned char *dflags,
+                                        evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -583,8 +611,8 @@ int evogp_hip_get_sr_division(void);
  * 6: evogp_hip_sr_gradient, evogp_hip_sr_const_step; 7: evogp_hip_sr_case_errors, evogp_hip_lexicase_workspace_bytes,
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
- * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals
- * were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
+ * then evogp_hip_tree_derivative_intervals were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
