@@ -292,6 +292,53 @@ int env_int(const char *name, int def) {
     const char *e = getenv(name);
     return e && *e ? atoi(e) : def;
 }
+
+// ---- the per-stream workspace pool (launch.hpp) ----
+StreamWorkspaces g_tape_workspaces, g_case_workspaces;
+
+float *StreamWorkspaces::get(hipStream_t stream, size_t bytes, int *rc) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu_);
+    auto &list = live_[dev & 63];
+    Block *ws = nullptr;
+    for (auto &e : list) if (e.stream == stream) ws = &e;
+    if (ws && ws->bytes >= bytes) return (float *)ws->buf;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        *rc = EVOGP_E_UNSUPPORTED;  // no allocation inside a capture
+        return nullptr;
+    }
+    void *buf = nullptr;
+    hipError_t e = engine_alloc_shared(&buf, bytes);
+    if (e != hipSuccess || !buf) {
+        (void)hipGetLastError();
+        *rc = e != hipSuccess ? (int)e : (int)hipErrorOutOfMemory;
+        return nullptr;
+    }
+    if (ws) {
+        retired_[dev & 63].push_back(ws->buf);
+        ws->buf = buf;
+        ws->bytes = bytes;
+    } else {
+        list.push_back({stream, buf, bytes});
+    }
+    return (float *)buf;
+}
+
+bool StreamWorkspaces::held() {
+    std::lock_guard<std::mutex> lock(mu_);
+    for (int d = 0; d < 64; ++d) if (!live_[d].empty() || !retired_[d].empty()) return true;
+    return false;
+}
+
+void StreamWorkspaces::release(int dev) {
+    std::lock_guard<std::mutex> lock(mu_);
+    for (auto &e : live_[dev & 63]) engine_free_shared(e.buf);
+    for (void *b : retired_[dev & 63]) engine_free_shared(b);
+    live_[dev & 63].clear();
+    retired_[dev & 63].clear();
+}
 }  // namespace evogp
 
 // ---- division mode of the SR-fitness fast path ---------------------------------------------------------------------------

@@ -1,7 +1,10 @@
-// launch.hpp — host-side helpers shared by the C-ABI launchers (device properties, work counters).
+// launch.hpp — host-side helpers shared by the C-ABI launchers (device properties, work counters, the per-stream workspace pool).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+
+#include <mutex>
+#include <vector>
 
 #include "../../include/evogp_hip.h"
 #include "../../include/evogp_hip_debug.h"   // (definitions are checked against their declarations)
@@ -67,12 +70,29 @@ void call_scratch_next_is_clean(hipStream_t stream);
 hipError_t engine_alloc_shared(void **ptr, size_t bytes);
 void engine_free_shared(void *ptr);
 
-// Global tapes of the constant-gradient kernel (sr_grad.hip): does the engine hold any, and free those of device `dev` (the caller has
-// waited for the device; evogp_hip_release_workspaces).
-bool grad_workspaces_held();
-void release_grad_workspaces(int dev);
-// The prediction buffers of the per-case errors (lexicase.hip), the same way.
-bool case_workspaces_held();
-void release_case_workspaces(int dev);
+// One engine-owned block of device memory per (device, stream) (common.hip).  Launches on one stream run one after the other, so they
+// may share a block; concurrent streams must not.  A block is never freed before release(): a graph captured earlier may point at it.
+class StreamWorkspaces {
+public:
+    // The block of `stream` on the current device, at least `bytes` long.  A larger request outside a stream capture allocates a new
+    // block (engine_alloc_shared) and RETIRES the old one; inside a capture it fails with EVOGP_E_UNSUPPORTED (make one eager call of
+    // this shape on the stream first).  nullptr and *rc on failure.
+    float *get(hipStream_t stream, size_t bytes, int *rc);
+    bool held();             // does any device hold a block, live or retired?
+    void release(int dev);   // free those of device `dev` (the caller has waited for the device; evogp_hip_release_workspaces)
+
+private:
+    struct Block { hipStream_t stream; void *buf; size_t bytes; };
+    std::mutex mu_;
+    std::vector<Block> live_[64];
+    std::vector<void *> retired_[64];
+};
+extern StreamWorkspaces g_tape_workspaces;   // the global tapes of the tape kernels (sr_forward.hpp plan_tape_launch)
+extern StreamWorkspaces g_case_workspaces;   // the predictions of the per-case errors (lexicase.hip)
+
+inline bool grad_workspaces_held() { return g_tape_workspaces.held(); }
+inline void release_grad_workspaces(int dev) { g_tape_workspaces.release(dev); }
+inline bool case_workspaces_held() { return g_case_workspaces.held(); }
+inline void release_case_workspaces(int dev) { g_case_workspaces.release(dev); }
 
 } // namespace evogp

@@ -1,8 +1,9 @@
 // lexicase.hip — per-case SR errors and epsilon-lexicase parent selection (gfx950; no counterpart in the reference).
 //
 // evogp_hip_sr_case_errors: the batch evaluation (sr_fitness.hip, the interpreters of evogp_hip_batch_evaluate) into an engine-owned
-// prediction buffer, then one epilogue kernel that reads the (pop, D, out) predictions and the labels and writes the CASE-MAJOR errors
-// errors[d][t] = (sum_o delta_o) / out_len through a 64 x 64 LDS tile (reads along d, writes along t, both coalesced).
+// prediction buffer (one per stream, from the workspace pool of launch.hpp), then one epilogue kernel that reads the (pop, D, out)
+// predictions and the labels and writes the CASE-MAJOR errors errors[d][t] = (sum_o delta_o) / out_len through a 64 x 64 LDS tile
+// (reads along d, writes along t, both coalesced).
 //
 // evogp_hip_lexicase_select: semi-dynamic epsilon-lexicase over case-major errors E[n][pop] (include/evogp_hip.h has the contract).
 // Five stages, all on the caller's stream, nothing synchronises with the host:
@@ -20,9 +21,6 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-
-#include <mutex>
-#include <vector>
 
 namespace evogp {
 
@@ -56,56 +54,8 @@ __global__ __launch_bounds__(256) void case_errors_kernel(const float *pred, con
     }
 }
 
-// The prediction buffer of a stream: grown outside stream captures, never freed before evogp_hip_release_workspaces (a graph
-// captured earlier may point at it), as the gradient tapes of sr_grad.hip.
-struct CaseWorkspace { hipStream_t stream; void *buf; size_t bytes; };
-static std::mutex g_case_mu;
-static std::vector<CaseWorkspace> g_case_ws[64];
-static std::vector<void *> g_case_retired[64];
-
-static float *case_workspace(hipStream_t stream, size_t bytes, int *rc) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(g_case_mu);
-    auto &list = g_case_ws[dev & 63];
-    CaseWorkspace *ws = nullptr;
-    for (auto &e : list) if (e.stream == stream) ws = &e;
-    if (ws && ws->bytes >= bytes) return (float *)ws->buf;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-        *rc = EVOGP_E_UNSUPPORTED;  // no allocation inside a capture: make one eager call of this shape on the stream first
-        return nullptr;
-    }
-    void *buf = nullptr;
-    hipError_t e = engine_alloc_shared(&buf, bytes);
-    if (e != hipSuccess || !buf) {
-        (void)hipGetLastError();
-        *rc = e != hipSuccess ? (int)e : (int)hipErrorOutOfMemory;
-        return nullptr;
-    }
-    if (ws) {
-        g_case_retired[dev & 63].push_back(ws->buf);
-        ws->buf = buf;
-        ws->bytes = bytes;
-    } else {
-        list.push_back({stream, buf, bytes});
-    }
-    return (float *)buf;
-}
-
-bool case_workspaces_held() {
-    std::lock_guard<std::mutex> lock(g_case_mu);
-    for (int d = 0; d < 64; ++d) if (!g_case_ws[d].empty() || !g_case_retired[d].empty()) return true;
-    return false;
-}
-
-void release_case_workspaces(int dev) {  // (the caller has waited for the device)
-    std::lock_guard<std::mutex> lock(g_case_mu);
-    for (auto &e : g_case_ws[dev & 63]) engine_free_shared(e.buf);
-    for (void *b : g_case_retired[dev & 63]) engine_free_shared(b);
-    g_case_ws[dev & 63].clear();
-    g_case_retired[dev & 63].clear();
-}
+// The prediction buffer of a stream: the engine's per-stream workspace pool (launch.hpp StreamWorkspaces), as the tapes of the tape kernels.
+static float *case_workspace(hipStream_t stream, size_t bytes, int *rc) { return g_case_workspaces.get(stream, bytes, rc); }
 
 // ---- lexicase selection --------------------------------------------------------------------------------------------------------
 constexpr unsigned kLexRowFeistel = (1u << 21);       // words 2^21 + r, r < 4: the round keys of event k's case permutation

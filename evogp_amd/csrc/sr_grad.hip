@@ -18,19 +18,13 @@
 //   * every CONST slot is reduced over the lanes with the fixed DPP butterfly (wave_sum), the waves' partials are added in wave
 //     order by one thread per node: no float atomics, bit-identical from run to run.
 //
-// The tapes live in LDS for rows of at most kGradLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in an engine-owned global
-// workspace (engine_alloc_shared) for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
-// column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.
+// The tapes live in LDS for rows of at most kTapeLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in the per-stream global
+// workspace of the tape kernels for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
+// column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.  Waves, workgroups, LDS
+// bytes and the workspace come from the plan the three tape passes share (sr_forward.hpp plan_tape_launch).
 #include "sr_adjoint.hpp"
-#include "launch.hpp"
-
-#include <mutex>
-#include <vector>
 
 namespace evogp {
-
-constexpr int kGradLdsLen = 64;      // rows up to this length keep their tapes in LDS
-constexpr int kGradMaxWaves = 4;     // waves per workgroup (row tiles of one tree)
 
 struct GradParams {
     const float *value;
@@ -40,7 +34,7 @@ struct GradParams {
     const float *y;  // [D][out_len]
     float *loss;     // [pop]
     float *grad;     // [pop][gp_len]
-    float *tape;     // global tapes (rows longer than kGradLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
+    float *tape;     // global tapes (rows longer than kTapeLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len, out_len, use_mse;
 };
 
@@ -49,7 +43,7 @@ struct GradParams {
 __host__ __device__ inline size_t grad_lds_head_words(int L, int W) { return (((size_t)4 * L + (size_t)W * L + W + 4) + 3) & ~(size_t)3; }
 
 template <bool MO>
-__global__ __launch_bounds__(kGradMaxWaves * 64) void sr_grad_kernel(GradParams p) {
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t grad_lds[];
     const int L = p.gp_len;
     const int lane = threadIdx.x & 63;
@@ -286,58 +280,6 @@ __global__ __launch_bounds__(256) void sr_const_step_kernel(StepParams q) {
     }
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------------------
-// Global tapes of rows longer than kGradLdsLen: one buffer per stream (concurrent launches must not share one), grown outside stream
-// captures, never freed before evogp_hip_release_workspaces (a graph captured earlier may point at it).
-struct GradWorkspace { hipStream_t stream; void *buf; size_t bytes; };
-static std::mutex g_grad_mu;
-static std::vector<GradWorkspace> g_grad_ws[64];
-static std::vector<void *> g_grad_retired[64];
-
-float *grad_workspace(hipStream_t stream, size_t bytes, int *rc) {  // (sr_forward.hpp: sr_subtree.hip shares it)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(g_grad_mu);
-    auto &list = g_grad_ws[dev & 63];
-    GradWorkspace *ws = nullptr;
-    for (auto &e : list) if (e.stream == stream) ws = &e;
-    if (ws && ws->bytes >= bytes) return (float *)ws->buf;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
-        *rc = EVOGP_E_UNSUPPORTED;  // no allocation inside a capture: make one eager call of this shape on the stream first
-        return nullptr;
-    }
-    void *buf = nullptr;
-    hipError_t e = engine_alloc_shared(&buf, bytes);
-    if (e != hipSuccess || !buf) {
-        (void)hipGetLastError();
-        *rc = e != hipSuccess ? (int)e : (int)hipErrorOutOfMemory;
-        return nullptr;
-    }
-    if (ws) {
-        g_grad_retired[dev & 63].push_back(ws->buf);
-        ws->buf = buf;
-        ws->bytes = bytes;
-    } else {
-        list.push_back({stream, buf, bytes});
-    }
-    return (float *)buf;
-}
-
-bool grad_workspaces_held() {
-    std::lock_guard<std::mutex> lock(g_grad_mu);
-    for (int d = 0; d < 64; ++d) if (!g_grad_ws[d].empty() || !g_grad_retired[d].empty()) return true;
-    return false;
-}
-
-void release_grad_workspaces(int dev) {  // (the caller has waited for the device)
-    std::lock_guard<std::mutex> lock(g_grad_mu);
-    for (auto &e : g_grad_ws[dev & 63]) engine_free_shared(e.buf);
-    for (void *b : g_grad_retired[dev & 63]) engine_free_shared(b);
-    g_grad_ws[dev & 63].clear();
-    g_grad_retired[dev & 63].clear();
-}
-
 }  // namespace evogp
 
 using namespace evogp;
@@ -351,41 +293,17 @@ extern "C" int evogp_hip_sr_gradient(unsigned pop_size, unsigned data_points, un
     if (!value || !type || !size || !variables || !labels || !loss || !grad) return EVOGP_E_NULLPTR;
     if (out_len > (unsigned)kMaxOutRegs) return EVOGP_E_UNSUPPORTED;
     const hipStream_t stream = (hipStream_t)stream_;
-    const DeviceInfo &dev = device_info();
     GradParams p{};
     p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.loss = loss; p.grad = grad;
     p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len; p.out_len = (int)out_len;
     p.use_mse = use_mse ? 1 : 0;
-    const int ntiles = (p.D + kWave - 1) / kWave;
-    const bool lds_tape = p.gp_len <= kGradLdsLen;
-    // Waves per workgroup: one when the population alone fills the chip, up to four (row tiles of one tree) when it does not.
-    const long fill = (long)dev.num_cus * 16;
-    int W = p.pop >= fill ? 1 : (ntiles < kGradMaxWaves ? ntiles : kGradMaxWaves);
-    size_t lds = grad_lds_head_words(p.gp_len, W) * 4;
-    long blocks;
-    if (lds_tape) {
-        lds += (size_t)W * 2 * p.gp_len * kWave * sizeof(float);
-        const long per_cu = (long)(dev.lds_per_cu / lds);
-        blocks = (long)dev.num_cus * (per_cu < 1 ? 1 : per_cu);
-    } else {
-        blocks = (long)dev.num_cus * 2 / W;  // 512 resident waves on a 256-CU device: 256 MiB of tapes at gp_len 1024
-    }
-    if (blocks > p.pop) blocks = p.pop;
-    if (!lds_tape) {
-        int rc = 0;
-        p.tape = grad_workspace(stream, (size_t)blocks * W * 2 * p.gp_len * kWave * sizeof(float), &rc);
-        if (!p.tape) return rc;
-    }
-    static std::once_flag attr_once;   // dynamic LDS beyond 64 KiB must be granted per kernel
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_err = hipFuncSetAttribute((const void *)sr_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (attr_err == hipSuccess)
-            attr_err = hipFuncSetAttribute((const void *)sr_grad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if (attr_err != hipSuccess) return (int)attr_err;
-    if (p.out_len > 1) hipLaunchKernelGGL(sr_grad_kernel<true>, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
-    else hipLaunchKernelGGL(sr_grad_kernel<false>, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
+    TapePlan plan;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, grad_lds_head_words, &plan)) return rc;
+    p.tape = plan.tape;
+    static LdsGrant grant;
+    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_grad_kernel<true>, (const void *)sr_grad_kernel<false>})) return (int)e;
+    if (p.out_len > 1) hipLaunchKernelGGL(sr_grad_kernel<true>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
+    else hipLaunchKernelGGL(sr_grad_kernel<false>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 

@@ -12,16 +12,12 @@
 // instead of d loss / d pred, so the adjoint slot of a CONST node holds the lane's J_j; and those slots are STORED per tile (a CONST
 // leaf has one parent, so one store per tile defines it) and folded into 45 register accumulators per lane after each tile's walk.
 // Lanes are reduced by the fixed DPP butterfly (wave_sum), waves in wave order through LDS: no float atomics, bit-identical from run
-// to run.  Tapes live in LDS for rows of at most kLmLdsLen nodes and in sr_grad.hip's per-stream global workspace for longer rows.
+// to run.  Tapes live in LDS for rows of at most kTapeLdsLen nodes and in the tape kernels' per-stream global workspace for longer rows;
+// the launch is the plan the three tape passes share (sr_forward.hpp plan_tape_launch), which is why the loss is sr_grad.hip's bit for bit.
 #include "sr_adjoint.hpp"
-#include "launch.hpp"
-
-#include <mutex>
 
 namespace evogp {
 
-constexpr int kLmLdsLen = 64;       // rows up to this length keep their tapes in LDS (sr_grad.hip's kGradLdsLen)
-constexpr int kLmMaxWaves = 4;      // waves per workgroup (row tiles of one tree)
 constexpr int kLmTri = kLmMaxConsts * (kLmMaxConsts + 1) / 2;   // 36: upper triangle of A
 constexpr int kLmWords = kLmTri + kLmMaxConsts;                 // 44: a row of `normal`
 constexpr int kLmPart = 48;         // words of one wave's partial sums in LDS: 44 of `normal`, the sum of r^2, padding
@@ -35,7 +31,7 @@ struct NormalEqParams {
     const float *y;  // [D]
     float *loss;     // [pop]
     float *normal;   // [pop][kLmWords]
-    float *tape;     // global tapes (rows longer than kLmLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
+    float *tape;     // global tapes (rows longer than kTapeLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len;
 };
 
@@ -68,7 +64,7 @@ __host__ __device__ inline size_t lm_lds_head_words(int L, int W) {
     return (((size_t)4 * L + (size_t)W * kLmPart + kLmMaxConsts + 4) + 3) & ~(size_t)3;
 }
 
-__global__ __launch_bounds__(kLmMaxWaves * 64) void sr_normal_eq_kernel(NormalEqParams p) {
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(NormalEqParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lm_lds[];
     const int L = p.gp_len;
     const int lane = threadIdx.x & 63;
@@ -365,38 +361,15 @@ extern "C" int evogp_hip_sr_normal_eq(unsigned pop_size, unsigned data_points, u
         return EVOGP_E_BADARG;
     if (!value || !type || !size || !variables || !labels || !loss || !normal) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    const DeviceInfo &dev = device_info();
     NormalEqParams p{};
     p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.loss = loss; p.normal = normal;
     p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len;
-    const int ntiles = (p.D + kWave - 1) / kWave;
-    const bool lds_tape = p.gp_len <= kLmLdsLen;
-    // Waves per workgroup as in evogp_hip_sr_gradient (so the two losses are summed in the same order): one when the population alone
-    // fills the chip, up to four (row tiles of one tree) when it does not.
-    const long fill = (long)dev.num_cus * 16;
-    const int W = p.pop >= fill ? 1 : (ntiles < kLmMaxWaves ? ntiles : kLmMaxWaves);
-    size_t lds = lm_lds_head_words(p.gp_len, W) * 4;
-    long blocks;
-    if (lds_tape) {
-        lds += (size_t)W * 2 * p.gp_len * kWave * sizeof(float);
-        const long per_cu = (long)(dev.lds_per_cu / lds);
-        blocks = (long)dev.num_cus * (per_cu < 1 ? 1 : per_cu);
-    } else {
-        blocks = (long)dev.num_cus * 2 / W;
-    }
-    if (blocks > p.pop) blocks = p.pop;
-    if (!lds_tape) {
-        int rc = 0;
-        p.tape = grad_workspace(stream, (size_t)blocks * W * 2 * p.gp_len * kWave * sizeof(float), &rc);
-        if (!p.tape) return rc;
-    }
-    static std::once_flag attr_once;   // dynamic LDS beyond 64 KiB must be granted per kernel
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_err = hipFuncSetAttribute((const void *)sr_normal_eq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if (attr_err != hipSuccess) return (int)attr_err;
-    hipLaunchKernelGGL(sr_normal_eq_kernel, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
+    TapePlan plan;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, lm_lds_head_words, &plan)) return rc;
+    p.tape = plan.tape;
+    static LdsGrant grant;
+    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_normal_eq_kernel})) return (int)e;
+    hipLaunchKernelGGL(sr_normal_eq_kernel, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 

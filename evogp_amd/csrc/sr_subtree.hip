@@ -16,19 +16,14 @@
 // tile of mine differed from it" (BAD), both in LDS; the last tile's lanes past D repeat row D - 1, so they cannot break it.  A node
 // is constant when no wave saw a difference and the waves' FIRSTs are one pattern.
 //
-// Tape and accumulator live in LDS for rows of at most kSubLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in the per-stream
-// engine workspace of the gradient kernel (grad_workspace: launches on one stream never overlap) for longer rows.
+// Tape and accumulator live in LDS for rows of at most kTapeLdsLen nodes (2 x 64 x 256 B = 32 KiB per wave) and in the per-stream
+// global workspace of the tape kernels (launches on one stream never overlap) for longer rows.  The launch is the plan the three tape
+// passes share (sr_forward.hpp plan_tape_launch): the same rows meet the same order of summation as in the gradient pass.
 //
 // prune_rows_kernel: one wave per tree, the rule of include/evogp_hip.h evogp_hip_prune_rows (tests/subtree_ref.py restates it).
 #include "sr_forward.hpp"
-#include "launch.hpp"
-
-#include <mutex>
 
 namespace evogp {
-
-constexpr int kSubLdsLen = 64;    // rows up to this length keep tape and accumulator in LDS
-constexpr int kSubMaxWaves = 4;   // waves per workgroup (row tiles of one tree)
 
 struct SubtreeParams {
     const float *value;
@@ -38,7 +33,7 @@ struct SubtreeParams {
     const float *y;     // [D]
     float *node_err;    // [pop][gp_len]
     float *node_const;  // [pop][gp_len]
-    float *tape;        // global tapes (rows longer than kSubLdsLen): [blocks * W][2][gp_len][64]; nullptr: they are in LDS
+    float *tape;        // global tapes (rows longer than kTapeLdsLen): [blocks * W][2][gp_len][64]; nullptr: they are in LDS
     int pop, D, gp_len, var_len, use_mse;
 };
 
@@ -46,7 +41,7 @@ struct SubtreeParams {
 // (u32), cls/len (2 words, padded to 4), then, for LDS tapes, W x 2 x L x 64 floats.
 __host__ __device__ inline size_t subtree_lds_head_words(int L, int W) { return (((size_t)4 * L + (size_t)3 * W * L + 4) + 3) & ~(size_t)3; }
 
-__global__ __launch_bounds__(kSubMaxWaves * 64) void sr_subtree_kernel(SubtreeParams p) {
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_subtree_kernel(SubtreeParams p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sub_lds[];
     const int L = p.gp_len;
     const int lane = threadIdx.x & 63;
@@ -303,37 +298,15 @@ extern "C" int evogp_hip_sr_subtree_errors(unsigned pop_size, unsigned data_poin
         return EVOGP_E_BADARG;
     if (!value || !type || !size || !variables || !labels || !node_err || !node_const) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    const DeviceInfo &dev = device_info();
     SubtreeParams p{};
     p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.node_err = node_err; p.node_const = node_const;
     p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len; p.use_mse = use_mse ? 1 : 0;
-    const int ntiles = (p.D + kWave - 1) / kWave;
-    const bool lds_tape = p.gp_len <= kSubLdsLen;
-    // Waves per workgroup and workgroups as evogp_hip_sr_gradient chooses them (the same rows meet the same order of summation)
-    const long fill = (long)dev.num_cus * 16;
-    const int W = p.pop >= fill ? 1 : (ntiles < kSubMaxWaves ? ntiles : kSubMaxWaves);
-    size_t lds = subtree_lds_head_words(p.gp_len, W) * 4;
-    long blocks;
-    if (lds_tape) {
-        lds += (size_t)W * 2 * p.gp_len * kWave * sizeof(float);
-        const long per_cu = (long)(dev.lds_per_cu / lds);
-        blocks = (long)dev.num_cus * (per_cu < 1 ? 1 : per_cu);
-    } else {
-        blocks = (long)dev.num_cus * 2 / W;
-    }
-    if (blocks > p.pop) blocks = p.pop;
-    if (!lds_tape) {
-        int rc = 0;
-        p.tape = grad_workspace(stream, (size_t)blocks * W * 2 * p.gp_len * kWave * sizeof(float), &rc);
-        if (!p.tape) return rc;
-    }
-    static std::once_flag attr_once;   // dynamic LDS beyond 64 KiB must be granted per kernel
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_err = hipFuncSetAttribute((const void *)sr_subtree_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    if (attr_err != hipSuccess) return (int)attr_err;
-    hipLaunchKernelGGL(sr_subtree_kernel, dim3((unsigned)blocks), dim3(W * 64), lds, stream, p);
+    TapePlan plan;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, subtree_lds_head_words, &plan)) return rc;
+    p.tape = plan.tape;
+    static LdsGrant grant;
+    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_subtree_kernel})) return (int)e;
+    hipLaunchKernelGGL(sr_subtree_kernel, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,11 @@
 // dtypes are checked explicitly (the reference relies on data_ptr<T>()), every tensor must live on the same device, and
 // launch errors are reported (the reference's check_cuda_error calls are commented out, :84,135,188,231,282).
 //
+// The ops are built from a few parts: Forest (a checked (value, type, size) triple with its sizes, device and typed pointers),
+// check_dataset (the prologue of the ops over a dataset), ForestOut (a fresh forest and its pointers) and Donors (the donor rows of
+// the row-range breed ops).  An op body is then: its own checks, its outputs, one C call, check_rc.  Every check comes before the
+// first allocation.
+//
 // Host code only (no kernels): compiled with g++ against the torch headers and linked to libevogp_hip.so.  There is no CPU
 // implementation and no fallback: a CPU tensor fails in the dispatcher exactly as with the reference.
 #include <ATen/ATen.h>
@@ -31,23 +36,18 @@ namespace {
 
 using at::Tensor;
 using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
+using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 constexpr int64_t kMaxStack = EVOGP_MAX_STACK;
 
+// `name` `suffix` is what an error text calls the tensor ("value" "_ori"); the text is put together only when a check fails
 void check_tensor(const Tensor &t, at::IntArrayRef shape, const char *name, const c10::Device &dev,
-                  c10::optional<at::ScalarType> dtype = c10::nullopt) {
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous CUDA tensor");
-    TORCH_CHECK(t.device() == dev, name, " lives on ", t.device(), " but the call runs on ", dev, ": all operands of one call must share a device");
-    TORCH_CHECK(t.sizes() == shape, name, " must have shape ", shape, ", but got shape ", t.sizes());
-    if (dtype) TORCH_CHECK(t.scalar_type() == *dtype, "expected scalar type ", *dtype, " for ", name, " but found ", t.scalar_type());
-}
-
-void check_forest(int64_t pop, int64_t gp_len, const Tensor &value, const Tensor &type, const Tensor &size, const c10::Device &dev,
-                  const char *suffix = "") {
-    const std::string v = std::string("value") + suffix, t = std::string("type") + suffix, s = std::string("subtree_size") + suffix;
-    check_tensor(value, {pop, gp_len}, v.c_str(), dev, at::kFloat);
-    check_tensor(type, {pop, gp_len}, t.c_str(), dev, at::kShort);
-    check_tensor(size, {pop, gp_len}, s.c_str(), dev, at::kShort);
+                  c10::optional<at::ScalarType> dtype = c10::nullopt, const char *suffix = "") {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, suffix, " must be a contiguous CUDA tensor");
+    TORCH_CHECK(t.device() == dev, name, suffix, " lives on ", t.device(), " but the call runs on ", dev,
+                ": all operands of one call must share a device");
+    TORCH_CHECK(t.sizes() == shape, name, suffix, " must have shape ", shape, ", but got shape ", t.sizes());
+    if (dtype) TORCH_CHECK(t.scalar_type() == *dtype, "expected scalar type ", *dtype, " for ", name, suffix, " but found ", t.scalar_type());
 }
 
 void check_sizes(int64_t pop_size, int64_t gp_len) {
@@ -63,11 +63,96 @@ void check_rc(int rc, const char *what) {
 // c10::DeviceGuard resolves to the registered implementation, and the stream pool is indexed by the device ordinal.)
 evogp_stream_t current_stream(const c10::Device &dev) { return (evogp_stream_t)c10::hip::getCurrentHIPStream(dev.index()).stream(); }
 
-Tensor3 empty_forest(int64_t rows, int64_t gp_len, const c10::Device &dev) {
-    return {at::empty({rows, gp_len}, at::TensorOptions().dtype(at::kFloat).device(dev)),
-            at::empty({rows, gp_len}, at::TensorOptions().dtype(at::kShort).device(dev)),
-            at::empty({rows, gp_len}, at::TensorOptions().dtype(at::kShort).device(dev))};
+Tensor empty(at::IntArrayRef shape, at::ScalarType dtype, const c10::Device &dev) {
+    return at::empty(shape, at::TensorOptions().dtype(dtype).device(dev));
 }
+
+// A checked forest: three contiguous (pop, gp_len) tensors float32 / int16 / int16 on one device.  The sizes are the caller's, or
+// those of `value` (infer; at most 2^31 - 1 rows, for every op that infers); the device is the caller's (`on`), or that of `value`.
+// A forest that goes WITH another one (donors) has no size rule of its own, only the shape: it may have no rows at all.
+struct Forest {
+    int64_t pop, gp_len;
+    c10::Device dev;
+    float *value;
+    int16_t *type, *size;
+
+    Forest(int64_t pop_size, int64_t gp_len_, const Tensor &v, const Tensor &t, const Tensor &s, const char *suffix = "",
+           const c10::Device *on = nullptr, bool goes_with_another = false)
+        : pop(pop_size), gp_len(gp_len_), dev(on ? *on : v.device()) {
+        if (!goes_with_another) check_sizes(pop, gp_len);
+        check_tensor(v, {pop, gp_len}, "value", dev, at::kFloat, suffix);
+        check_tensor(t, {pop, gp_len}, "type", dev, at::kShort, suffix);
+        check_tensor(s, {pop, gp_len}, "subtree_size", dev, at::kShort, suffix);
+        value = v.data_ptr<float>(), type = t.data_ptr<int16_t>(), size = s.data_ptr<int16_t>();
+    }
+
+    static Forest infer(const Tensor &v, const Tensor &t, const Tensor &s) {
+        TORCH_CHECK(v.dim() == 2, "value must be a (pop_size, gp_len) tensor");
+        TORCH_CHECK(v.size(0) <= 0x7FFFFFFF, "too many trees: ", v.size(0));
+        return Forest(v.size(0), v.size(1), v, t, s);
+    }
+    // `rows` donor rows for a forest on `dev` (rows >= 0: an all-elite range or generation has no offspring)
+    static Forest donors(int64_t rows, int64_t gp_len, const Tensor &v, const Tensor &t, const Tensor &s, const c10::Device &dev) {
+        return Forest(rows, gp_len, v, t, s, " (donor)", &dev, true);
+    }
+};
+
+// A fresh forest of `rows` rows on `dev` and its typed pointers.
+struct ForestOut {
+    Tensor tv, tt, ts;
+    float *value;
+    int16_t *type, *size;
+
+    ForestOut(int64_t rows, int64_t gp_len, const c10::Device &dev)
+        : tv(empty({rows, gp_len}, at::kFloat, dev)), tt(empty({rows, gp_len}, at::kShort, dev)), ts(empty({rows, gp_len}, at::kShort, dev)),
+          value(tv.data_ptr<float>()), type(tt.data_ptr<int16_t>()), size(ts.data_ptr<int16_t>()) {}
+
+    Tensor3 tuple() const { return {tv, tt, ts}; }
+    Tensor4 with(const Tensor &fourth) const { return {tv, tt, ts, fourth}; }
+};
+
+// The prologue of the ops over a dataset: the forest, the sizes, variables (data_points, var_len) and labels (data_points, out_len);
+// `op` is the op's name for its error texts.
+enum class OutLen { Any, One, UpTo16 };   // what the op allows: any positive out_len, single-output trees only, the output registers
+
+struct Dataset : Forest {
+    const float *X, *y;
+};
+
+Dataset check_dataset(const char *op, OutLen rule, int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                      const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    switch (rule) {
+    case OutLen::Any: TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len); break;
+    case OutLen::One: TORCH_CHECK(out_len == 1, op, ": single-output trees only (out_len must be 1), but got ", out_len); break;
+    case OutLen::UpTo16: TORCH_CHECK(out_len > 0 && out_len <= 16, "out_len must be in range (0, 16], but got ", out_len); break;
+    }
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
+    check_tensor(labels, {data_points, out_len}, "labels", f.dev, at::kFloat);
+    return {f, variables.data_ptr<float>(), labels.data_ptr<float>()};
+}
+
+// The donor rows of the row-range breed ops.  The donor arrays are aligned with the OFFSPRING rows of the range: they may cover the
+// whole range (row_count rows; the rows of elites are never read) or only its offspring (row_count minus the elite rows at the head
+// of the range) -- then no padding copy is needed.  The engine indexes donors by (row - row_begin), so the pointers are rewound by
+// the rows that are left out.
+struct Donors {
+    const float *value;
+    const int16_t *type, *size;
+
+    Donors(const Tensor &v, const Tensor &t, const Tensor &s, int64_t row_begin, int64_t row_count, int64_t n_elite, int64_t gp_len,
+           const c10::Device &dev) {
+        const int64_t head = std::max<int64_t>(0, std::min(row_begin + row_count, n_elite) - row_begin);  // elite rows at the head of the range
+        const int64_t drows = v.dim() == 2 ? v.size(0) : -1;
+        TORCH_CHECK(drows == row_count || drows == row_count - head, "donor arrays must have ", row_count, " or ", row_count - head,
+                    " rows, but got ", drows);
+        const Forest f = Forest::donors(drows, gp_len, v, t, s, dev);
+        const int64_t skip = drows == row_count - head ? head : 0;
+        value = f.value - skip * gp_len, type = f.type - skip * gp_len, size = f.size - skip * gp_len;
+    }
+};
 
 // the reference reads keys.data_ptr<unsigned int>() (torch_wrapper.cu:76); signed integer keys carry the same 32-bit patterns
 Tensor keys_u32(const Tensor &keys) {
@@ -76,9 +161,10 @@ Tensor keys_u32(const Tensor &keys) {
     return keys.to(at::kLong).bitwise_and(0xFFFFFFFFLL).to(at::kUInt32).contiguous();
 }
 
-Tensor3 generate_impl(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len, double out_prob,
-                      double const_prob, const Tensor &keys_in, const Tensor &depth2leaf_probs, const Tensor &roulette_funcs,
-                      const Tensor &const_samples, int64_t tree_index_offset, const Tensor *active_word, int64_t active_below) {
+// what the three generators check: the sizes, the probabilities, the 32-bit arguments and the three tables (on the device of the first)
+void check_generate(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len, double out_prob,
+                    double const_prob, int64_t tree_index_offset, int64_t active_below, const Tensor &depth2leaf_probs,
+                    const Tensor &roulette_funcs, const Tensor &const_samples, const c10::Device &dev) {
     check_sizes(pop_size, gp_len);
     TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
     TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len);
@@ -87,23 +173,29 @@ Tensor3 generate_impl(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t
     TORCH_CHECK(const_prob >= 0 && const_prob <= 1, "const_prob must be in range [0, 1], but got ", const_prob);
     TORCH_CHECK(tree_index_offset >= 0 && tree_index_offset < (1LL << 32), "tree_index_offset must fit in 32 bits");
     TORCH_CHECK(active_below >= 0 && active_below < (1LL << 32), "active_below must fit in 32 bits");
-    const c10::Device dev = keys_in.device();
-    check_tensor(keys_in, {2}, "keys", dev);
     check_tensor(depth2leaf_probs, {EVOGP_MAX_FULL_DEPTH}, "depth2leaf_probs", dev, at::kFloat);
     check_tensor(roulette_funcs, {EVOGP_NUM_FUNCS}, "roulette_funcs", dev, at::kFloat);
     check_tensor(const_samples, {const_samples_len}, "const_samples", dev, at::kFloat);
+}
+
+Tensor3 generate_impl(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len, double out_prob,
+                      double const_prob, const Tensor &keys_in, const Tensor &depth2leaf_probs, const Tensor &roulette_funcs,
+                      const Tensor &const_samples, int64_t tree_index_offset, const Tensor *active_word, int64_t active_below) {
+    const c10::Device dev = keys_in.device();
+    check_generate(pop_size, gp_len, var_len, out_len, const_samples_len, out_prob, const_prob, tree_index_offset, active_below,
+                   depth2leaf_probs, roulette_funcs, const_samples, dev);
+    check_tensor(keys_in, {2}, "keys", dev);
     if (active_word) check_tensor(*active_word, {pop_size}, "active_word", dev, at::kInt);
     const Tensor keys = keys_u32(keys_in);
     c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size, gp_len, dev);
-    const int rc = evogp_hip_generate_masked(
-        (unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, (unsigned)const_samples_len, (float)out_prob,
-        (float)const_prob, (const unsigned *)keys.data_ptr(), depth2leaf_probs.data_ptr<float>(), roulette_funcs.data_ptr<float>(),
-        const_samples.data_ptr<float>(), std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-        std::get<2>(out).data_ptr<int16_t>(), (unsigned)tree_index_offset, active_word ? active_word->data_ptr<int>() : nullptr,
-        (unsigned)active_below, current_stream(dev));
-    check_rc(rc, "tree_generate");
-    return out;
+    const ForestOut out(pop_size, gp_len, dev);
+    check_rc(evogp_hip_generate_masked((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, (unsigned)const_samples_len,
+                                       (float)out_prob, (float)const_prob, (const unsigned *)keys.data_ptr(), depth2leaf_probs.data_ptr<float>(),
+                                       roulette_funcs.data_ptr<float>(), const_samples.data_ptr<float>(), out.value, out.type, out.size,
+                                       (unsigned)tree_index_offset, active_word ? active_word->data_ptr<int>() : nullptr, (unsigned)active_below,
+                                       current_stream(dev)),
+             "tree_generate");
+    return out.tuple();
 }
 
 // rows of trees whose counter-based word (4, n + tree_index_offset) of (seed, generation) is not below active_below are left
@@ -111,24 +203,17 @@ Tensor3 generate_impl(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t
 Tensor3 tree_generate_masked_hashed(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, int64_t const_samples_len, double out_prob,
                                     double const_prob, const Tensor &depth2leaf_probs, const Tensor &roulette_funcs, const Tensor &const_samples,
                                     int64_t tree_index_offset, int64_t seed, int64_t generation, int64_t active_below) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0 && out_len > 0 && const_samples_len > 0, "var_len, out_len and const_samples_len must be larger than 0");
-    TORCH_CHECK(out_prob >= 0 && out_prob <= 1 && const_prob >= 0 && const_prob <= 1, "out_prob / const_prob must be in range [0, 1]");
-    TORCH_CHECK(tree_index_offset >= 0 && tree_index_offset < (1LL << 32) && active_below >= 0 && active_below < (1LL << 32),
-                "tree_index_offset / active_below must fit in 32 bits");
     const c10::Device dev = depth2leaf_probs.device();
-    check_tensor(depth2leaf_probs, {EVOGP_MAX_FULL_DEPTH}, "depth2leaf_probs", dev, at::kFloat);
-    check_tensor(roulette_funcs, {EVOGP_NUM_FUNCS}, "roulette_funcs", dev, at::kFloat);
-    check_tensor(const_samples, {const_samples_len}, "const_samples", dev, at::kFloat);
+    check_generate(pop_size, gp_len, var_len, out_len, const_samples_len, out_prob, const_prob, tree_index_offset, active_below,
+                   depth2leaf_probs, roulette_funcs, const_samples, dev);
     c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size, gp_len, dev);
-    const int rc = evogp_hip_generate_masked_hashed(
-        (unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, (unsigned)const_samples_len, (float)out_prob, (float)const_prob,
-        depth2leaf_probs.data_ptr<float>(), roulette_funcs.data_ptr<float>(), const_samples.data_ptr<float>(), std::get<0>(out).data_ptr<float>(),
-        std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(), (unsigned)tree_index_offset, seed, generation,
-        (unsigned)active_below, current_stream(dev));
-    check_rc(rc, "tree_generate_masked_hashed");
-    return out;
+    const ForestOut out(pop_size, gp_len, dev);
+    check_rc(evogp_hip_generate_masked_hashed((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, (unsigned)const_samples_len,
+                                              (float)out_prob, (float)const_prob, depth2leaf_probs.data_ptr<float>(), roulette_funcs.data_ptr<float>(),
+                                              const_samples.data_ptr<float>(), out.value, out.type, out.size, (unsigned)tree_index_offset, seed,
+                                              generation, (unsigned)active_below, current_stream(dev)),
+             "tree_generate_masked_hashed");
+    return out.tuple();
 }
 
 // ---- the reference's five ops -------------------------------------------------------------------------------------------
@@ -141,19 +226,16 @@ Tensor3 tree_generate(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t
 
 Tensor3 tree_mutate(int64_t pop_size, int64_t gp_len, const Tensor &value_ori, const Tensor &type_ori, const Tensor &size_ori,
                     const Tensor &mutate_indices, const Tensor &value_new, const Tensor &type_new, const Tensor &size_new) {
-    check_sizes(pop_size, gp_len);
     const c10::Device dev = value_new.device();
-    check_forest(pop_size, gp_len, value_ori, type_ori, size_ori, dev, "_ori");
+    const Forest ori(pop_size, gp_len, value_ori, type_ori, size_ori, "_ori", &dev);
     check_tensor(mutate_indices, {pop_size}, "mutateIndices", dev, at::kInt);
-    check_forest(pop_size, gp_len, value_new, type_new, size_new, dev, "_new");
+    const Forest fresh(pop_size, gp_len, value_new, type_new, size_new, "_new");
     c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size, gp_len, dev);
-    const int rc = evogp_hip_mutate((int)pop_size, (int)gp_len, value_ori.data_ptr<float>(), type_ori.data_ptr<int16_t>(),
-                                    size_ori.data_ptr<int16_t>(), mutate_indices.data_ptr<int>(), value_new.data_ptr<float>(),
-                                    type_new.data_ptr<int16_t>(), size_new.data_ptr<int16_t>(), std::get<0>(out).data_ptr<float>(),
-                                    std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(), current_stream(dev));
-    check_rc(rc, "tree_mutate");
-    return out;
+    const ForestOut out(pop_size, gp_len, dev);
+    check_rc(evogp_hip_mutate((int)pop_size, (int)gp_len, ori.value, ori.type, ori.size, mutate_indices.data_ptr<int>(), fresh.value, fresh.type,
+                              fresh.size, out.value, out.type, out.size, current_stream(dev)),
+             "tree_mutate");
+    return out.tuple();
 }
 
 Tensor3 tree_crossover(int64_t pop_size_ori, int64_t pop_size_new, int64_t gp_len, const Tensor &value_ori, const Tensor &type_ori,
@@ -161,75 +243,62 @@ Tensor3 tree_crossover(int64_t pop_size_ori, int64_t pop_size_new, int64_t gp_le
                        const Tensor &right_node_idx) {
     TORCH_CHECK(pop_size_ori > 0, "pop_size_ori must be larger than 0, but got ", pop_size_ori);
     TORCH_CHECK(pop_size_new > 0, "pop_size_new must be larger than 0, but got ", pop_size_new);
-    TORCH_CHECK(gp_len > 0 && gp_len <= kMaxStack, "gp_len must be in range (0, ", kMaxStack, "], but got ", gp_len);
-    const c10::Device dev = value_ori.device();
-    check_forest(pop_size_ori, gp_len, value_ori, type_ori, size_ori, dev, "_ori");
+    const Forest ori(pop_size_ori, gp_len, value_ori, type_ori, size_ori, "_ori");
+    const c10::Device dev = ori.dev;
     check_tensor(left_idx, {pop_size_new}, "left_idx", dev, at::kInt);
     check_tensor(right_idx, {pop_size_new}, "right_idx", dev, at::kInt);
     check_tensor(left_node_idx, {pop_size_new}, "left_node_idx", dev, at::kInt);
     check_tensor(right_node_idx, {pop_size_new}, "right_node_idx", dev, at::kInt);
     c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size_new, gp_len, dev);
-    const int rc = evogp_hip_crossover((int)pop_size_ori, (int)pop_size_new, (int)gp_len, value_ori.data_ptr<float>(),
-                                       type_ori.data_ptr<int16_t>(), size_ori.data_ptr<int16_t>(), left_idx.data_ptr<int>(),
-                                       right_idx.data_ptr<int>(), left_node_idx.data_ptr<int>(), right_node_idx.data_ptr<int>(),
-                                       std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-                                       std::get<2>(out).data_ptr<int16_t>(), current_stream(dev));
-    check_rc(rc, "tree_crossover");
-    return out;
+    const ForestOut out(pop_size_new, gp_len, dev);
+    check_rc(evogp_hip_crossover((int)pop_size_ori, (int)pop_size_new, (int)gp_len, ori.value, ori.type, ori.size, left_idx.data_ptr<int>(),
+                                 right_idx.data_ptr<int>(), left_node_idx.data_ptr<int>(), right_node_idx.data_ptr<int>(), out.value, out.type,
+                                 out.size, current_stream(dev)),
+             "tree_crossover");
+    return out.tuple();
 }
 
 Tensor tree_evaluate(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value, const Tensor &type,
                      const Tensor &size, const Tensor &variables) {
-    check_sizes(pop_size, gp_len);
+    const Forest f(pop_size, gp_len, value, type, size);
     TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
     TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {pop_size, var_len}, "variables", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor results = at::empty({pop_size, out_len}, value.options());
-    const int rc = evogp_hip_evaluate((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, value.data_ptr<float>(),
-                                      type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), variables.data_ptr<float>(),
-                                      results.data_ptr<float>(), current_stream(dev));
-    check_rc(rc, "tree_evaluate");
+    check_tensor(variables, {pop_size, var_len}, "variables", f.dev, at::kFloat);
+    c10::DeviceGuard guard(f.dev);
+    Tensor results = empty({pop_size, out_len}, at::kFloat, f.dev);
+    check_rc(evogp_hip_evaluate((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value, f.type, f.size,
+                                variables.data_ptr<float>(), results.data_ptr<float>(), current_stream(f.dev)),
+             "tree_evaluate");
     return results;
 }
 
-Tensor sr_fitness_impl(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
+Tensor sr_fitness_impl(const char *op, int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                        const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
                        int64_t kernel_type, int64_t func_mask = 0) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
-    TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len);
-    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    const Dataset d = check_dataset(op, OutLen::Any, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
     TORCH_CHECK(kernel_type >= 0 && kernel_type <= 4, "kernel_type must be in 0..4, but got ", kernel_type);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor fitness = at::empty({pop_size}, value.options());
     TORCH_CHECK(func_mask >= 0 && func_mask < (1LL << 32), "func_mask must fit in 32 bits");
-    const int rc = evogp_hip_sr_fitness_hinted((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
-                                               use_mse ? 1 : 0, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                               variables.data_ptr<float>(), labels.data_ptr<float>(), fitness.data_ptr<float>(),
-                                               (unsigned)kernel_type, (unsigned)func_mask, current_stream(dev));
-    check_rc(rc, "tree_SR_fitness");
+    c10::DeviceGuard guard(d.dev);
+    Tensor fitness = empty({pop_size}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_fitness_hinted((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                         use_mse ? 1 : 0, d.value, d.type, d.size, d.X, d.y, fitness.data_ptr<float>(), (unsigned)kernel_type,
+                                         (unsigned)func_mask, current_stream(d.dev)),
+             op);
     return fitness;
 }
 
 Tensor tree_SR_fitness(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                        const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
                        int64_t kernel_type) {
-    return sr_fitness_impl(pop_size, data_points, gp_len, var_len, out_len, use_mse, value, type, size, variables, labels, kernel_type);
+    return sr_fitness_impl("tree_SR_fitness", pop_size, data_points, gp_len, var_len, out_len, use_mse, value, type, size, variables, labels, kernel_type);
 }
 
 // tree_SR_fitness for a caller that knows the set of functions that can occur in the forest (0: unknown) -- include/evogp_hip.h
 Tensor tree_SR_fitness_masked(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                               const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
                               int64_t kernel_type, int64_t func_mask) {
-    return sr_fitness_impl(pop_size, data_points, gp_len, var_len, out_len, use_mse, value, type, size, variables, labels, kernel_type, func_mask);
+    return sr_fitness_impl("tree_SR_fitness_masked", pop_size, data_points, gp_len, var_len, out_len, use_mse, value, type, size, variables, labels, kernel_type,
+                           func_mask);
 }
 
 // ---- extra ops (no counterpart in the reference) ------------------------------------------------------------------------
@@ -237,20 +306,11 @@ Tensor tree_SR_fitness_masked(int64_t pop_size, int64_t data_points, int64_t gp_
 std::tuple<Tensor, Tensor> tree_SR_gradient(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                                             const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
                                             const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
-    TORCH_CHECK(out_len > 0 && out_len <= 16, "out_len must be in range (0, 16], but got ", out_len);
-    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor loss = at::empty({pop_size}, value.options());
-    Tensor grad = at::empty({pop_size, gp_len}, value.options());
+    const Dataset d = check_dataset("tree_SR_gradient", OutLen::UpTo16, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), grad = empty({pop_size, gp_len}, at::kFloat, d.dev);
     check_rc(evogp_hip_sr_gradient((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, use_mse ? 1 : 0,
-                                   value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), variables.data_ptr<float>(),
-                                   labels.data_ptr<float>(), loss.data_ptr<float>(), grad.data_ptr<float>(), current_stream(dev)),
+                                   d.value, d.type, d.size, d.X, d.y, loss.data_ptr<float>(), grad.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_gradient");
     return {loss, grad};
 }
@@ -259,21 +319,12 @@ std::tuple<Tensor, Tensor> tree_SR_gradient(int64_t pop_size, int64_t data_point
 std::tuple<Tensor, Tensor> tree_SR_subtree_errors(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
                                                   bool use_mse, const Tensor &value, const Tensor &type, const Tensor &size,
                                                   const Tensor &variables, const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
-    TORCH_CHECK(out_len == 1, "tree_SR_subtree_errors: single-output trees only (out_len must be 1), but got ", out_len);
-    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor node_err = at::empty({pop_size, gp_len}, value.options());
-    Tensor node_const = at::empty({pop_size, gp_len}, value.options());
+    const Dataset d = check_dataset("tree_SR_subtree_errors", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor node_err = empty({pop_size, gp_len}, at::kFloat, d.dev), node_const = empty({pop_size, gp_len}, at::kFloat, d.dev);
     check_rc(evogp_hip_sr_subtree_errors((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
-                                         use_mse ? 1 : 0, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                         variables.data_ptr<float>(), labels.data_ptr<float>(), node_err.data_ptr<float>(),
-                                         node_const.data_ptr<float>(), current_stream(dev)),
+                                         use_mse ? 1 : 0, d.value, d.type, d.size, d.X, d.y, node_err.data_ptr<float>(),
+                                         node_const.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_subtree_errors");
     return {node_err, node_const};
 }
@@ -282,67 +333,44 @@ std::tuple<Tensor, Tensor> tree_SR_subtree_errors(int64_t pop_size, int64_t data
 std::tuple<Tensor, Tensor> tree_SR_linear_scaling(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
                                                   const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
                                                   const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
-    TORCH_CHECK(out_len == 1, "tree_SR_linear_scaling: single-output trees only (out_len must be 1), but got ", out_len);
-    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor loss = at::empty({pop_size}, value.options());
-    Tensor coef = at::empty({pop_size, 2}, value.options());
-    check_rc(evogp_hip_sr_linear_scaling((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
-                                         value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                         variables.data_ptr<float>(), labels.data_ptr<float>(), loss.data_ptr<float>(), coef.data_ptr<float>(),
-                                         current_stream(dev)),
+    const Dataset d = check_dataset("tree_SR_linear_scaling", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), coef = empty({pop_size, 2}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_linear_scaling((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
+                                         d.type, d.size, d.X, d.y, loss.data_ptr<float>(), coef.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_linear_scaling");
     return {loss, coef};
 }
 
 // every row T as ADD(MUL(T, slope), intercept) in rows of out_gp_len words (evogp_hip_wrap_linear); applied (pop,) uint8
-std::tuple<Tensor, Tensor, Tensor, Tensor> tree_wrap_linear(int64_t out_gp_len, const Tensor &value, const Tensor &type, const Tensor &size,
-                                                            const Tensor &coef) {
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
-    const int64_t pop_size = value.size(0), gp_len = value.size(1);
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(out_gp_len >= gp_len && out_gp_len <= kMaxStack, "out_gp_len must be in range [", gp_len, ", ", kMaxStack, "], but got ", out_gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(coef, {pop_size, 2}, "coef", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size, out_gp_len, dev);
-    Tensor applied = at::empty({pop_size}, at::TensorOptions().dtype(at::kByte).device(dev));
-    check_rc(evogp_hip_wrap_linear((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-                                   size.data_ptr<int16_t>(), coef.data_ptr<float>(), std::get<0>(out).data_ptr<float>(),
-                                   std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(), applied.data_ptr<uint8_t>(),
-                                   current_stream(dev)),
+Tensor4 tree_wrap_linear(int64_t out_gp_len, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &coef) {
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(out_gp_len >= f.gp_len && out_gp_len <= kMaxStack, "out_gp_len must be in range [", f.gp_len, ", ", kMaxStack, "], but got ", out_gp_len);
+    check_tensor(coef, {f.pop, 2}, "coef", f.dev, at::kFloat);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(f.pop, out_gp_len, f.dev);
+    Tensor applied = empty({f.pop}, at::kByte, f.dev);
+    check_rc(evogp_hip_wrap_linear((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)out_gp_len, f.value, f.type, f.size, coef.data_ptr<float>(), out.value,
+                                   out.type, out.size, applied.data_ptr<uint8_t>(), current_stream(f.dev)),
              "tree_wrap_linear");
-    return {std::get<0>(out), std::get<1>(out), std::get<2>(out), applied};
+    return out.with(applied);
 }
 
 // hoist the best subtree, fold the row-constant ones (evogp_hip_prune_rows): a new forest, the chosen roots and their losses
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> tree_prune(int64_t out_len, bool hoist, bool fold, const Tensor &value, const Tensor &type,
                                                               const Tensor &size, const Tensor &node_err, const Tensor &node_const) {
     TORCH_CHECK(out_len == 1, "tree_prune: single-output trees only (out_len must be 1), but got ", out_len);
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
-    const int64_t pop_size = value.size(0), gp_len = value.size(1);
-    check_sizes(pop_size, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(node_err, {pop_size, gp_len}, "node_err", dev, at::kFloat);
-    check_tensor(node_const, {pop_size, gp_len}, "node_const", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor out_value = at::empty_like(value), out_type = at::empty_like(type), out_size = at::empty_like(size);
-    Tensor root_pos = at::empty({pop_size}, value.options().dtype(at::kInt));
-    Tensor loss = at::empty({pop_size}, value.options());
-    check_rc(evogp_hip_prune_rows((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_len, hoist ? 1 : 0, fold ? 1 : 0, value.data_ptr<float>(),
-                                  type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), node_err.data_ptr<float>(), node_const.data_ptr<float>(),
-                                  out_value.data_ptr<float>(), out_type.data_ptr<int16_t>(), out_size.data_ptr<int16_t>(),
-                                  root_pos.data_ptr<int>(), loss.data_ptr<float>(), current_stream(dev)),
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(node_err, {f.pop, f.gp_len}, "node_err", f.dev, at::kFloat);
+    check_tensor(node_const, {f.pop, f.gp_len}, "node_const", f.dev, at::kFloat);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(f.pop, f.gp_len, f.dev);
+    Tensor root_pos = empty({f.pop}, at::kInt, f.dev), loss = empty({f.pop}, at::kFloat, f.dev);
+    check_rc(evogp_hip_prune_rows((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)out_len, hoist ? 1 : 0, fold ? 1 : 0, f.value, f.type, f.size,
+                                  node_err.data_ptr<float>(), node_const.data_ptr<float>(), out.value, out.type, out.size, root_pos.data_ptr<int>(),
+                                  loss.data_ptr<float>(), current_stream(f.dev)),
              "tree_prune");
-    return {out_value, out_type, out_size, root_pos, loss};
+    return {out.tv, out.tt, out.ts, root_pos, loss};
 }
 
 // one iteration of the constant descent, in place (include/evogp_hip.h evogp_hip_sr_const_step); phase 2 ignores loss_cand / grad_cand
@@ -350,24 +378,20 @@ void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tens
                         Tensor grad, const Tensor &loss_cand, const Tensor &grad_cand, Tensor step) {
     TORCH_CHECK(phase >= 1 && phase <= 3, "phase must be 1, 2 or 3, but got ", phase);
     TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len);
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
-    const int64_t pop_size = value.size(0), gp_len = value.size(1);
-    check_sizes(pop_size, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(value_cand, {pop_size, gp_len}, "value_cand", dev, at::kFloat);
-    check_tensor(loss, {pop_size}, "loss", dev, at::kFloat);
-    check_tensor(grad, {pop_size, gp_len}, "grad", dev, at::kFloat);
-    check_tensor(step, {pop_size}, "step", dev, at::kFloat);
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(value_cand, {f.pop, f.gp_len}, "value_cand", f.dev, at::kFloat);
+    check_tensor(loss, {f.pop}, "loss", f.dev, at::kFloat);
+    check_tensor(grad, {f.pop, f.gp_len}, "grad", f.dev, at::kFloat);
+    check_tensor(step, {f.pop}, "step", f.dev, at::kFloat);
     if (phase & 1) {
-        check_tensor(loss_cand, {pop_size}, "loss_cand", dev, at::kFloat);
-        check_tensor(grad_cand, {pop_size, gp_len}, "grad_cand", dev, at::kFloat);
+        check_tensor(loss_cand, {f.pop}, "loss_cand", f.dev, at::kFloat);
+        check_tensor(grad_cand, {f.pop, f.gp_len}, "grad_cand", f.dev, at::kFloat);
     }
-    c10::DeviceGuard guard(dev);
-    check_rc(evogp_hip_sr_const_step((unsigned)pop_size, (unsigned)gp_len, (unsigned)out_len, (int)phase, value.data_ptr<float>(),
-                                     type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), value_cand.data_ptr<float>(), loss.data_ptr<float>(),
-                                     grad.data_ptr<float>(), (phase & 1) ? loss_cand.data_ptr<float>() : nullptr,
-                                     (phase & 1) ? grad_cand.data_ptr<float>() : nullptr, step.data_ptr<float>(), current_stream(dev)),
+    c10::DeviceGuard guard(f.dev);
+    check_rc(evogp_hip_sr_const_step((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)out_len, (int)phase, f.value, f.type, f.size,
+                                     value_cand.data_ptr<float>(), loss.data_ptr<float>(), grad.data_ptr<float>(),
+                                     (phase & 1) ? loss_cand.data_ptr<float>() : nullptr, (phase & 1) ? grad_cand.data_ptr<float>() : nullptr,
+                                     step.data_ptr<float>(), current_stream(f.dev)),
              "tree_SR_const_step");
 }
 
@@ -375,20 +399,11 @@ void tree_SR_const_step(int64_t phase, int64_t out_len, Tensor value, const Tens
 std::tuple<Tensor, Tensor> tree_SR_normal_eq(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
                                              const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
                                              const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
-    TORCH_CHECK(out_len == 1, "tree_SR_normal_eq: single-output trees only (out_len must be 1), but got ", out_len);
-    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor loss = at::empty({pop_size}, value.options());
-    Tensor normal = at::empty({pop_size, (int64_t)EVOGP_LM_NORMAL_WORDS}, value.options());
-    check_rc(evogp_hip_sr_normal_eq((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
-                                    value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), variables.data_ptr<float>(),
-                                    labels.data_ptr<float>(), loss.data_ptr<float>(), normal.data_ptr<float>(), current_stream(dev)),
+    const Dataset d = check_dataset("tree_SR_normal_eq", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), normal = empty({pop_size, (int64_t)EVOGP_LM_NORMAL_WORDS}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_normal_eq((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value, d.type,
+                                    d.size, d.X, d.y, loss.data_ptr<float>(), normal.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_normal_eq");
     return {loss, normal};
 }
@@ -397,41 +412,31 @@ std::tuple<Tensor, Tensor> tree_SR_normal_eq(int64_t pop_size, int64_t data_poin
 void tree_SR_lm_step(int64_t phase, Tensor value, const Tensor &type, const Tensor &size, Tensor value_cand, Tensor loss, Tensor normal,
                      const Tensor &loss_cand, const Tensor &normal_cand, Tensor damping) {
     TORCH_CHECK(phase >= 1 && phase <= 3, "phase must be 1, 2 or 3, but got ", phase);
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop_size, gp_len) tensor");
-    const int64_t pop_size = value.size(0), gp_len = value.size(1), words = EVOGP_LM_NORMAL_WORDS;
-    check_sizes(pop_size, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(value_cand, {pop_size, gp_len}, "value_cand", dev, at::kFloat);
-    check_tensor(loss, {pop_size}, "loss", dev, at::kFloat);
-    check_tensor(normal, {pop_size, words}, "normal", dev, at::kFloat);
-    check_tensor(damping, {pop_size}, "damping", dev, at::kFloat);
+    const Forest f = Forest::infer(value, type, size);
+    const int64_t words = EVOGP_LM_NORMAL_WORDS;
+    check_tensor(value_cand, {f.pop, f.gp_len}, "value_cand", f.dev, at::kFloat);
+    check_tensor(loss, {f.pop}, "loss", f.dev, at::kFloat);
+    check_tensor(normal, {f.pop, words}, "normal", f.dev, at::kFloat);
+    check_tensor(damping, {f.pop}, "damping", f.dev, at::kFloat);
     if (phase & 1) {
-        check_tensor(loss_cand, {pop_size}, "loss_cand", dev, at::kFloat);
-        check_tensor(normal_cand, {pop_size, words}, "normal_cand", dev, at::kFloat);
+        check_tensor(loss_cand, {f.pop}, "loss_cand", f.dev, at::kFloat);
+        check_tensor(normal_cand, {f.pop, words}, "normal_cand", f.dev, at::kFloat);
     }
-    c10::DeviceGuard guard(dev);
-    check_rc(evogp_hip_sr_lm_step((unsigned)pop_size, (unsigned)gp_len, 1u, (int)phase, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-                                  size.data_ptr<int16_t>(), value_cand.data_ptr<float>(), loss.data_ptr<float>(), normal.data_ptr<float>(),
-                                  (phase & 1) ? loss_cand.data_ptr<float>() : nullptr, (phase & 1) ? normal_cand.data_ptr<float>() : nullptr,
-                                  damping.data_ptr<float>(), current_stream(dev)),
+    c10::DeviceGuard guard(f.dev);
+    check_rc(evogp_hip_sr_lm_step((unsigned)f.pop, (unsigned)f.gp_len, 1u, (int)phase, f.value, f.type, f.size, value_cand.data_ptr<float>(),
+                                  loss.data_ptr<float>(), normal.data_ptr<float>(), (phase & 1) ? loss_cand.data_ptr<float>() : nullptr,
+                                  (phase & 1) ? normal_cand.data_ptr<float>() : nullptr, damping.data_ptr<float>(), current_stream(f.dev)),
              "tree_SR_lm_step");
 }
 
 // case-major per-case errors (D, pop) of every tree (include/evogp_hip.h evogp_hip_sr_case_errors), validated like tree_batch_evaluate
 Tensor tree_SR_case_errors(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, bool use_mse,
                            const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(var_len > 0 && out_len > 0 && data_points > 0, "var_len, out_len and data_points must be positive");
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor errors = at::empty({data_points, pop_size}, value.options());
+    const Dataset d = check_dataset("tree_SR_case_errors", OutLen::Any, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor errors = empty({data_points, pop_size}, at::kFloat, d.dev);
     check_rc(evogp_hip_sr_case_errors((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
-                                      use_mse ? 1 : 0, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                      variables.data_ptr<float>(), labels.data_ptr<float>(), errors.data_ptr<float>(), current_stream(dev)),
+                                      use_mse ? 1 : 0, d.value, d.type, d.size, d.X, d.y, errors.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_case_errors");
     return errors;
 }
@@ -447,11 +452,11 @@ Tensor lexicase_select(const Tensor &errors, const Tensor &eps, int64_t n_events
     const c10::Device dev = errors.device();
     check_tensor(eps, {n}, "eps", dev, at::kFloat);
     c10::DeviceGuard guard(dev);
-    Tensor winners = at::empty({n_events}, at::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor winners = empty({n_events}, at::kInt, dev);
     if (n_events == 0) return winners;
     unsigned long long bytes = 0;
     check_rc(evogp_hip_lexicase_workspace_bytes((unsigned)n, (unsigned)pop, (unsigned)n_events, &bytes), "lexicase_select");
-    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, dev);
     check_rc(evogp_hip_lexicase_select((unsigned)n, (unsigned)pop, errors.data_ptr<float>(), eps.data_ptr<float>(), (unsigned)n_events, seed,
                                        generation, winners.data_ptr<int>(), ws.data_ptr(), current_stream(dev)),
              "lexicase_select");
@@ -460,40 +465,34 @@ Tensor lexicase_select(const Tensor &errors, const Tensor &eps, int64_t n_events
 
 // int64[pop]: the bits of the 64-bit structure hash of every tree (evogp_hip_tree_hash)
 Tensor tree_hash(const Tensor &value, const Tensor &type, const Tensor &size) {
-    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    c10::DeviceGuard guard(dev);
-    Tensor hash = at::empty({pop}, at::TensorOptions().dtype(at::kLong).device(dev));
-    check_rc(evogp_hip_tree_hash((unsigned)pop, (unsigned)gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                 (unsigned long long *)hash.data_ptr<int64_t>(), current_stream(dev)),
+    const Forest f = Forest::infer(value, type, size);
+    c10::DeviceGuard guard(f.dev);
+    Tensor hash = empty({f.pop}, at::kLong, f.dev);
+    check_rc(evogp_hip_tree_hash((unsigned)f.pop, (unsigned)f.gp_len, f.value, f.type, f.size, (unsigned long long *)hash.data_ptr<int64_t>(),
+                                 current_stream(f.dev)),
              "tree_hash");
     return hash;
+}
+
+// the box of the interval ops: lower and upper, (var_len,) float32 each; returns var_len
+int64_t check_box(const Tensor &lower, const Tensor &upper, const c10::Device &dev) {
+    TORCH_CHECK(lower.dim() == 1 && lower.size(0) > 0, "lower must be a (var_len,) tensor with var_len > 0");
+    check_tensor(lower, {lower.size(0)}, "lower", dev, at::kFloat);
+    check_tensor(upper, {lower.size(0)}, "upper", dev, at::kFloat);
+    return lower.size(0);
 }
 
 // (lo float32, hi float32, flags uint8), each (pop, gp_len): the interval of every subtree over the box [lower, upper] (evogp_hip_tree_intervals)
 std::tuple<Tensor, Tensor, Tensor> tree_intervals(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &lower,
                                                   const Tensor &upper) {
-    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    TORCH_CHECK(lower.dim() == 1 && lower.size(0) > 0, "lower must be a (var_len,) tensor with var_len > 0");
-    const int64_t var_len = lower.size(0);
-    check_tensor(lower, {var_len}, "lower", dev, at::kFloat);
-    check_tensor(upper, {var_len}, "upper", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor lo = at::empty({pop, gp_len}, value.options());
-    Tensor hi = at::empty({pop, gp_len}, value.options());
-    Tensor flags = at::empty({pop, gp_len}, at::TensorOptions().dtype(at::kByte).device(dev));
-    check_rc(evogp_hip_tree_intervals((unsigned)pop, (unsigned)gp_len, (unsigned)var_len, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-                                      size.data_ptr<int16_t>(), lower.data_ptr<float>(), upper.data_ptr<float>(), lo.data_ptr<float>(),
-                                      hi.data_ptr<float>(), flags.data_ptr<uint8_t>(), current_stream(dev)),
+    const Forest f = Forest::infer(value, type, size);
+    const int64_t var_len = check_box(lower, upper, f.dev);
+    c10::DeviceGuard guard(f.dev);
+    Tensor lo = empty({f.pop, f.gp_len}, at::kFloat, f.dev), hi = empty({f.pop, f.gp_len}, at::kFloat, f.dev);
+    Tensor flags = empty({f.pop, f.gp_len}, at::kByte, f.dev);
+    check_rc(evogp_hip_tree_intervals((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)var_len, f.value, f.type, f.size, lower.data_ptr<float>(),
+                                      upper.data_ptr<float>(), lo.data_ptr<float>(), hi.data_ptr<float>(), flags.data_ptr<uint8_t>(),
+                                      current_stream(f.dev)),
              "tree_intervals");
     return {lo, hi, flags};
 }
@@ -502,30 +501,20 @@ std::tuple<Tensor, Tensor, Tensor> tree_intervals(const Tensor &value, const Ten
 // float32, dflags uint8), each (K, pop, gp_len): bounds on its partial derivative in variable wrt[k] (evogp_hip_tree_derivative_intervals)
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_derivative_intervals(const Tensor &value, const Tensor &type, const Tensor &size,
                                                                                    const Tensor &lower, const Tensor &upper, const Tensor &wrt) {
-    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    TORCH_CHECK(lower.dim() == 1 && lower.size(0) > 0, "lower must be a (var_len,) tensor with var_len > 0");
-    const int64_t var_len = lower.size(0);
-    check_tensor(lower, {var_len}, "lower", dev, at::kFloat);
-    check_tensor(upper, {var_len}, "upper", dev, at::kFloat);
+    const Forest f = Forest::infer(value, type, size);
+    const int64_t var_len = check_box(lower, upper, f.dev);
     TORCH_CHECK(wrt.dim() == 1 && wrt.size(0) > 0 && wrt.size(0) <= 65535, "wrt must be a (K,) tensor with 1 <= K <= 65535");
     const int64_t K = wrt.size(0);
-    check_tensor(wrt, {K}, "wrt", dev, at::kInt);
-    c10::DeviceGuard guard(dev);
-    const auto bytes = at::TensorOptions().dtype(at::kByte).device(dev);
-    Tensor vlo = at::empty({pop, gp_len}, value.options()), vhi = at::empty({pop, gp_len}, value.options());
-    Tensor vflags = at::empty({pop, gp_len}, bytes);
-    Tensor dlo = at::empty({K, pop, gp_len}, value.options()), dhi = at::empty({K, pop, gp_len}, value.options());
-    Tensor dflags = at::empty({K, pop, gp_len}, bytes);
-    check_rc(evogp_hip_tree_derivative_intervals((unsigned)pop, (unsigned)gp_len, (unsigned)var_len, value.data_ptr<float>(),
-                                                 type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), lower.data_ptr<float>(),
-                                                 upper.data_ptr<float>(), (unsigned)K, wrt.data_ptr<int>(), vlo.data_ptr<float>(),
-                                                 vhi.data_ptr<float>(), vflags.data_ptr<uint8_t>(), dlo.data_ptr<float>(), dhi.data_ptr<float>(),
-                                                 dflags.data_ptr<uint8_t>(), current_stream(dev)),
+    check_tensor(wrt, {K}, "wrt", f.dev, at::kInt);
+    c10::DeviceGuard guard(f.dev);
+    Tensor vlo = empty({f.pop, f.gp_len}, at::kFloat, f.dev), vhi = empty({f.pop, f.gp_len}, at::kFloat, f.dev);
+    Tensor vflags = empty({f.pop, f.gp_len}, at::kByte, f.dev);
+    Tensor dlo = empty({K, f.pop, f.gp_len}, at::kFloat, f.dev), dhi = empty({K, f.pop, f.gp_len}, at::kFloat, f.dev);
+    Tensor dflags = empty({K, f.pop, f.gp_len}, at::kByte, f.dev);
+    check_rc(evogp_hip_tree_derivative_intervals((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)var_len, f.value, f.type, f.size,
+                                                 lower.data_ptr<float>(), upper.data_ptr<float>(), (unsigned)K, wrt.data_ptr<int>(),
+                                                 vlo.data_ptr<float>(), vhi.data_ptr<float>(), vflags.data_ptr<uint8_t>(), dlo.data_ptr<float>(),
+                                                 dhi.data_ptr<float>(), dflags.data_ptr<uint8_t>(), current_stream(f.dev)),
              "tree_derivative_intervals");
     return {vlo, vhi, vflags, dlo, dhi, dflags};
 }
@@ -533,21 +522,15 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_derivative_inter
 // int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
 // workspace comes from torch's caching allocator
 Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
-    TORCH_CHECK(value.is_cuda() && value.dim() == 2, "value must be a CUDA tensor of shape (pop, gp_len)");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    TORCH_CHECK(pop <= 0x7FFFFFFF, "too many trees: ", pop);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    check_tensor(hash, {pop}, "hash", dev, at::kLong);
-    c10::DeviceGuard guard(dev);
-    Tensor class_id = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(hash, {f.pop}, "hash", f.dev, at::kLong);
+    c10::DeviceGuard guard(f.dev);
+    Tensor class_id = empty({f.pop}, at::kInt, f.dev);
     unsigned long long bytes = 0;
-    check_rc(evogp_hip_tree_classes_workspace_bytes((unsigned)pop, &bytes), "tree_classes");
-    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-    check_rc(evogp_hip_tree_classes((unsigned)pop, (unsigned)gp_len, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                    (const unsigned long long *)hash.data_ptr<int64_t>(), class_id.data_ptr<int>(), ws.data_ptr(),
-                                    current_stream(dev)),
+    check_rc(evogp_hip_tree_classes_workspace_bytes((unsigned)f.pop, &bytes), "tree_classes");
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_tree_classes((unsigned)f.pop, (unsigned)f.gp_len, f.value, f.type, f.size, (const unsigned long long *)hash.data_ptr<int64_t>(),
+                                    class_id.data_ptr<int>(), ws.data_ptr(), current_stream(f.dev)),
              "tree_classes");
     return class_id;
 }
@@ -563,12 +546,10 @@ Tensor3 pareto_rank(const Tensor &err, const Tensor &cx, int64_t cx_bound) {
     const c10::Device dev = err.device();
     check_tensor(cx, {pop}, "cx", dev, at::kInt);
     c10::DeviceGuard guard(dev);
-    Tensor front = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
-    Tensor crowding = at::empty({pop}, err.options());
-    Tensor order = at::empty({pop}, at::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor front = empty({pop}, at::kInt, dev), crowding = empty({pop}, at::kFloat, dev), order = empty({pop}, at::kInt, dev);
     unsigned long long bytes = 0;
     check_rc(evogp_hip_pareto_rank_workspace_bytes((unsigned)pop, &bytes), "pareto_rank");
-    Tensor ws = at::empty({(int64_t)bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, dev);
     check_rc(evogp_hip_pareto_rank((unsigned)pop, (unsigned)cx_bound, err.data_ptr<float>(), cx.data_ptr<int>(), front.data_ptr<int>(),
                                    crowding.data_ptr<float>(), order.data_ptr<int>(), ws.data_ptr(), current_stream(dev)),
              "pareto_rank");
@@ -586,7 +567,7 @@ Tensor nsga2_select(const Tensor &order, int64_t pool, int64_t n, int64_t t_size
     TORCH_CHECK(n >= 0 && n <= 0x7FFFFFFF, "n must be in [0, 2^31), but got ", n);
     const c10::Device dev = order.device();
     c10::DeviceGuard guard(dev);
-    Tensor winners = at::empty({n}, at::TensorOptions().dtype(at::kInt).device(dev));
+    Tensor winners = empty({n}, at::kInt, dev);
     if (n == 0) return winners;
     check_rc(evogp_hip_nsga2_select((unsigned)pop, order.data_ptr<int>(), (unsigned)pool, (unsigned)n, (unsigned)t_size, seed, generation,
                                     winners.data_ptr<int>(), current_stream(dev)),
@@ -612,37 +593,31 @@ Tensor3 tree_generate_masked(int64_t pop_size, int64_t gp_len, int64_t var_len, 
 
 Tensor tree_batch_evaluate(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
                            const Tensor &type, const Tensor &size, const Tensor &variables) {
-    check_sizes(pop_size, gp_len);
+    const Forest f(pop_size, gp_len, value, type, size);
     TORCH_CHECK(var_len > 0 && out_len > 0 && data_points > 0, "var_len, out_len and data_points must be positive");
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor results = at::empty({pop_size, data_points, out_len}, value.options());
-    const int rc = evogp_hip_batch_evaluate((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len,
-                                            (unsigned)out_len, value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(),
-                                            variables.data_ptr<float>(), results.data_ptr<float>(), current_stream(dev));
-    check_rc(rc, "tree_batch_evaluate");
+    check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
+    c10::DeviceGuard guard(f.dev);
+    Tensor results = empty({pop_size, data_points, out_len}, at::kFloat, f.dev);
+    check_rc(evogp_hip_batch_evaluate((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value,
+                                      f.type, f.size, variables.data_ptr<float>(), results.data_ptr<float>(), current_stream(f.dev)),
+             "tree_batch_evaluate");
     return results;
 }
 
 // counts[t] = #rows whose arg-max output (as torch.argmax(clip(softmax(.))) sees it) equals the int32 label
 Tensor tree_batch_argmax_count(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
                                const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
-    check_sizes(pop_size, gp_len);
+    const Forest f(pop_size, gp_len, value, type, size);
     TORCH_CHECK(data_points > 0 && var_len > 0, "data_points and var_len must be larger than 0");
     TORCH_CHECK(out_len >= 2 && out_len <= 16, "out_len must be in [2, 16], but got ", out_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {data_points, var_len}, "variables", dev, at::kFloat);
-    check_tensor(labels, {data_points}, "labels", dev, at::kInt);
-    c10::DeviceGuard guard(dev);
-    Tensor counts = at::empty({pop_size}, at::TensorOptions().dtype(at::kInt).device(dev));
-    const int rc = evogp_hip_batch_argmax_count((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len,
-                                                (unsigned)out_len, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-                                                size.data_ptr<int16_t>(), variables.data_ptr<float>(), labels.data_ptr<int>(),
-                                                (unsigned *)counts.data_ptr<int>(), current_stream(dev));
-    check_rc(rc, "tree_batch_argmax_count");
+    check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
+    check_tensor(labels, {data_points}, "labels", f.dev, at::kInt);
+    c10::DeviceGuard guard(f.dev);
+    Tensor counts = empty({pop_size}, at::kInt, f.dev);
+    check_rc(evogp_hip_batch_argmax_count((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value,
+                                          f.type, f.size, variables.data_ptr<float>(), labels.data_ptr<int>(), (unsigned *)counts.data_ptr<int>(),
+                                          current_stream(f.dev)),
+             "tree_batch_argmax_count");
     return counts;
 }
 
@@ -650,39 +625,33 @@ Tensor tree_batch_argmax_count(int64_t pop_size, int64_t data_points, int64_t gp
 // the lists cannot express, which tree_evaluate_prepared then has to send through the stack interpreter)
 std::tuple<Tensor, Tensor> tree_evaluate_prepare(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
                                                  const Tensor &type, const Tensor &size) {
-    check_sizes(pop_size, gp_len);
+    const Forest f(pop_size, gp_len, value, type, size);
     TORCH_CHECK(var_len > 0 && var_len <= 255, "var_len must be in [1, 255], but got ", var_len);
     TORCH_CHECK(out_len >= 2 && out_len <= 32, "out_len must be in [2, 32], but got ", out_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    c10::DeviceGuard guard(dev);
+    c10::DeviceGuard guard(f.dev);
     const int64_t bytes = (int64_t)evogp_hip_evaluate_workspace_bytes((unsigned)pop_size, (unsigned)gp_len);
-    Tensor ws = at::empty({bytes}, at::TensorOptions().dtype(at::kByte).device(dev));
-    const int rc = evogp_hip_evaluate_prepare((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, value.data_ptr<float>(),
-                                              type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), ws.data_ptr(), (size_t)bytes, current_stream(dev));
-    check_rc(rc, "tree_evaluate_prepare");
+    Tensor ws = empty({bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_evaluate_prepare((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value, f.type, f.size,
+                                        ws.data_ptr(), (size_t)bytes, current_stream(f.dev)),
+             "tree_evaluate_prepare");
     Tensor info = ws.narrow(0, bytes - 64, 64).view(at::kInt);
     return {ws, info};
 }
 
 Tensor tree_evaluate_prepared(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value, const Tensor &type,
                               const Tensor &size, const Tensor &workspace, bool with_fallback, const Tensor &variables) {
-    check_sizes(pop_size, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
-    check_tensor(variables, {pop_size, var_len}, "variables", dev, at::kFloat);
-    check_tensor(workspace, {(int64_t)evogp_hip_evaluate_workspace_bytes((unsigned)pop_size, (unsigned)gp_len)}, "workspace", dev, at::kByte);
-    c10::DeviceGuard guard(dev);
-    Tensor results = at::empty({pop_size, out_len}, value.options());
-    const int rc = evogp_hip_evaluate_prepared((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, value.data_ptr<float>(),
-                                               type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), workspace.data_ptr(), with_fallback ? 1 : 0,
-                                               variables.data_ptr<float>(), results.data_ptr<float>(), current_stream(dev));
-    check_rc(rc, "tree_evaluate_prepared");
+    const Forest f(pop_size, gp_len, value, type, size);
+    check_tensor(variables, {pop_size, var_len}, "variables", f.dev, at::kFloat);
+    check_tensor(workspace, {(int64_t)evogp_hip_evaluate_workspace_bytes((unsigned)pop_size, (unsigned)gp_len)}, "workspace", f.dev, at::kByte);
+    c10::DeviceGuard guard(f.dev);
+    Tensor results = empty({pop_size, out_len}, at::kFloat, f.dev);
+    check_rc(evogp_hip_evaluate_prepared((unsigned)pop_size, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value, f.type, f.size,
+                                         workspace.data_ptr(), with_fallback ? 1 : 0, variables.data_ptr<float>(), results.data_ptr<float>(),
+                                         current_stream(f.dev)),
+             "tree_evaluate_prepared");
     return results;
 }
 
-// int32[rows][n_cols] whose columns [lo, hi) hold the counter-based random words of (seed, generation) (breed.hip); the other
-// columns are uninitialised
 // scores = NaN -> -inf, else -errors (negate) or errors: the sign of SymbolicRegression.evaluate and the NaN scrub of StandardPipeline.step in one launch
 Tensor fitness_scores(const Tensor &errors, bool negate) {
     TORCH_CHECK(errors.is_cuda() && errors.scalar_type() == at::kFloat && errors.is_contiguous() && errors.dim() == 1 && errors.numel() > 0,
@@ -694,6 +663,8 @@ Tensor fitness_scores(const Tensor &errors, bool negate) {
     return out;
 }
 
+// int32[rows][n_cols] whose columns [lo, hi) hold the counter-based random words of (seed, generation) (breed.hip); the other
+// columns are uninitialised
 Tensor random_words(int64_t seed, int64_t generation, int64_t rows, int64_t n_cols, int64_t lo, int64_t hi, c10::Device device) {
     TORCH_CHECK(device.is_cuda(), "random_words: the native generator runs on the GPU");
     TORCH_CHECK(rows > 0 && n_cols > 0 && lo >= 0 && lo <= hi && hi <= n_cols, "random_words: column range out of the array");
@@ -759,66 +730,54 @@ void check_order(const Tensor &order, int64_t need, const c10::Device &dev) {
                 "order must be a contiguous int32 CUDA vector of >= max(n_elite, n_surv) entries on the forest's device");
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor> breed_default(int64_t pop_size, int64_t gp_len, int64_t n_elite, int64_t n_surv, const Tensor &value,
-                                                         const Tensor &type, const Tensor &size, const Tensor &order, const Tensor &rnd,
-                                                         int64_t mutate_below, const Tensor &donor_value, const Tensor &donor_type,
-                                                         const Tensor &donor_size, bool want_decisions) {
-    check_sizes(pop_size, gp_len);
+Tensor4 breed_default(int64_t pop_size, int64_t gp_len, int64_t n_elite, int64_t n_surv, const Tensor &value, const Tensor &type,
+                      const Tensor &size, const Tensor &order, const Tensor &rnd, int64_t mutate_below, const Tensor &donor_value,
+                      const Tensor &donor_type, const Tensor &donor_size, bool want_decisions) {
+    const Forest f(pop_size, gp_len, value, type, size);
     TORCH_CHECK(n_elite >= 0 && n_elite <= pop_size, "n_elite must be in [0, pop_size], but got ", n_elite);
     TORCH_CHECK(n_surv > 0 && n_surv <= pop_size, "n_surv must be in (0, pop_size], but got ", n_surv);
     TORCH_CHECK(mutate_below >= 0 && mutate_below < (1LL << 32), "mutate_below must fit in 32 bits");
-    const c10::Device dev = value.device();
-    check_forest(pop_size, gp_len, value, type, size, dev);
     const int64_t n_new = pop_size - n_elite;
-    check_order(order, std::max(n_elite, n_surv), dev);
-    check_tensor(rnd, {6, n_new}, "rnd", dev, at::kInt);
-    check_forest(n_new, gp_len, donor_value, donor_type, donor_size, dev, " (donor)");
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop_size, gp_len, dev);
-    Tensor dec = at::empty({want_decisions ? n_new : 0, 6}, at::TensorOptions().dtype(at::kInt).device(dev));
-    const int rc = evogp_hip_breed_default((int)pop_size, (int)gp_len, (int)n_elite, (int)n_surv, value.data_ptr<float>(),
-                                           type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), order.data_ptr<int>(), rnd.data_ptr<int>(),
-                                           (unsigned)mutate_below, donor_value.data_ptr<float>(), donor_type.data_ptr<int16_t>(),
-                                           donor_size.data_ptr<int16_t>(), std::get<0>(out).data_ptr<float>(),
-                                           std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(),
-                                           want_decisions ? dec.data_ptr<int>() : nullptr, current_stream(dev));
-    check_rc(rc, "breed_default");
-    return {std::get<0>(out), std::get<1>(out), std::get<2>(out), dec};
+    check_order(order, std::max(n_elite, n_surv), f.dev);
+    check_tensor(rnd, {6, n_new}, "rnd", f.dev, at::kInt);
+    const Forest donors = Forest::donors(n_new, gp_len, donor_value, donor_type, donor_size, f.dev);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(pop_size, gp_len, f.dev);
+    Tensor dec = empty({want_decisions ? n_new : 0, 6}, at::kInt, f.dev);
+    check_rc(evogp_hip_breed_default((int)pop_size, (int)gp_len, (int)n_elite, (int)n_surv, f.value, f.type, f.size, order.data_ptr<int>(),
+                                     rnd.data_ptr<int>(), (unsigned)mutate_below, donors.value, donors.type, donors.size, out.value, out.type, out.size,
+                                     want_decisions ? dec.data_ptr<int>() : nullptr, current_stream(f.dev)),
+             "breed_default");
+    return out.with(dec);
 }
 
-// Rows [row_begin, row_begin + row_count) of the next generation.  value / type / size: the whole population, or only the
-// trees `order` names (a sharded run's survivor table).  The donor arrays are aligned with the OFFSPRING rows of the range:
-// they may cover the whole range (row_count rows; the rows of elites are never read) or only its offspring (row_count minus
-// the elite rows at the head of the range) -- then no padding copy is needed.
-Tensor3 breed_default_rows(int64_t pop_size, int64_t gp_len, int64_t n_elite, int64_t n_surv, const Tensor &value, const Tensor &type,
-                           const Tensor &size, const Tensor &order, const Tensor &rnd, int64_t mutate_below, const Tensor &donor_value,
-                           const Tensor &donor_type, const Tensor &donor_size, int64_t row_begin, int64_t row_count) {
+// The table of the row-range breed ops: value / type / size hold the whole population, or only the trees the selection names (a sharded
+// run's survivor table), in rows of gp_len words; [row_begin, row_begin + row_count) are the rows of the next generation to make.
+Forest check_breed_rows(int64_t pop_size, int64_t gp_len, const Tensor &value, const Tensor &type, const Tensor &size, int64_t mutate_below,
+                        int64_t row_begin, int64_t row_count) {
     check_sizes(pop_size, gp_len);
-    TORCH_CHECK(n_elite >= 0 && n_elite <= pop_size && n_surv > 0 && n_surv <= pop_size, "n_elite / n_surv out of range");
     TORCH_CHECK(row_begin >= 0 && row_count > 0 && row_begin + row_count <= pop_size, "row range out of the population");
     TORCH_CHECK(mutate_below >= 0 && mutate_below < (1LL << 32), "mutate_below must fit in 32 bits");
     TORCH_CHECK(value.dim() == 2 && value.size(0) > 0, "value must be a (rows, gp_len) tensor");
-    const int64_t table_rows = value.size(0);
-    const c10::Device dev = value.device();
-    check_forest(table_rows, gp_len, value, type, size, dev);
-    check_order(order, std::max(n_elite, n_surv), dev);
-    check_tensor(rnd, {6, pop_size - n_elite}, "rnd", dev, at::kInt);
-    const int64_t head = std::max<int64_t>(0, std::min(row_begin + row_count, n_elite) - row_begin);  // elite rows at the head of the range
-    const int64_t drows = donor_value.dim() == 2 ? donor_value.size(0) : -1;
-    TORCH_CHECK(drows == row_count || drows == row_count - head, "donor arrays must have ", row_count, " or ", row_count - head,
-                " rows, but got ", drows);
-    check_forest(drows, gp_len, donor_value, donor_type, donor_size, dev, " (donor)");
-    const int64_t skip = drows == row_count - head ? head : 0;  // the engine indexes donors by (row - row_begin)
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(row_count, gp_len, dev);
-    const int rc = evogp_hip_breed_default_table(
-        (int)pop_size, (int)table_rows, (int)gp_len, (int)n_elite, (int)n_surv, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-        size.data_ptr<int16_t>(), order.data_ptr<int>(), rnd.data_ptr<int>(), (unsigned)mutate_below,
-        donor_value.data_ptr<float>() - skip * gp_len, donor_type.data_ptr<int16_t>() - skip * gp_len,
-        donor_size.data_ptr<int16_t>() - skip * gp_len, std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-        std::get<2>(out).data_ptr<int16_t>(), nullptr, (int)row_begin, (int)row_count, current_stream(dev));
-    check_rc(rc, "breed_default_rows");
-    return out;
+    return Forest(value.size(0), gp_len, value, type, size);
+}
+
+// Rows [row_begin, row_begin + row_count) of the next generation from the survivor order (the donors: Donors above).
+Tensor3 breed_default_rows(int64_t pop_size, int64_t gp_len, int64_t n_elite, int64_t n_surv, const Tensor &value, const Tensor &type,
+                           const Tensor &size, const Tensor &order, const Tensor &rnd, int64_t mutate_below, const Tensor &donor_value,
+                           const Tensor &donor_type, const Tensor &donor_size, int64_t row_begin, int64_t row_count) {
+    const Forest f = check_breed_rows(pop_size, gp_len, value, type, size, mutate_below, row_begin, row_count);
+    TORCH_CHECK(n_elite >= 0 && n_elite <= pop_size && n_surv > 0 && n_surv <= pop_size, "n_elite / n_surv out of range");
+    check_order(order, std::max(n_elite, n_surv), f.dev);
+    check_tensor(rnd, {6, pop_size - n_elite}, "rnd", f.dev, at::kInt);
+    const Donors donors(donor_value, donor_type, donor_size, row_begin, row_count, n_elite, gp_len, f.dev);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(row_count, gp_len, f.dev);
+    check_rc(evogp_hip_breed_default_table((int)pop_size, (int)f.pop, (int)gp_len, (int)n_elite, (int)n_surv, f.value, f.type, f.size,
+                                           order.data_ptr<int>(), rnd.data_ptr<int>(), (unsigned)mutate_below, donors.value, donors.type, donors.size,
+                                           out.value, out.type, out.size, nullptr, (int)row_begin, (int)row_count, current_stream(f.dev)),
+             "breed_default_rows");
+    return out.tuple();
 }
 
 // The same rows for ANY selection operator: the elites and the parents are two lists of table rows (parents may repeat, as
@@ -826,42 +785,26 @@ Tensor3 breed_default_rows(int64_t pop_size, int64_t gp_len, int64_t n_elite, in
 Tensor3 breed_rows_impl(int64_t pop_size, int64_t gp_len, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &elite_rows,
                         const Tensor &parent_rows, const Tensor *rnd_or_null, int64_t seed, int64_t generation, int64_t mutate_below,
                         const Tensor &donor_value, const Tensor &donor_type, const Tensor &donor_size, int64_t row_begin, int64_t row_count) {
-    check_sizes(pop_size, gp_len);
-    TORCH_CHECK(row_begin >= 0 && row_count > 0 && row_begin + row_count <= pop_size, "row range out of the population");
-    TORCH_CHECK(mutate_below >= 0 && mutate_below < (1LL << 32), "mutate_below must fit in 32 bits");
-    TORCH_CHECK(value.dim() == 2 && value.size(0) > 0, "value must be a (rows, gp_len) tensor");
-    const int64_t table_rows = value.size(0);
-    const c10::Device dev = value.device();
-    check_forest(table_rows, gp_len, value, type, size, dev);
+    const Forest f = check_breed_rows(pop_size, gp_len, value, type, size, mutate_below, row_begin, row_count);
     TORCH_CHECK(elite_rows.dim() == 1 && parent_rows.dim() == 1, "elite_rows / parent_rows must be vectors");
     const int64_t n_elite = elite_rows.size(0), n_surv = parent_rows.size(0);
     TORCH_CHECK(n_elite <= pop_size && n_surv > 0, "need n_elite <= pop_size and at least one parent, got ", n_elite, ", ", n_surv);
-    check_order(parent_rows, n_surv, dev);
-    if (n_elite > 0) check_order(elite_rows, n_elite, dev);
-    if (rnd_or_null) check_tensor(*rnd_or_null, {6, pop_size - n_elite}, "rnd", dev, at::kInt);
-    const int64_t head = std::max<int64_t>(0, std::min(row_begin + row_count, n_elite) - row_begin);
-    const int64_t drows = donor_value.dim() == 2 ? donor_value.size(0) : -1;
-    TORCH_CHECK(drows == row_count || drows == row_count - head, "donor arrays must have ", row_count, " or ", row_count - head,
-                " rows, but got ", drows);
-    check_forest(drows, gp_len, donor_value, donor_type, donor_size, dev, " (donor)");
-    const int64_t skip = drows == row_count - head ? head : 0;
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(row_count, gp_len, dev);
+    check_order(parent_rows, n_surv, f.dev);
+    if (n_elite > 0) check_order(elite_rows, n_elite, f.dev);
+    if (rnd_or_null) check_tensor(*rnd_or_null, {6, pop_size - n_elite}, "rnd", f.dev, at::kInt);
+    const Donors donors(donor_value, donor_type, donor_size, row_begin, row_count, n_elite, gp_len, f.dev);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(row_count, gp_len, f.dev);
+    const int *elites = n_elite > 0 ? elite_rows.data_ptr<int>() : nullptr, *parents = parent_rows.data_ptr<int>();
     const int rc = rnd_or_null
-        ? evogp_hip_breed_lists(
-              (int)pop_size, (int)table_rows, (int)gp_len, (int)n_elite, (int)n_surv, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-              size.data_ptr<int16_t>(), n_elite > 0 ? elite_rows.data_ptr<int>() : nullptr, parent_rows.data_ptr<int>(), rnd_or_null->data_ptr<int>(),
-              (unsigned)mutate_below, donor_value.data_ptr<float>() - skip * gp_len, donor_type.data_ptr<int16_t>() - skip * gp_len,
-              donor_size.data_ptr<int16_t>() - skip * gp_len, std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-              std::get<2>(out).data_ptr<int16_t>(), nullptr, (int)row_begin, (int)row_count, current_stream(dev))
-        : evogp_hip_breed_lists_hashed(
-              (int)pop_size, (int)table_rows, (int)gp_len, (int)n_elite, (int)n_surv, value.data_ptr<float>(), type.data_ptr<int16_t>(),
-              size.data_ptr<int16_t>(), n_elite > 0 ? elite_rows.data_ptr<int>() : nullptr, parent_rows.data_ptr<int>(), seed, generation,
-              (unsigned)mutate_below, donor_value.data_ptr<float>() - skip * gp_len, donor_type.data_ptr<int16_t>() - skip * gp_len,
-              donor_size.data_ptr<int16_t>() - skip * gp_len, std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-              std::get<2>(out).data_ptr<int16_t>(), nullptr, (int)row_begin, (int)row_count, current_stream(dev));
+        ? evogp_hip_breed_lists((int)pop_size, (int)f.pop, (int)gp_len, (int)n_elite, (int)n_surv, f.value, f.type, f.size, elites, parents,
+                                rnd_or_null->data_ptr<int>(), (unsigned)mutate_below, donors.value, donors.type, donors.size, out.value, out.type,
+                                out.size, nullptr, (int)row_begin, (int)row_count, current_stream(f.dev))
+        : evogp_hip_breed_lists_hashed((int)pop_size, (int)f.pop, (int)gp_len, (int)n_elite, (int)n_surv, f.value, f.type, f.size, elites, parents, seed,
+                                       generation, (unsigned)mutate_below, donors.value, donors.type, donors.size, out.value, out.type, out.size,
+                                       nullptr, (int)row_begin, (int)row_count, current_stream(f.dev));
     check_rc(rc, "breed_rows");
-    return out;
+    return out.tuple();
 }
 
 Tensor3 breed_rows(int64_t pop_size, int64_t gp_len, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &elite_rows,
@@ -879,67 +822,55 @@ Tensor3 breed_rows_hashed(int64_t pop_size, int64_t gp_len, const Tensor &value,
                            donor_type, donor_size, row_begin, row_count);
 }
 
+// the (pop, 2) decisions of the native mutations, or an empty tensor
+Tensor decisions(bool want, int64_t pop, const c10::Device &dev) { return want ? empty({pop, 2}, at::kInt, dev) : empty({0}, at::kInt, dev); }
+
 // DeleteMutation (mode 0) / HoistMutation (mode 1) drawn and applied in one launch (include/evogp_hip.h evogp_hip_structural_mutate)
-std::tuple<Tensor, Tensor, Tensor, Tensor> structural_mutate(int64_t mode, double rate, int64_t max_size, bool inner_is_offset, int64_t skip_rows, int64_t seed,
-                                                             int64_t call, const Tensor &value, const Tensor &type, const Tensor &size, bool want_decisions) {
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop, gp_len) tensor");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop, gp_len, dev);
-    Tensor dec = want_decisions ? at::empty({pop, 2}, value.options().dtype(at::kInt)) : at::empty({0}, value.options().dtype(at::kInt));
-    check_rc(evogp_hip_structural_mutate((int)pop, (int)gp_len, (int)mode, (float)rate, (int)max_size, inner_is_offset ? 1 : 0, (int)skip_rows, seed, call,
-                                         value.data_ptr<float>(), type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), std::get<0>(out).data_ptr<float>(),
-                                         std::get<1>(out).data_ptr<int16_t>(), std::get<2>(out).data_ptr<int16_t>(),
-                                         want_decisions ? dec.data_ptr<int>() : nullptr, current_stream(dev)),
+Tensor4 structural_mutate(int64_t mode, double rate, int64_t max_size, bool inner_is_offset, int64_t skip_rows, int64_t seed, int64_t call,
+                          const Tensor &value, const Tensor &type, const Tensor &size, bool want_decisions) {
+    const Forest f = Forest::infer(value, type, size);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(f.pop, f.gp_len, f.dev);
+    Tensor dec = decisions(want_decisions, f.pop, f.dev);
+    check_rc(evogp_hip_structural_mutate((int)f.pop, (int)f.gp_len, (int)mode, (float)rate, (int)max_size, inner_is_offset ? 1 : 0, (int)skip_rows, seed,
+                                         call, f.value, f.type, f.size, out.value, out.type, out.size, want_decisions ? dec.data_ptr<int>() : nullptr,
+                                         current_stream(f.dev)),
              "structural_mutate");
-    return {std::get<0>(out), std::get<1>(out), std::get<2>(out), dec};
+    return out.with(dec);
 }
 
 // InsertMutation drawn and applied in one launch over fresh trees from tree_generate_masked_hashed(seed, call, mutate_below) (evogp_hip_insert_mutate)
-std::tuple<Tensor, Tensor, Tensor, Tensor> insert_mutate(int64_t mutate_below, int64_t skip_rows, int64_t seed, int64_t call, const Tensor &value,
-                                                         const Tensor &type, const Tensor &size, const Tensor &donor_value, const Tensor &donor_type,
-                                                         const Tensor &donor_size, bool want_decisions) {
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop, gp_len) tensor");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
+Tensor4 insert_mutate(int64_t mutate_below, int64_t skip_rows, int64_t seed, int64_t call, const Tensor &value, const Tensor &type,
+                      const Tensor &size, const Tensor &donor_value, const Tensor &donor_type, const Tensor &donor_size, bool want_decisions) {
+    const Forest f = Forest::infer(value, type, size);
     TORCH_CHECK(mutate_below >= 0 && mutate_below < (1LL << 32), "mutate_below must fit in 32 bits");
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    check_forest(pop, gp_len, donor_value, donor_type, donor_size, dev);
-    c10::DeviceGuard guard(dev);
-    Tensor3 out = empty_forest(pop, gp_len, dev);
-    Tensor dec = want_decisions ? at::empty({pop, 2}, value.options().dtype(at::kInt)) : at::empty({0}, value.options().dtype(at::kInt));
-    check_rc(evogp_hip_insert_mutate((int)pop, (int)gp_len, (unsigned)mutate_below, (int)skip_rows, seed, call, value.data_ptr<float>(),
-                                     type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), donor_value.data_ptr<float>(), donor_type.data_ptr<int16_t>(),
-                                     donor_size.data_ptr<int16_t>(), std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<int16_t>(),
-                                     std::get<2>(out).data_ptr<int16_t>(), want_decisions ? dec.data_ptr<int>() : nullptr, current_stream(dev)),
+    const Forest donors = Forest::donors(f.pop, f.gp_len, donor_value, donor_type, donor_size, f.dev);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(f.pop, f.gp_len, f.dev);
+    Tensor dec = decisions(want_decisions, f.pop, f.dev);
+    check_rc(evogp_hip_insert_mutate((int)f.pop, (int)f.gp_len, (unsigned)mutate_below, (int)skip_rows, seed, call, f.value, f.type, f.size, donors.value,
+                                     donors.type, donors.size, out.value, out.type, out.size, want_decisions ? dec.data_ptr<int>() : nullptr,
+                                     current_stream(f.dev)),
              "insert_mutate");
-    return {std::get<0>(out), std::get<1>(out), std::get<2>(out), dec};
+    return out.with(dec);
 }
 
 // Multi / Single Point / Const mutation drawn and applied in one launch: the new value array (evogp_hip_point_mutate)
 Tensor point_mutate(int64_t mode, double rate, double intensity, bool per_node, bool modify_output, bool fix_roulette, int64_t skip_rows, int64_t input_len,
                     int64_t output_len, int64_t seed, int64_t call, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &roulette_ufuncs,
                     const Tensor &roulette_bfuncs, const Tensor &roulette_tfuncs, const Tensor &const_samples) {
-    TORCH_CHECK(value.dim() == 2, "value must be a (pop, gp_len) tensor");
-    const int64_t pop = value.size(0), gp_len = value.size(1);
-    check_sizes(pop, gp_len);
-    const c10::Device dev = value.device();
-    check_forest(pop, gp_len, value, type, size, dev);
-    check_tensor(roulette_ufuncs, {29}, "roulette_ufuncs", dev, at::kFloat);
-    check_tensor(roulette_bfuncs, {29}, "roulette_bfuncs", dev, at::kFloat);
-    check_tensor(roulette_tfuncs, {29}, "roulette_tfuncs", dev, at::kFloat);
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(roulette_ufuncs, {29}, "roulette_ufuncs", f.dev, at::kFloat);
+    check_tensor(roulette_bfuncs, {29}, "roulette_bfuncs", f.dev, at::kFloat);
+    check_tensor(roulette_tfuncs, {29}, "roulette_tfuncs", f.dev, at::kFloat);
     TORCH_CHECK(const_samples.dim() == 1 && const_samples.size(0) > 0, "const_samples must be a non-empty vector");
-    check_tensor(const_samples, {const_samples.size(0)}, "const_samples", dev, at::kFloat);
-    c10::DeviceGuard guard(dev);
-    Tensor out = at::empty_like(value);
-    check_rc(evogp_hip_point_mutate((int)pop, (int)gp_len, (int)mode, (float)rate, (float)intensity, per_node ? 1 : 0, modify_output ? 1 : 0, fix_roulette ? 1 : 0,
-                                    (int)skip_rows, (int)input_len, (int)output_len, (int)const_samples.size(0), seed, call, value.data_ptr<float>(),
-                                    type.data_ptr<int16_t>(), size.data_ptr<int16_t>(), roulette_ufuncs.data_ptr<float>(), roulette_bfuncs.data_ptr<float>(),
-                                    roulette_tfuncs.data_ptr<float>(), const_samples.data_ptr<float>(), out.data_ptr<float>(), current_stream(dev)),
+    check_tensor(const_samples, {const_samples.size(0)}, "const_samples", f.dev, at::kFloat);
+    c10::DeviceGuard guard(f.dev);
+    Tensor out = empty({f.pop, f.gp_len}, at::kFloat, f.dev);
+    check_rc(evogp_hip_point_mutate((int)f.pop, (int)f.gp_len, (int)mode, (float)rate, (float)intensity, per_node ? 1 : 0, modify_output ? 1 : 0,
+                                    fix_roulette ? 1 : 0, (int)skip_rows, (int)input_len, (int)output_len, (int)const_samples.size(0), seed, call, f.value,
+                                    f.type, f.size, roulette_ufuncs.data_ptr<float>(), roulette_bfuncs.data_ptr<float>(), roulette_tfuncs.data_ptr<float>(),
+                                    const_samples.data_ptr<float>(), out.data_ptr<float>(), current_stream(f.dev)),
              "point_mutate");
     return out;
 }
