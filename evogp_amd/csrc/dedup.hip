@@ -19,10 +19,8 @@
 // equal rows carry equal hashes.  Without a collision the first comparison decides; a run of r colliding distinct rows costs O(r^2)
 // comparisons of up to n words each.
 #include "evogp_defs.hpp"
+#include "group_sort.hpp"
 #include "launch.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace evogp {
 
@@ -102,24 +100,22 @@ __global__ __launch_bounds__(kDedupWaves * 64) void tree_classes_kernel(const fl
     if (lane == 0) class_id[t] = (int)rep;
 }
 
-struct DedupLayout { size_t keys_a, keys_b, vals_a, vals_b, head_pos, seg, temp, temp_bytes, total; };
+struct DedupWorkspace {
+    unsigned long long *keys_a, *keys_b;
+    unsigned *vals_a, *vals_b, *head_pos, *seg;
+    void *temp;
+    size_t temp_bytes;
+};
 
-static hipError_t dedup_layout(unsigned pop, DedupLayout *L) {
-    size_t t_sort = 0, t_incl = 0;
-    rocprim::double_buffer<unsigned long long> kb(nullptr, nullptr);
-    rocprim::double_buffer<unsigned> vb(nullptr, nullptr);
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, kb, vb, pop, 0, 64, (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::inclusive_scan(nullptr, t_incl, (const unsigned *)nullptr, (unsigned *)nullptr, (size_t)pop, rocprim::maximum<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    L->temp_bytes = t_sort > t_incl ? t_sort : t_incl;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255u) & ~(size_t)255u; return o; };
-    L->keys_a = take((size_t)pop * 8); L->keys_b = take((size_t)pop * 8);
-    L->vals_a = take((size_t)pop * 4); L->vals_b = take((size_t)pop * 4);
-    L->head_pos = take((size_t)pop * 4); L->seg = take((size_t)pop * 4);
-    L->temp = take(L->temp_bytes);
-    L->total = off;
+static hipError_t dedup_workspace(unsigned pop, Arena &a, DedupWorkspace *w) {
+    hipError_t e;
+    w->temp_bytes = 0;
+    if ((e = sort_buffers_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_max_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    w->keys_a = a.take<unsigned long long>(pop); w->keys_b = a.take<unsigned long long>(pop);
+    w->vals_a = a.take<unsigned>(pop); w->vals_b = a.take<unsigned>(pop);
+    w->head_pos = a.take<unsigned>(pop); w->seg = a.take<unsigned>(pop);
+    w->temp = a.take_bytes(w->temp_bytes);
     return hipSuccess;
 }
 
@@ -139,10 +135,11 @@ extern "C" int evogp_hip_tree_hash(unsigned pop, unsigned gp_len, const float *v
 extern "C" int evogp_hip_tree_classes_workspace_bytes(unsigned pop, unsigned long long *bytes) {
     if (pop == 0 || pop > 0x7FFFFFFFu) return EVOGP_E_BADARG;
     if (!bytes) return EVOGP_E_NULLPTR;
-    DedupLayout L;
-    const hipError_t e = dedup_layout(pop, &L);
+    Arena a{nullptr};
+    DedupWorkspace w;
+    const hipError_t e = dedup_workspace(pop, a, &w);
     if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    *bytes = (unsigned long long)a.off;
     return EVOGP_OK;
 }
 
@@ -151,28 +148,22 @@ extern "C" int evogp_hip_tree_classes(unsigned pop, unsigned gp_len, const float
     if (pop == 0 || pop > 0x7FFFFFFFu || gp_len == 0 || gp_len > (unsigned)kMaxStack) return EVOGP_E_BADARG;
     if (!value || !type || !size || !hash_in || !class_id_out || !workspace) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    DedupLayout L;
-    hipError_t e = dedup_layout(pop, &L);
+    Arena a{(char *)workspace};
+    DedupWorkspace w;
+    hipError_t e = dedup_workspace(pop, a, &w);
     if (e != hipSuccess) return (int)e;
-    char *ws = (char *)workspace;
-    unsigned long long *keys_a = (unsigned long long *)(ws + L.keys_a), *keys_b = (unsigned long long *)(ws + L.keys_b);
-    unsigned *vals_a = (unsigned *)(ws + L.vals_a), *vals_b = (unsigned *)(ws + L.vals_b);
-    unsigned *head_pos = (unsigned *)(ws + L.head_pos), *seg = (unsigned *)(ws + L.seg);
-    void *temp = ws + L.temp;
     const dim3 grid((pop + 255u) / 256u), block(256);
 
-    hipLaunchKernelGGL(dedup_pairs_kernel, grid, block, 0, stream, hash_in, pop, keys_a, vals_a);
+    hipLaunchKernelGGL(dedup_pairs_kernel, grid, block, 0, stream, hash_in, pop, w.keys_a, w.vals_a);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    rocprim::double_buffer<unsigned long long> kb(keys_a, keys_b);
-    rocprim::double_buffer<unsigned> vb(vals_a, vals_b);
-    size_t tb = L.temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, kb, vb, pop, 0, 64, stream)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(dedup_heads_kernel, grid, block, 0, stream, kb.current(), pop, head_pos);
+    bool in_b;
+    if ((e = sort_buffers(w.temp, w.temp_bytes, w.keys_a, w.keys_b, w.vals_a, w.vals_b, pop, &in_b, stream)) != hipSuccess) return (int)e;
+    const unsigned long long *key = in_b ? w.keys_b : w.keys_a;
+    const unsigned *members = in_b ? w.vals_b : w.vals_a;
+    hipLaunchKernelGGL(dedup_heads_kernel, grid, block, 0, stream, key, pop, w.head_pos);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    tb = L.temp_bytes;
-    if ((e = rocprim::inclusive_scan(temp, tb, (const unsigned *)head_pos, seg, (size_t)pop, rocprim::maximum<unsigned>(), stream)) != hipSuccess)
-        return (int)e;
+    if ((e = scan_max(w.temp, w.temp_bytes, w.head_pos, w.seg, pop, stream)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(tree_classes_kernel, dim3((pop + kDedupWaves - 1u) / kDedupWaves), dim3(kDedupWaves * 64), 0, stream, value, type, size,
-                       (const unsigned *)vb.current(), (const unsigned *)seg, pop, gp_len, class_id_out);
+                       members, (const unsigned *)w.seg, pop, gp_len, class_id_out);
     return (int)hipGetLastError();
 }

@@ -83,6 +83,18 @@ __host__ __device__ inline unsigned counter_word(unsigned long long base, unsign
 
 __device__ inline float bits2f(uint32_t u) { return __uint_as_float(u); }
 __device__ inline uint32_t f2bits(float f) { return __float_as_uint(f); }
+// neither an infinity nor a NaN
+__device__ inline bool finite_f(float x) { return (f2bits(x) & 0x7F800000u) != 0x7F800000u; }
+
+// ---- errors as sort keys (lexicase.hip, nsga2.hip) ------------------------------------------------------------------------------------
+// key(x): NaN -> +inf, -0 -> +0
+__device__ inline float error_key(float x) { return x != x ? __builtin_inff() : (x == 0.0f ? 0.0f : x); }
+// order-preserving unsigned image of a key (keys are never NaN), and its inverse
+__device__ inline unsigned float_ord(float k) {
+    const unsigned u = __float_as_uint(k);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float float_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 
 // broadcast a wave-uniform value into an SGPR so the compiler keeps control flow scalar
 __device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -90,6 +90,19 @@ private:
 extern StreamWorkspaces g_tape_workspaces;   // the global tapes of the tape kernels (sr_forward.hpp plan_tape_launch)
 extern StreamWorkspaces g_case_workspaces;   // the predictions of the per-case errors (lexicase.hip)
 
+// The buffers of a caller-provided workspace, handed out front to back in 256-byte granules.  base == nullptr is a size query:
+// every take returns nullptr and `off` ends up as the bytes the same sequence of takes needs.
+struct Arena {
+    char *base;
+    size_t off = 0;
+    void *take_bytes(size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255u) & ~(size_t)255u;
+        return base ? base + o : nullptr;
+    }
+    template <class T> T *take(size_t count) { return (T *)take_bytes(count * sizeof(T)); }
+};
+
 inline bool grad_workspaces_held() { return g_tape_workspaces.held(); }
 inline void release_grad_workspaces(int dev) { g_tape_workspaces.release(dev); }
 inline bool case_workspaces_held() { return g_case_workspaces.held(); }

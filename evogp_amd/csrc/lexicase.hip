@@ -17,10 +17,8 @@
 //   5. pick      winners[k] = member (word_k mod S) of the pool listed class by class, S = the members of the pool's classes
 // A hash collision merges two classes (probability about pop^2 / 2^65).
 #include "evogp_defs.hpp"
+#include "group_sort.hpp"
 #include "launch.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace evogp {
 
@@ -64,14 +62,6 @@ constexpr unsigned kLexCap = 2048;                    // classes a wave keeps in
 constexpr unsigned kLexWavesPerBlock = 4;
 constexpr unsigned kLexMaxWaves = 4096;               // 16 per CU of a 256-CU device
 
-// key(x): NaN -> +inf, -0 -> +0
-__device__ inline float lex_key(float x) { return x != x ? __builtin_inff() : (x == 0.0f ? 0.0f : x); }
-// order-preserving unsigned image of a key (keys are never NaN)
-__device__ inline unsigned lex_ord(float k) {
-    const unsigned u = __float_as_uint(k);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float lex_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 // epsilon of a case: NaN and negative entries count as 0
 __device__ inline float lex_eps(float e) { return e > 0.0f ? e : 0.0f; }
 
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(256) void lex_hash_kernel(const float *E, unsigned 
     if (i >= pop) return;
     unsigned long long h = 0x243F6A8885A308D3ull;
     for (unsigned c = 0; c < n; ++c) {
-        const unsigned bits = __float_as_uint(lex_key(E[(size_t)c * pop + i]));
+        const unsigned bits = __float_as_uint(error_key(E[(size_t)c * pop + i]));
         h = mix64((h ^ bits) + 0x9E3779B97F4A7C15ull);
     }
     hash[i] = h;
@@ -160,14 +150,14 @@ __global__ __launch_bounds__(1024) void lex_prep_kernel(LexPrep q) {
     const unsigned c = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const float *Ec = q.E + (size_t)c * q.pop;
     unsigned lo = ~0u;
-    for (unsigned i = tid; i < q.pop; i += 1024u) lo = min(lo, lex_ord(lex_key(Ec[i])));
+    for (unsigned i = tid; i < q.pop; i += 1024u) lo = min(lo, float_ord(error_key(Ec[i])));
     lo = wave_min_u(lo);
     if (lane == 0) s_w[w] = lo;
     __syncthreads();
     lo = s_w[0];
     for (int k = 1; k < 16; ++k) lo = min(lo, s_w[k]);
     __syncthreads();
-    const float m = lex_unord(lo), thr = m + lex_eps(q.eps[c]);
+    const float m = float_unord(lo), thr = m + lex_eps(q.eps[c]);
     const unsigned C = *q.nclass;
     unsigned *dst = q.fp + (size_t)c * q.pop;
     unsigned out = 0;
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(1024) void lex_prep_kernel(LexPrep q) {
         const unsigned cl = base + tid;
         bool keep = false;
         if (cl < C) {
-            const float k = lex_key(Ec[q.rep[cl]]);
+            const float k = error_key(Ec[q.rep[cl]]);
             keep = k <= thr || k == m;
         }
         const unsigned long long bal = __ballot(keep);
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
             unsigned lo = ~0u, hi = 0u;
             if (inlist) {
                 for (unsigned i = lane; i < cnt; i += 64u) {
-                    const unsigned o = lex_ord(lex_key(Ec[p.rep[list[i]]]));
+                    const unsigned o = float_ord(error_key(Ec[p.rep[list[i]]]));
                     lo = min(lo, o);
                     hi = max(hi, o);
                 }
@@ -253,7 +243,7 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
                     while (b) {
                         const unsigned q = (unsigned)__builtin_ctz(b);
                         b &= b - 1u;
-                        const unsigned o = lex_ord(lex_key(Ec[p.rep[fpl[wd * 32u + q]]]));
+                        const unsigned o = float_ord(error_key(Ec[p.rep[fpl[wd * 32u + q]]]));
                         lo = min(lo, o);
                         hi = max(hi, o);
                     }
@@ -261,7 +251,7 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
             }
             lo = wave_min_u(lo);
             hi = wave_max_u(hi);
-            const float m = lex_unord(lo), M = lex_unord(hi), thr = m + lex_eps(p.eps[c]);
+            const float m = float_unord(lo), M = float_unord(hi), thr = m + lex_eps(p.eps[c]);
             if (M <= thr) continue;   // nobody leaves the pool
             if (inlist) {
                 unsigned out = 0;
@@ -271,7 +261,7 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
                     unsigned cl = 0;
                     if (i < cnt) {
                         cl = list[i];
-                        const float kk = lex_key(Ec[p.rep[cl]]);
+                        const float kk = error_key(Ec[p.rep[cl]]);
                         keep = kk <= thr || kk == m;
                     }
                     const unsigned long long bal = __ballot(keep);
@@ -288,7 +278,7 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
                     while (b) {
                         const unsigned q = (unsigned)__builtin_ctz(b);
                         b &= b - 1u;
-                        const float kk = lex_key(Ec[p.rep[fpl[wd * 32u + q]]]);
+                        const float kk = error_key(Ec[p.rep[fpl[wd * 32u + q]]]);
                         if (!(kk <= thr || kk == m)) nb &= ~(1u << q);
                     }
                     bits[wd] = nb;
@@ -385,12 +375,13 @@ __global__ __launch_bounds__(256) void lex_events_kernel(LexEvents p) {
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------
-struct LexLayout {
-    size_t keys_a, keys_b, vals_a, vals_b, flag_t, cls_t, head_pos, seg, rep, start, count, nclass, p1, fp, bits, temp, temp_bytes, total;
+struct LexWorkspace {
+    unsigned long long *keys_a, *keys_b;
+    unsigned *vals_a, *vals_b, *flag_t, *cls_t, *head_pos, *seg, *rep, *start, *count, *nclass, *p1, *fp, *bits;
+    void *temp;
+    size_t temp_bytes;
     unsigned waves, words;
 };
-
-static size_t lex_align(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 static unsigned lex_waves(unsigned n, unsigned n_events) {
     unsigned long long w = n_events < kLexMaxWaves ? n_events : kLexMaxWaves;
@@ -399,32 +390,23 @@ static unsigned lex_waves(unsigned n, unsigned n_events) {
     return (unsigned)((w + kLexWavesPerBlock - 1) / kLexWavesPerBlock * kLexWavesPerBlock);
 }
 
-static hipError_t lex_layout(unsigned n, unsigned pop, unsigned n_events, LexLayout *L) {
-    size_t t_sort = 0, t_excl = 0, t_incl = 0;
-    rocprim::double_buffer<unsigned long long> kb(nullptr, nullptr);
-    rocprim::double_buffer<unsigned> vb(nullptr, nullptr);
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, kb, vb, pop, 0, 64, (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(nullptr, t_excl, (const unsigned *)nullptr, (unsigned *)nullptr, 0u, (size_t)pop, rocprim::plus<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::inclusive_scan(nullptr, t_incl, (const unsigned *)nullptr, (unsigned *)nullptr, (size_t)pop, rocprim::maximum<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    L->temp_bytes = t_sort > t_excl ? t_sort : t_excl;
-    if (t_incl > L->temp_bytes) L->temp_bytes = t_incl;
-    L->waves = lex_waves(n, n_events);
-    L->words = (pop + 31u) / 32u;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += lex_align(bytes); return o; };
-    L->keys_a = take((size_t)pop * 8); L->keys_b = take((size_t)pop * 8);
-    L->vals_a = take((size_t)pop * 4); L->vals_b = take((size_t)pop * 4);
-    L->flag_t = take((size_t)pop * 4); L->cls_t = take((size_t)pop * 4);
-    L->head_pos = take((size_t)pop * 4); L->seg = take((size_t)pop * 4);
-    L->rep = take((size_t)pop * 4); L->start = take((size_t)pop * 4); L->count = take((size_t)pop * 4);
-    L->nclass = take(4); L->p1 = take((size_t)n * 4);
-    L->fp = take((size_t)n * pop * 4);
-    L->bits = take((size_t)L->waves * L->words * 4);
-    L->temp = take(L->temp_bytes);
-    L->total = off;
+static hipError_t lex_workspace(unsigned n, unsigned pop, unsigned n_events, Arena &a, LexWorkspace *w) {
+    hipError_t e;
+    w->temp_bytes = 0;
+    if ((e = sort_buffers_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_plus_excl_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_max_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    w->waves = lex_waves(n, n_events);
+    w->words = (pop + 31u) / 32u;
+    w->keys_a = a.take<unsigned long long>(pop); w->keys_b = a.take<unsigned long long>(pop);
+    w->vals_a = a.take<unsigned>(pop); w->vals_b = a.take<unsigned>(pop);
+    w->flag_t = a.take<unsigned>(pop); w->cls_t = a.take<unsigned>(pop);
+    w->head_pos = a.take<unsigned>(pop); w->seg = a.take<unsigned>(pop);
+    w->rep = a.take<unsigned>(pop); w->start = a.take<unsigned>(pop); w->count = a.take<unsigned>(pop);
+    w->nclass = a.take<unsigned>(1); w->p1 = a.take<unsigned>(n);
+    w->fp = a.take<unsigned>((size_t)n * pop);
+    w->bits = a.take<unsigned>((size_t)w->waves * w->words);
+    w->temp = a.take_bytes(w->temp_bytes);
     return hipSuccess;
 }
 
@@ -458,10 +440,11 @@ extern "C" int evogp_hip_sr_case_errors(unsigned pop_size, unsigned data_points,
 extern "C" int evogp_hip_lexicase_workspace_bytes(unsigned n_cases, unsigned pop, unsigned n_events, unsigned long long *bytes) {
     if (n_cases == 0 || pop == 0 || pop > 0x7FFFFFFFu) return EVOGP_E_BADARG;
     if (!bytes) return EVOGP_E_NULLPTR;
-    LexLayout L;
-    const hipError_t e = lex_layout(n_cases, pop, n_events, &L);
+    Arena a{nullptr};
+    LexWorkspace w;
+    const hipError_t e = lex_workspace(n_cases, pop, n_events, a, &w);
     if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    *bytes = (unsigned long long)a.off;
     return EVOGP_OK;
 }
 
@@ -471,42 +454,30 @@ extern "C" int evogp_hip_lexicase_select(unsigned n_cases, unsigned pop, const f
     if (n_events == 0) return EVOGP_OK;
     if (!errors || !eps || !winners || !workspace) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    LexLayout L;
-    hipError_t e = lex_layout(n_cases, pop, n_events, &L);
+    Arena a{(char *)workspace};
+    LexWorkspace w;
+    hipError_t e = lex_workspace(n_cases, pop, n_events, a, &w);
     if (e != hipSuccess) return (int)e;
-    char *ws = (char *)workspace;
-    auto at = [&](size_t off) { return (void *)(ws + off); };
-    unsigned long long *keys_a = (unsigned long long *)at(L.keys_a), *keys_b = (unsigned long long *)at(L.keys_b);
-    unsigned *vals_a = (unsigned *)at(L.vals_a), *vals_b = (unsigned *)at(L.vals_b);
-    unsigned *flag_t = (unsigned *)at(L.flag_t), *cls_t = (unsigned *)at(L.cls_t), *head_pos = (unsigned *)at(L.head_pos), *seg = (unsigned *)at(L.seg);
-    unsigned *rep = (unsigned *)at(L.rep), *start = (unsigned *)at(L.start), *count = (unsigned *)at(L.count), *nclass = (unsigned *)at(L.nclass);
-    unsigned *p1 = (unsigned *)at(L.p1), *fp = (unsigned *)at(L.fp), *bits = (unsigned *)at(L.bits);
-    void *temp = at(L.temp);
     const dim3 grid((pop + 255u) / 256u), block(256);
 
     // 1-2. hash, sort, classes
-    hipLaunchKernelGGL(lex_hash_kernel, grid, block, 0, stream, errors, n_cases, pop, keys_a, vals_a);
+    hipLaunchKernelGGL(lex_hash_kernel, grid, block, 0, stream, errors, n_cases, pop, w.keys_a, w.vals_a);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    rocprim::double_buffer<unsigned long long> kb(keys_a, keys_b);
-    rocprim::double_buffer<unsigned> vb(vals_a, vals_b);
-    size_t tb = L.temp_bytes;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, kb, vb, pop, 0, 64, stream)) != hipSuccess) return (int)e;
-    const unsigned long long *key = kb.current();
-    const unsigned *members = vb.current();
-    hipLaunchKernelGGL(lex_heads_kernel, grid, block, 0, stream, key, members, pop, flag_t, head_pos);
+    bool in_b;
+    if ((e = sort_buffers(w.temp, w.temp_bytes, w.keys_a, w.keys_b, w.vals_a, w.vals_b, pop, &in_b, stream)) != hipSuccess) return (int)e;
+    const unsigned long long *key = in_b ? w.keys_b : w.keys_a;
+    const unsigned *members = in_b ? w.vals_b : w.vals_a;
+    hipLaunchKernelGGL(lex_heads_kernel, grid, block, 0, stream, key, members, pop, w.flag_t, w.head_pos);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    tb = L.temp_bytes;
-    if ((e = rocprim::exclusive_scan(temp, tb, (const unsigned *)flag_t, cls_t, 0u, (size_t)pop, rocprim::plus<unsigned>(), stream)) != hipSuccess)
-        return (int)e;
-    tb = L.temp_bytes;
-    if ((e = rocprim::inclusive_scan(temp, tb, (const unsigned *)head_pos, seg, (size_t)pop, rocprim::maximum<unsigned>(), stream)) != hipSuccess)
-        return (int)e;
-    hipLaunchKernelGGL(lex_classes_kernel, grid, block, 0, stream, key, members, seg, flag_t, cls_t, pop, rep, start, count, nclass);
+    if ((e = scan_plus_excl(w.temp, w.temp_bytes, w.flag_t, w.cls_t, pop, stream)) != hipSuccess) return (int)e;
+    if ((e = scan_max(w.temp, w.temp_bytes, w.head_pos, w.seg, pop, stream)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(lex_classes_kernel, grid, block, 0, stream, key, members, (const unsigned *)w.seg, (const unsigned *)w.flag_t,
+                       (const unsigned *)w.cls_t, pop, w.rep, w.start, w.count, w.nclass);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if (g_lex_stop == 1) return EVOGP_OK;
 
     // 3. the first pool of every case
-    LexPrep q{errors, eps, rep, nclass, fp, p1, g_lex_counters, n_cases, pop};
+    LexPrep q{errors, eps, w.rep, w.nclass, w.fp, w.p1, g_lex_counters, n_cases, pop};
     hipLaunchKernelGGL(lex_prep_kernel, dim3(n_cases), dim3(1024), 0, stream, q);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if (g_lex_stop == 2) return EVOGP_OK;
@@ -515,9 +486,9 @@ extern "C" int evogp_hip_lexicase_select(unsigned n_cases, unsigned pop, const f
     unsigned b = 0;
     while (b < 32u && (1ull << b) < n_cases) ++b;
     if (b & 1u) ++b;
-    LexEvents ev{errors, eps, members, rep, start, count, fp, p1, bits, winners, g_lex_counters, counter_base(seed, generation), n_cases, pop,
-                 n_events, b / 2u, L.words};
-    hipLaunchKernelGGL(lex_events_kernel, dim3(L.waves / kLexWavesPerBlock), dim3(64 * kLexWavesPerBlock), 0, stream, ev);
+    LexEvents ev{errors, eps, members, w.rep, w.start, w.count, w.fp, w.p1, w.bits, winners, g_lex_counters, counter_base(seed, generation),
+                 n_cases, pop, n_events, b / 2u, w.words};
+    hipLaunchKernelGGL(lex_events_kernel, dim3(w.waves / kLexWavesPerBlock), dim3(64 * kLexWavesPerBlock), 0, stream, ev);
     return (int)hipGetLastError();
 }
 

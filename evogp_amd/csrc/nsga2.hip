@@ -18,10 +18,8 @@
 //                of every front recorded by the trees at the front's boundaries; Deb's distance in plain float32 operations
 //   5. order     a sort by (front, ~image(crowding)); all four sorts are stable and start from ascending tree index
 #include "evogp_defs.hpp"
+#include "group_sort.hpp"
 #include "launch.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace evogp {
 
@@ -30,14 +28,6 @@ constexpr unsigned kNsgaUnrankedKey = 0xFFFFFFFFu;    // (the image of a finite 
 constexpr unsigned kNsgaUnrankedCx = 0x10000u;
 constexpr int kNsgaUnrankedFront = 0x7FFFFFFF;
 constexpr unsigned kNsgaChainThreads = 1024, kNsgaChainItems = 4;
-
-// key(e): NaN -> +inf, -0 -> +0
-__device__ inline float nsga_key(float x) { return x != x ? __builtin_inff() : (x == 0.0f ? 0.0f : x); }
-// order-preserving unsigned image of a key (keys are never NaN)
-__device__ inline unsigned nsga_ord(float k) {
-    const unsigned u = __float_as_uint(k);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // inclusive max-scan over the 64 lanes (the DPP sequence of wave_scan_incl)
 __device__ inline int wave_scan_max_incl(int v) {
@@ -56,10 +46,10 @@ __global__ __launch_bounds__(256) void nsga_keys_kernel(const float *err, const 
                                                         unsigned *tree) {
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     if (t >= pop) return;
-    const float k = nsga_key(err[t]);
+    const float k = error_key(err[t]);
     const int c = cx[t];
     const bool ranked = k > -__builtin_inff() && k < __builtin_inff() && c >= 0 && (unsigned)c <= cx_bound;
-    key[t] = ranked ? nsga_ord(k) : kNsgaUnrankedKey;
+    key[t] = ranked ? float_ord(k) : kNsgaUnrankedKey;
     tree[t] = t;
 }
 
@@ -224,7 +214,7 @@ __global__ __launch_bounds__(256) void nsga_points_kernel(const unsigned long lo
     if (fr == (unsigned)kNsgaUnrankedFront) return;
     const unsigned p = pid[w] + head[w] - 1u;      // (pid: the heads in front of w)
     if (head[w]) {
-        pt_key[p] = nsga_key(err[tree[w]]);
+        pt_key[p] = error_key(err[tree[w]]);
         pt_cx[p] = (unsigned)(k & 0x1FFFFull);
     }
     if (w == 0u || (unsigned)(key[w - 1u] >> 17) != fr) first_of[fr] = p;
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(256) void nsga_crowding_kernel(const unsigned long 
         }
     }
     crowding[t] = d;
-    okey[t] = ((unsigned long long)fr << 32) | (unsigned long long)(~nsga_ord(d));   // front ascending, then crowding descending
+    okey[t] = ((unsigned long long)fr << 32) | (unsigned long long)(~float_ord(d));   // front ascending, then crowding descending
     otree[t] = t;
 }
 
@@ -266,43 +256,36 @@ __global__ __launch_bounds__(256) void nsga_select_kernel(const int *order, unsi
 }
 
 // ---- workspace -------------------------------------------------------------------------------------------------------------------
-struct NsgaLayout {
-    size_t k32_a, k32_b, v_a, v_b, k64_a, k64_b, head, scan, f2, t2, gid, bend, fen, front_u, pt_key, pt_cx, first_of, last_of, temp, temp_bytes,
-        total;
+struct NsgaWorkspace {
+    unsigned *k32_a, *k32_b, *v_a, *v_b;
+    unsigned long long *k64_a, *k64_b;
+    unsigned *head, *scan, *f2, *t2, *gid, *bend;
+    int *fen, *front_u;
+    float *pt_key;
+    unsigned *pt_cx, *first_of, *last_of;
+    void *temp;
+    size_t temp_bytes;
 };
 
 static int g_nsga_stop = 0;
 
-static size_t nsga_align(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-static hipError_t nsga_layout(unsigned pop, NsgaLayout *L) {
-    size_t t32 = 0, t64 = 0, t_excl = 0, t_plus = 0, t_max = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, t32, (const unsigned *)nullptr, (unsigned *)nullptr, (const unsigned *)nullptr, (unsigned *)nullptr,
-                                             (size_t)pop, 0u, 32u, (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::radix_sort_pairs(nullptr, t64, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const unsigned *)nullptr,
-                                  (unsigned *)nullptr, (size_t)pop, 0u, 64u, (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(nullptr, t_excl, (const unsigned *)nullptr, (unsigned *)nullptr, 0u, (size_t)pop, rocprim::plus<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::inclusive_scan(nullptr, t_plus, (const unsigned *)nullptr, (unsigned *)nullptr, (size_t)pop, rocprim::plus<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    e = rocprim::inclusive_scan(nullptr, t_max, (const unsigned *)nullptr, (unsigned *)nullptr, (size_t)pop, rocprim::maximum<unsigned>(), (hipStream_t)0);
-    if (e != hipSuccess) return e;
-    size_t tb = t32;
-    for (size_t v : {t64, t_excl, t_plus, t_max}) tb = v > tb ? v : tb;
-    L->temp_bytes = tb;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += nsga_align(bytes); return o; };
-    const size_t n4 = (size_t)pop * 4, n8 = (size_t)pop * 8;
-    L->k32_a = take(n4); L->k32_b = take(n4); L->v_a = take(n4); L->v_b = take(n4);
-    L->k64_a = take(n8); L->k64_b = take(n8);
-    L->head = take(n4); L->scan = take(n4); L->f2 = take(n4); L->t2 = take(n4); L->gid = take(n4);
-    L->bend = take((size_t)(kNsgaUnrankedCx + 1u) * 4);
-    L->fen = take(n4 + 4);
-    L->front_u = take(n4); L->pt_key = take(n4); L->pt_cx = take(n4); L->first_of = take(n4); L->last_of = take(n4);
-    L->temp = take(L->temp_bytes);
-    L->total = off;
+static hipError_t nsga_workspace(unsigned pop, Arena &a, NsgaWorkspace *w) {
+    hipError_t e;
+    w->temp_bytes = 0;
+    if ((e = sort_pairs_u32_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = sort_pairs_u64_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_plus_excl_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_plus_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    if ((e = scan_max_temp(pop, &w->temp_bytes)) != hipSuccess) return e;
+    w->k32_a = a.take<unsigned>(pop); w->k32_b = a.take<unsigned>(pop); w->v_a = a.take<unsigned>(pop); w->v_b = a.take<unsigned>(pop);
+    w->k64_a = a.take<unsigned long long>(pop); w->k64_b = a.take<unsigned long long>(pop);
+    w->head = a.take<unsigned>(pop); w->scan = a.take<unsigned>(pop); w->f2 = a.take<unsigned>(pop); w->t2 = a.take<unsigned>(pop);
+    w->gid = a.take<unsigned>(pop);
+    w->bend = a.take<unsigned>(kNsgaUnrankedCx + 1u);
+    w->fen = a.take<int>((size_t)pop + 1u);
+    w->front_u = a.take<int>(pop); w->pt_key = a.take<float>(pop); w->pt_cx = a.take<unsigned>(pop);
+    w->first_of = a.take<unsigned>(pop); w->last_of = a.take<unsigned>(pop);
+    w->temp = a.take_bytes(w->temp_bytes);
     return hipSuccess;
 }
 
@@ -313,10 +296,11 @@ using namespace evogp;
 extern "C" int evogp_hip_pareto_rank_workspace_bytes(unsigned pop, unsigned long long *bytes) {
     if (pop == 0 || pop >= 0x7FFFFFFFu) return EVOGP_E_BADARG;
     if (!bytes) return EVOGP_E_NULLPTR;
-    NsgaLayout L;
-    const hipError_t e = nsga_layout(pop, &L);
+    Arena a{nullptr};
+    NsgaWorkspace w;
+    const hipError_t e = nsga_workspace(pop, a, &w);
     if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    *bytes = (unsigned long long)a.off;
     return EVOGP_OK;
 }
 
@@ -325,71 +309,56 @@ extern "C" int evogp_hip_pareto_rank(unsigned pop, unsigned cx_bound, const floa
     if (pop == 0 || pop >= 0x7FFFFFFFu || cx_bound > 65535u) return EVOGP_E_BADARG;
     if (!err || !cx || !front || !crowding || !order || !workspace) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    NsgaLayout L;
-    hipError_t e = nsga_layout(pop, &L);
+    Arena a{(char *)workspace};
+    NsgaWorkspace w;
+    hipError_t e = nsga_workspace(pop, a, &w);
     if (e != hipSuccess) return (int)e;
-    char *ws = (char *)workspace;
-    auto u32 = [&](size_t off) { return (unsigned *)(ws + off); };
-    unsigned *k32_a = u32(L.k32_a), *k32_b = u32(L.k32_b), *v_a = u32(L.v_a), *v_b = u32(L.v_b);
-    unsigned long long *k64_a = (unsigned long long *)(ws + L.k64_a), *k64_b = (unsigned long long *)(ws + L.k64_b);
-    unsigned *head = u32(L.head), *scan = u32(L.scan), *f2 = u32(L.f2), *t2 = u32(L.t2), *gid = u32(L.gid), *bend = u32(L.bend);
-    int *fen = (int *)(ws + L.fen), *front_u = (int *)(ws + L.front_u);
-    float *pt_key = (float *)(ws + L.pt_key);
-    unsigned *pt_cx = u32(L.pt_cx), *first_of = u32(L.first_of), *last_of = u32(L.last_of);
-    void *temp = ws + L.temp;
     const dim3 grid((pop + 255u) / 256u), block(256);
-    size_t tb;
-#define NSGA_LAUNCHED() if ((e = hipGetLastError()) != hipSuccess) return (int)e
-#define NSGA_PRIM(call) tb = L.temp_bytes; if ((e = (call)) != hipSuccess) return (int)e
 
     // 1. the key order: k32_b / v_b = keys and trees in key order, scan = the first position of every tree's run of equal keys
-    hipLaunchKernelGGL(nsga_keys_kernel, grid, block, 0, stream, err, cx, pop, cx_bound, k32_a, v_a);
-    NSGA_LAUNCHED();
-    NSGA_PRIM(rocprim::radix_sort_pairs(temp, tb, (const unsigned *)k32_a, k32_b, (const unsigned *)v_a, v_b, (size_t)pop, 0u, 32u, stream));
-    const unsigned *tree1 = v_b;
-    hipLaunchKernelGGL(nsga_runs_kernel, grid, block, 0, stream, (const unsigned *)k32_b, tree1, cx, pop, head, k32_a, v_a);
-    NSGA_LAUNCHED();
-    NSGA_PRIM(rocprim::inclusive_scan(temp, tb, (const unsigned *)head, scan, (size_t)pop, rocprim::maximum<unsigned>(), stream));
+    hipLaunchKernelGGL(nsga_keys_kernel, grid, block, 0, stream, err, cx, pop, cx_bound, w.k32_a, w.v_a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = sort_pairs(w.temp, w.temp_bytes, w.k32_a, w.k32_b, w.v_a, w.v_b, pop, 0u, 32u, stream)) != hipSuccess) return (int)e;
+    const unsigned *tree1 = w.v_b;
+    hipLaunchKernelGGL(nsga_runs_kernel, grid, block, 0, stream, (const unsigned *)w.k32_b, tree1, cx, pop, w.head, w.k32_a, w.v_a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = scan_max(w.temp, w.temp_bytes, w.head, w.scan, pop, stream)) != hipSuccess) return (int)e;
     if (g_nsga_stop == 1) return EVOGP_OK;
 
     // 2. the bucket order: k32_b = cx, t2 / f2 = the tree and the first position of its key, gid = the group numbers
-    unsigned *s2 = u32(L.front_u);   // (free until the chain kernel)
-    NSGA_PRIM(rocprim::radix_sort_pairs(temp, tb, (const unsigned *)k32_a, k32_b, (const unsigned *)v_a, s2, (size_t)pop, 0u, 17u, stream));
-    hipLaunchKernelGGL(nsga_groups_kernel, grid, block, 0, stream, (const unsigned *)k32_b, (const unsigned *)s2, (const unsigned *)scan, tree1, pop, f2,
-                       t2, head, bend, front);
-    NSGA_LAUNCHED();
-    NSGA_PRIM(rocprim::inclusive_scan(temp, tb, (const unsigned *)head, gid, (size_t)pop, rocprim::plus<unsigned>(), stream));
+    unsigned *s2 = (unsigned *)w.front_u;   // (free until the chain kernel)
+    if ((e = sort_pairs(w.temp, w.temp_bytes, w.k32_a, w.k32_b, w.v_a, s2, pop, 0u, 17u, stream)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(nsga_groups_kernel, grid, block, 0, stream, (const unsigned *)w.k32_b, (const unsigned *)s2, (const unsigned *)w.scan, tree1,
+                       pop, w.f2, w.t2, w.head, w.bend, front);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = scan_plus(w.temp, w.temp_bytes, w.head, w.gid, pop, stream)) != hipSuccess) return (int)e;
     if (g_nsga_stop == 2) return EVOGP_OK;
 
     // 3. the fronts
-    if ((e = hipMemsetAsync(fen, 0xFF, ((size_t)pop + 1u) * 4, stream)) != hipSuccess) return (int)e;
-    NsgaChain ch{k32_b, f2, t2, gid, bend, fen, front_u, front, pop};
+    if ((e = hipMemsetAsync(w.fen, 0xFF, ((size_t)pop + 1u) * 4, stream)) != hipSuccess) return (int)e;
+    NsgaChain ch{w.k32_b, w.f2, w.t2, w.gid, w.bend, w.fen, w.front_u, front, pop};
     hipLaunchKernelGGL(nsga_chain_kernel, dim3(1), dim3(kNsgaChainThreads), 0, stream, ch);
-    NSGA_LAUNCHED();
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if (g_nsga_stop == 3) return EVOGP_OK;
 
     // 4. the points of every front and their crowding distance
-    hipLaunchKernelGGL(nsga_front_keys_kernel, grid, block, 0, stream, (const int *)front, cx, pop, k64_a, v_a);
-    NSGA_LAUNCHED();
-    NSGA_PRIM(rocprim::radix_sort_pairs(temp, tb, (const unsigned long long *)k64_a, k64_b, (const unsigned *)v_a, v_b, (size_t)pop, 0u, 48u, stream));
-    hipLaunchKernelGGL(nsga_point_heads_kernel, grid, block, 0, stream, (const unsigned long long *)k64_b, pop, head);
-    NSGA_LAUNCHED();
-    NSGA_PRIM(rocprim::exclusive_scan(temp, tb, (const unsigned *)head, scan, 0u, (size_t)pop, rocprim::plus<unsigned>(), stream));
-    hipLaunchKernelGGL(nsga_points_kernel, grid, block, 0, stream, (const unsigned long long *)k64_b, (const unsigned *)v_b, (const unsigned *)head,
-                       (const unsigned *)scan, err, pop, pt_key, pt_cx, first_of, last_of);
-    NSGA_LAUNCHED();
-    hipLaunchKernelGGL(nsga_crowding_kernel, grid, block, 0, stream, (const unsigned long long *)k64_b, (const unsigned *)v_b, (const unsigned *)head,
-                       (const unsigned *)scan, (const float *)pt_key, (const unsigned *)pt_cx, (const unsigned *)first_of, (const unsigned *)last_of, pop,
-                       crowding, k64_a, v_a);
-    NSGA_LAUNCHED();
+    hipLaunchKernelGGL(nsga_front_keys_kernel, grid, block, 0, stream, (const int *)front, cx, pop, w.k64_a, w.v_a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = sort_pairs(w.temp, w.temp_bytes, w.k64_a, w.k64_b, w.v_a, w.v_b, pop, 0u, 48u, stream)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(nsga_point_heads_kernel, grid, block, 0, stream, (const unsigned long long *)w.k64_b, pop, w.head);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if ((e = scan_plus_excl(w.temp, w.temp_bytes, w.head, w.scan, pop, stream)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(nsga_points_kernel, grid, block, 0, stream, (const unsigned long long *)w.k64_b, (const unsigned *)w.v_b,
+                       (const unsigned *)w.head, (const unsigned *)w.scan, err, pop, w.pt_key, w.pt_cx, w.first_of, w.last_of);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(nsga_crowding_kernel, grid, block, 0, stream, (const unsigned long long *)w.k64_b, (const unsigned *)w.v_b,
+                       (const unsigned *)w.head, (const unsigned *)w.scan, (const float *)w.pt_key, (const unsigned *)w.pt_cx,
+                       (const unsigned *)w.first_of, (const unsigned *)w.last_of, pop, crowding, w.k64_a, w.v_a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if (g_nsga_stop == 4) return EVOGP_OK;
 
     // 5. the order
-    NSGA_PRIM(rocprim::radix_sort_pairs(temp, tb, (const unsigned long long *)k64_a, k64_b, (const unsigned *)v_a, (unsigned *)order, (size_t)pop, 0u, 63u,
-                                        stream));
-#undef NSGA_LAUNCHED
-#undef NSGA_PRIM
-    return EVOGP_OK;
+    return (int)sort_pairs(w.temp, w.temp_bytes, w.k64_a, w.k64_b, w.v_a, (unsigned *)order, pop, 0u, 63u, stream);
 }
 
 extern "C" int evogp_hip_nsga2_select(unsigned pop, const int *order, unsigned pool, unsigned n_tournaments, unsigned t_size, long long seed,

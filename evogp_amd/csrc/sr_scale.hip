@@ -76,8 +76,6 @@ __device__ inline float wave_max_f(float v) {
     return v;
 }
 
-__device__ inline bool scale_finite(float x) { return (f2bits(x) & 0x7F800000u) != 0x7F800000u; }
-
 // ---- 1. label statistics: one workgroup, thread i takes rows i, i + 256, ...; lanes by the butterfly, waves in order ----------------
 __global__ __launch_bounds__(kStatsThreads) void label_stats_kernel(const float *y, int D, double *stats) {
     __shared__ double s_w[kStatsThreads / kWave];
@@ -126,7 +124,7 @@ __device__ inline void scale_store(const ScaleParams &p, int t, const Moments &m
             loss = loss > 0.0 ? loss : 0.0;
         }
         lf = (float)loss; af = (float)a; bf = (float)b;
-        if (!scale_finite(af) || !scale_finite(bf)) lf = af = bf = nan;
+        if (!finite_f(af) || !finite_f(bf)) lf = af = bf = nan;
     }
     p.loss[t] = lf;
     p.coef[2 * (size_t)t] = af;
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(kScaleWaves * 64, VL <= 16 ? (LEAN ? kScaleLeanWave
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const float pr = st.tos[k];
-                    bad |= !scale_finite(pr);
+                    bad |= !finite_f(pr);
                     mn = fminf(mn, pr);
                     mx = fmaxf(mx, pr);
                     const double pd = valid[k] ? (double)pr : 0.0;
@@ -300,7 +298,7 @@ __global__ __launch_bounds__(64) void sr_scale_general_kernel(ScaleParams p, int
                 const bool valid = d < p.D;
                 const size_t dc = valid ? (size_t)d : (size_t)p.D - 1;
                 const float pr = run_general<false>(tt, tv, len, p.X + dc * p.var_len, p.var_len, 1, outs, stk);
-                bad |= !scale_finite(pr);
+                bad |= !finite_f(pr);
                 mn = fminf(mn, pr);
                 mx = fmaxf(mx, pr);
                 const double pd = valid ? (double)pr : 0.0;
@@ -359,7 +357,7 @@ __global__ __launch_bounds__(kWrapWaves * 64) void wrap_linear_kernel(WrapParams
     len = len < 0 ? 0 : (len > L ? L : len);
     const int cls = uni(classify_tree(q.type + row, q.value + row, len, false, 1, 1, kMaxStack));
     const float a = q.coef[2 * (size_t)t], b = q.coef[2 * (size_t)t + 1];
-    const bool wrap = cls == TREE_OK && scale_finite(a) && scale_finite(b) && len + 4 <= Lo;
+    const bool wrap = cls == TREE_OK && finite_f(a) && finite_f(b) && len + 4 <= Lo;
     for (int j = lane; j < Lo; j += kWave) {
         float v = 0.0f;
         int ty = 0, s = 0;

@@ -177,8 +177,6 @@ __device__ inline int wave_scan_max_incl(int v) {
     return v;
 }
 
-__device__ inline bool finite_f(float x) { return (f2bits(x) & 0x7F800000u) != 0x7F800000u; }
-
 // subtree size of node j as the row states it, kept inside the live prefix (a well-formed tree's sizes already are)
 __device__ inline int node_span(const int16_t *size, size_t row, int j, int len) {
     const int s = (int)size[row + j];
