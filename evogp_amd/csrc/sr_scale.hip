@@ -5,7 +5,7 @@
 //     Sp = sum p_d      Spp = sum p_d^2      Spv = sum p_d * ((double)y_d - ybar)
 // plus min p_d, max p_d and "some p_d is not finite" in float32: the closed form needs nothing else, so the (pop, D) predictions are
 // never stored.  Four launches on the caller's stream, nothing synchronises with the host:
-//   1. label_stats_kernel   ONE workgroup: ybar and Syy = sum ((double)y_d - ybar)^2 in a fixed order, two doubles that stay on the device
+//   1. label_stats_kernel   (sr_moments.hpp) ONE workgroup: ybar and Syy = sum ((double)y_d - ybar)^2 in a fixed order, two doubles that stay on the device
 //   2. sr_scale_kernel      sr_fast_kernel's decomposition (sr_fitness.hip) on the register interpreter (interp.hpp run_chunk), launched
 //                           twice as sr_fitness.hip's launch_pair: the LEAN build over every tree, then the FULL build (all 29 functions)
 //                           over the trees the LEAN one marked as using a transcendental function or pow.  The rows are cut into tiles of 64 x K, wave w of a workgroup takes tiles w, w + W, ...; the
@@ -22,6 +22,7 @@
 // evogp_hip_wrap_linear: one wave per tree, coalesced copies in the style of replace_row.hpp build_row.
 #include "interp.hpp"
 #include "launch.hpp"
+#include "sr_moments.hpp"
 #include "sr_params.hpp"
 
 namespace evogp {
@@ -29,7 +30,6 @@ namespace evogp {
 constexpr int kScaleK = 4;        // rows per lane
 constexpr int kScaleDepth = 16;   // register stack entries; deeper trees go to the scratch stack
 constexpr int kScaleWaves = 4;    // waves per workgroup: a workgroup's row tile is 64 * kScaleK * kScaleWaves = 1024 rows
-constexpr int kStatsThreads = 256;
 // Resident waves per SIMD the LEAN build is held to.  Unbounded it takes 186 VGPRs (two waves); at the 168 of three waves it spills 10
 // registers (36 B of scratch per lane) and is still the faster one: the interpreter waits on latency, not on registers.
 constexpr int kScaleLeanWaves = 3;
@@ -47,59 +47,6 @@ struct ScaleParams {
                            // kSentinelHeavy, [3] batch counter of the FULL pass
     int pop, D, gp_len, var_len, batch, ntiles;
 };
-
-template <int CTRL, int ROW_MASK>
-__device__ inline double dpp_move_d(double v) {
-    const int lo = dpp_move<CTRL, ROW_MASK>(0, __double2loint(v));
-    const int hi = dpp_move<CTRL, ROW_MASK>(0, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-// wave_sum (evogp_defs.hpp) on a double: the same fixed association
-__device__ inline double wave_sum_d(double x) {
-    double v = x;
-    v += dpp_move_d<kDppRowShr | 1, 0xf>(v);
-    v += dpp_move_d<kDppRowShr | 2, 0xf>(v);
-    v += dpp_move_d<kDppRowShr | 4, 0xf>(v);
-    v += dpp_move_d<kDppRowShr | 8, 0xf>(v);
-    v += dpp_move_d<kDppBcast15, 0xa>(v);
-    v += dpp_move_d<kDppBcast31, 0xc>(v);
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-
-__device__ inline float wave_min_f(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline float wave_max_f(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// ---- 1. label statistics: one workgroup, thread i takes rows i, i + 256, ...; lanes by the butterfly, waves in order ----------------
-__global__ __launch_bounds__(kStatsThreads) void label_stats_kernel(const float *y, int D, double *stats) {
-    __shared__ double s_w[kStatsThreads / kWave];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    auto block_sum = [&](double x) {
-        const double s = wave_sum_d(x);
-        __syncthreads();   // (the previous round's reads are over)
-        if (lane == 0) s_w[w] = s;
-        __syncthreads();
-        double total = 0.0;
-        for (int k = 0; k < kStatsThreads / kWave; ++k) total += s_w[k];
-        return total;
-    };
-    double s = 0.0;
-    for (int i = threadIdx.x; i < D; i += kStatsThreads) s += (double)y[i];
-    const double ybar = block_sum(s) / (double)D;
-    double q = 0.0;
-    for (int i = threadIdx.x; i < D; i += kStatsThreads) {
-        const double v = (double)y[i] - ybar;
-        q += v * v;
-    }
-    const double syy = block_sum(q);
-    if (threadIdx.x == 0) { stats[0] = ybar; stats[1] = syy; }
-}
 
 // ---- the closed form (one thread per tree) ---------------------------------------------------------------------------------------------
 struct Moments {

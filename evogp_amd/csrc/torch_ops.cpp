@@ -113,7 +113,8 @@ struct ForestOut {
 
 // The prologue of the ops over a dataset: the forest, the sizes, variables (data_points, var_len) and labels (data_points, out_len);
 // `op` is the op's name for its error texts.
-enum class OutLen { Any, One, UpTo16 };   // what the op allows: any positive out_len, single-output trees only, the output registers
+enum class OutLen { Any, One, UpTo16, Genes };   // what the op allows: any positive out_len, single-output trees only, the output registers,
+                                                 // 1..EVOGP_GENES_MAX features of ONE label column
 
 struct Dataset : Forest {
     const float *X, *y;
@@ -127,10 +128,12 @@ Dataset check_dataset(const char *op, OutLen rule, int64_t pop_size, int64_t dat
     case OutLen::Any: TORCH_CHECK(out_len > 0, "out_len must be larger than 0, but got ", out_len); break;
     case OutLen::One: TORCH_CHECK(out_len == 1, op, ": single-output trees only (out_len must be 1), but got ", out_len); break;
     case OutLen::UpTo16: TORCH_CHECK(out_len > 0 && out_len <= 16, "out_len must be in range (0, 16], but got ", out_len); break;
+    case OutLen::Genes: TORCH_CHECK(out_len > 0 && out_len <= EVOGP_GENES_MAX, "out_len must be in range (0, ", EVOGP_GENES_MAX, "], but got ", out_len); break;
     }
     TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
     check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
-    check_tensor(labels, {data_points, out_len}, "labels", f.dev, at::kFloat);
+    if (rule == OutLen::Genes && labels.dim() == 1) check_tensor(labels, {data_points}, "labels", f.dev, at::kFloat);   // (D,) or (D, 1)
+    else check_tensor(labels, {data_points, rule == OutLen::Genes ? 1 : out_len}, "labels", f.dev, at::kFloat);
     return {f, variables.data_ptr<float>(), labels.data_ptr<float>()};
 }
 
@@ -340,6 +343,33 @@ std::tuple<Tensor, Tensor> tree_SR_linear_scaling(int64_t pop_size, int64_t data
                                          d.type, d.size, d.X, d.y, loss.data_ptr<float>(), coef.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_linear_scaling");
     return {loss, coef};
+}
+
+// multi-gene fitness (evogp_hip_sr_gene_fitness): loss (pop,), coef (pop, 1 + out_len) = intercept, weights; with_moments: also the
+// (pop, out_len (out_len + 5) / 2) float64 moments the solve read
+Tensor3 gene_fitness_impl(const char *op, bool with_moments, int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                          const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
+    const Dataset d = check_dataset(op, OutLen::Genes, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), coef = empty({pop_size, 1 + out_len}, at::kFloat, d.dev), moments;
+    if (with_moments) moments = empty({pop_size, out_len * (out_len + 5) / 2}, at::kDouble, d.dev);
+    check_rc(evogp_hip_sr_gene_fitness((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
+                                       d.type, d.size, d.X, d.y, loss.data_ptr<float>(), coef.data_ptr<float>(),
+                                       with_moments ? moments.data_ptr<double>() : nullptr, current_stream(d.dev)),
+             op);
+    return {loss, coef, moments};
+}
+
+std::tuple<Tensor, Tensor> tree_SR_gene_fitness(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                const Tensor &labels) {
+    const Tensor3 r = gene_fitness_impl("tree_SR_gene_fitness", false, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    return {std::get<0>(r), std::get<1>(r)};
+}
+
+Tensor3 tree_SR_gene_moments(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                             const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels) {
+    return gene_fitness_impl("tree_SR_gene_moments", true, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
 }
 
 // every row T as ADD(MUL(T, slope), intercept) in rows of out_gp_len words (evogp_hip_wrap_linear); applied (pop,) uint8
@@ -978,6 +1008,10 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_classes(Tensor value, Tensor node_type, Tensor subtree_size, Tensor hash) -> Tensor");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
+    m.def("tree_SR_gene_fitness(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
+    m.def("tree_SR_gene_moments(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef, Tensor moments)");
     m.def("tree_wrap_linear(int out_gp_len, Tensor value, Tensor node_type, Tensor subtree_size, Tensor coef)"
           " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
     m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
@@ -1018,6 +1052,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_hash", &tree_hash);
     m.impl("tree_classes", &tree_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
+    m.impl("tree_SR_gene_fitness", &tree_SR_gene_fitness);
+    m.impl("tree_SR_gene_moments", &tree_SR_gene_moments);
     m.impl("tree_wrap_linear", &tree_wrap_linear);
     m.impl("tree_intervals", &tree_intervals);
     m.impl("tree_derivative_intervals", &tree_derivative_intervals);

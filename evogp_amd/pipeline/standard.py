@@ -31,6 +31,7 @@ class StandardPipeline(BasePipeline):
         self.valid_fitness_boundry = valid_fitness_boundry
         self.best_tree = None
         self.best_fitness = float("-inf")
+        self.best_coef = None   # a multigene problem: the (1 + G,) coefficients of best_tree's model, on the host
         self.fitness = None
 
     def step(self):
@@ -56,6 +57,10 @@ class StandardPipeline(BasePipeline):
             if getattr(self.problem, "linear_scaling", False):
                 # the reported tree is the model whose error the fitness states: the tree with its slope and intercept written in
                 self.best_tree = self.problem.scaled(forest[best:best + 1], dedup=False)[0]   # (one tree: nothing to deduplicate)
+            elif getattr(self.problem, "multigene", False):
+                # the weights cannot be written into the tree (an OUT node hands its operand on, not its result): they go next to it
+                self.best_tree = forest[best]
+                self.best_coef = self.problem.gene_model(forest[best:best + 1], dedup=False)[1][0].cpu()
             else:
                 self.best_tree = forest[best]
         return host

@@ -21,7 +21,7 @@ class SymbolicRegression(BaseProblem):
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
                  dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
-                 input_margin: float = 0.0, monotonic=None):
+                 input_margin: float = 0.0, monotonic=None, multigene: bool = False):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -42,7 +42,13 @@ class SymbolicRegression(BaseProblem):
         arithmetic over its partial derivatives proves it nondecreasing (+1) or nonincreasing (-1) in the variable, or its derivative
         within [dmin, dmax], on the whole box (``Forest.monotone_mask``); the others get NaN / -inf as above.  With
         ``linear_scaling`` the constraint is on the tree's shape and the fitted slope may flip it, so under a +-1 constraint
-        ``scaled_fitness`` gives a NaN loss to a tree whose slope is negative; a (dmin, dmax) pair bounds the unscaled tree."""
+        ``scaled_fitness`` gives a NaN loss to a tree whose slope is negative; a (dmin, dmax) pair bounds the unscaled tree.
+        ``multigene`` (GPTIPS; Arnaldo et al. 2014; MSE, labels of shape ``(D, 1)``): the ``G = output_len`` outputs of a tree, 1 .. 8 of
+        them, are features and the tree is scored by the error of ``b0 + sum_j w_j g_j(x)`` with the least-squares coefficients
+        (``Forest.SR_gene_fitness``, which honours ``dedup``); ``gene_model(forest)`` returns the losses and the coefficients, and
+        StandardPipeline keeps those of its best tree in ``best_coef``.  It contains linear scaling, and the single-output passes do not
+        apply to it: ``ValueError`` together with ``linear_scaling``, ``const_opt_steps`` > 0, ``simplify_every`` > 0,
+        ``interval_check`` or ``monotonic``, and from ``evaluate`` / ``scores`` with ``use_MSE=False``."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -86,6 +92,15 @@ class SymbolicRegression(BaseProblem):
                 raise ValueError("monotonic must constrain at least one variable")
             if not self.interval_check:
                 self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
+        self.multigene = bool(multigene)
+        if self.multigene:
+            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+                raise ValueError(f"multigene fits one label column, (D, 1), but the labels have shape {tuple(self.labels.shape)}")
+            for name, on in (("linear_scaling", self.linear_scaling), ("const_opt_steps > 0", self.const_opt_steps > 0),
+                             ("simplify_every > 0", self.simplify_every > 0), ("interval_check", self.interval_check),
+                             ("monotonic", self.monotonic is not None)):
+                if on:
+                    raise ValueError(f"multigene cannot be combined with {name}: that pass works on single-output trees")
         self._sign_constrained = self.monotonic is not None and any(isinstance(c, int) for c in self.monotonic.values())
         self._box_check = self.interval_check or self.monotonic is not None
 
@@ -176,7 +191,59 @@ class SymbolicRegression(BaseProblem):
 
     def _check_scaling(self, use_MSE: bool):
         if not use_MSE:
-            raise ValueError("linear_scaling minimises the mean squared error: use_MSE must be True")
+            raise ValueError(f"{'multigene' if self.multigene else 'linear_scaling'} minimises the mean squared error: use_MSE must be True")
+
+    def gene_model(self, forest: Forest, dedup: Optional[bool] = None):
+        """``(loss (pop,), coef (pop, 1 + G))`` of every tree as a multi-gene model on this problem's data: ``Forest.SR_gene_fitness``,
+        or under ``execute_mode="torch"`` the same definition from ``batch_forward``'s outputs in float64 torch (which materialises
+        them).  ``dedup``: None takes the problem's setting"""
+        if self.execute_mode != "torch":
+            return forest.SR_gene_fitness(self.datapoints, self.labels, dedup=self.dedup if dedup is None else bool(dedup))
+        g32 = forest.batch_forward(self.datapoints)   # (pop, D, G) float32
+        pop, D, G = g32.shape
+        g = g32.to(torch.float64)
+        y = self.labels.to(g.device)[:, 0].to(torch.float64)
+        ybar = y.mean()
+        v = y - ybar
+        syy_D = (v * v).sum() / D
+        m = g.mean(1)
+        gc = g - m[:, None, :]
+        C = torch.einsum("pdi,pdj->pij", gc, gc) / D
+        c = torch.einsum("pdi,d->pi", gc, v) / D
+        var = torch.diagonal(C, dim1=1, dim2=2)
+        flat = (g32.min(1).values == g32.max(1).values) | (var <= 0) | (D == 1)
+        # the LDL^T of the definition, gene by gene over the whole population: a dropped gene keeps an identity row
+        Lm = torch.zeros_like(C)
+        dd = torch.ones_like(m)
+        kept = torch.zeros_like(flat)
+        for j in range(G):
+            dj = var[:, j].clone()
+            for k in range(j):
+                a = C[:, k, j].clone()
+                for q in range(k):
+                    a = a - Lm[:, j, q] * Lm[:, k, q] * dd[:, q]
+                l = torch.where(kept[:, k], a / dd[:, k], torch.zeros_like(a))
+                Lm[:, j, k] = l
+                dj = dj - l * l * dd[:, k]
+            kept[:, j] = ~flat[:, j] & (dj > 2.0 ** -30 * var[:, j])
+            dd[:, j] = torch.where(kept[:, j], dj, torch.ones_like(dj))
+            Lm[:, j, :j] = torch.where(kept[:, j, None], Lm[:, j, :j], torch.zeros_like(Lm[:, j, :j]))
+        w = torch.where(kept, c, torch.zeros_like(c))
+        for j in range(G):
+            for k in range(j):
+                w[:, j] = w[:, j] - Lm[:, j, k] * w[:, k]
+        w = w / dd
+        for j in range(G - 1, -1, -1):
+            for i in range(j + 1, G):
+                w[:, j] = w[:, j] - Lm[:, i, j] * w[:, i]
+        w = torch.where(kept, w, torch.zeros_like(w))
+        b0 = ybar - (w * m).sum(1)
+        loss = torch.clamp(syy_D - (w * c).sum(1), min=0.0)
+        coef = torch.cat([b0[:, None], w], dim=1).to(torch.float32)
+        bad = ~torch.isfinite(g32).all(2).all(1) | ~torch.isfinite(coef).all(1)
+        nan = float("nan")
+        return (torch.where(bad, torch.full_like(loss, nan), loss).to(torch.float32),
+                torch.where(bad[:, None], torch.full_like(coef, nan), coef))
 
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         fitness = self._evaluate(forest, use_MSE)
@@ -189,6 +256,9 @@ class SymbolicRegression(BaseProblem):
         return self._masked(forest, fitness, float("-inf")) if self._box_check else fitness
 
     def _evaluate(self, forest: Forest, use_MSE: bool) -> Tensor:
+        if self.multigene:
+            self._check_scaling(use_MSE)
+            return -self.gene_model(forest)[0]
         if self.linear_scaling:
             self._check_scaling(use_MSE)
             return -self.scaled_fitness(forest)[0]
@@ -200,7 +270,11 @@ class SymbolicRegression(BaseProblem):
         return -forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
 
     def _scores(self, forest: Forest, use_MSE: bool) -> Tensor:
-        if self.linear_scaling:
+        if self.multigene:
+            self._check_scaling(use_MSE)
+            if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
+                return torch.ops.evogp_hip.fitness_scores(self.gene_model(forest)[0], True)
+        elif self.linear_scaling:
             self._check_scaling(use_MSE)
             if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
                 return torch.ops.evogp_hip.fitness_scores(self.scaled_fitness(forest)[0], True)

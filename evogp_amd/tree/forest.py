@@ -12,7 +12,8 @@ descent or Levenberg-Marquardt on the constants, no counterpart in the reference
 (the loss of every subtree, and the rewrite into a smaller tree that is no worse) and ``SR_scaled_fitness`` / ``apply_scaling`` (linear
 scaling: the loss under the least-squares slope and intercept, and the tree that carries them) and ``SR_intervals`` / ``safe_mask`` (interval
 arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it) and
-``SR_derivative_intervals`` / ``monotone_mask`` (bounds of every subtree's partial derivatives over the box, and the trees proven monotone).  Every heavy method is one call into
+``SR_derivative_intervals`` / ``monotone_mask`` (bounds of every subtree's partial derivatives over the box, and the trees proven monotone) and
+``SR_gene_fitness`` / ``SR_gene_moments`` / ``gene_predict`` (multi-gene regression: the outputs of a tree as features of a least-squares model).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -37,6 +38,7 @@ from .utils import NType, check_tensor
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
+GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
 
@@ -429,6 +431,60 @@ class Forest:
         mask = self.func_mask
         return (Forest(self.input_len, self.output_len, value, ntype, size, func_mask=(mask | _WRAP_FUNCS) if mask else 0),
                 applied.to(torch.bool))
+
+    # ---- multi-gene fitness ----------------------------------------------------------------------
+    def _gene_data(self, what: str, inputs: Tensor, labels: Tensor):
+        if not 1 <= self.output_len <= GENES_MAX:
+            raise ValueError(f"{what} works on forests of 1 .. {GENES_MAX} outputs, but output_len is {self.output_len}")
+        inputs, labels = check_tensor(inputs, self.batch_node_value.device), check_tensor(labels, self.batch_node_value.device)
+        n = inputs.shape[0]
+        if inputs.shape != (n, self.input_len):
+            raise ValueError(f"inputs shape should be ({n}, {self.input_len}), but got {tuple(inputs.shape)}")
+        if labels.shape not in ((n,), (n, 1)):
+            raise ValueError(f"{what} fits ONE label column: labels shape should be ({n},) or ({n}, 1), but got {tuple(labels.shape)}")
+        return inputs.contiguous().to(torch.float32), labels.contiguous().to(torch.float32)
+
+    def SR_gene_fitness(self, inputs: Tensor, labels: Tensor, dedup: bool = False):
+        """``(loss (pop,), coef (pop, 1 + G))``, float32: multi-gene regression (GPTIPS; Arnaldo et al. 2014).  The ``G = output_len``
+        outputs of a tree are features ``g_1 .. g_G`` and the model is ``coef[0] + sum_j coef[1 + j] * g_j(x)`` with the least-squares
+        coefficients of every tree; ``loss`` is its mean squared error on ONE label column, ``(D,)`` or ``(D, 1)``.  The float64
+        co-moments are taken inside the evaluation kernel in one pass (csrc/sr_genes.hip): the ``(pop, D, G)`` outputs are never
+        stored.  A gene that is constant over the rows, or collinear with the genes in front of it up to float32 rounding (LDL^T
+        pivot below 2^-30 of its variance), gets weight exactly 0; a malformed tree or one with a non-finite gene value gets NaN
+        throughout (include/evogp_hip.h has the full definition).  ``1 <= G <= 8``.  Deterministic, no host synchronisation.
+
+        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
+        inputs, labels = self._gene_data("SR_gene_fitness", inputs, labels)
+        source, class_id = self._first_rows_only() if dedup else (self, None)
+        loss, coef = torch.ops.evogp_hip.tree_SR_gene_fitness(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
+                                                              self.output_len, *source._tensors(), inputs, labels)
+        if dedup:
+            loss, coef = loss[class_id], coef[class_id]
+        return loss, coef
+
+    def SR_gene_moments(self, inputs: Tensor, labels: Tensor):
+        """``(mean (pop, G), cov (pop, G, G), cov_y (pop, G))``, float64: the moments ``SR_gene_fitness`` solves from -- the mean of
+        every gene, the covariance of the genes (the kernel's upper triangle, mirrored) and their covariance with the labels, all
+        with divisor D.  A malformed tree has zeros."""
+        inputs, labels = self._gene_data("SR_gene_moments", inputs, labels)
+        G = self.output_len
+        _, _, m = torch.ops.evogp_hip.tree_SR_gene_moments(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, G,
+                                                           *self._tensors(), inputs, labels)
+        iu = torch.triu_indices(G, G, device=m.device)
+        cov = torch.zeros(self.pop_size, G, G, dtype=m.dtype, device=m.device)
+        cov[:, iu[0], iu[1]] = m[:, G:G + iu.shape[1]]
+        cov[:, iu[1], iu[0]] = m[:, G:G + iu.shape[1]]
+        return m[:, :G], cov, m[:, G + iu.shape[1]:]
+
+    def gene_predict(self, inputs: Tensor, coef: Tensor) -> Tensor:
+        """``(pop, D)`` float32: the multi-gene model ``coef[:, 0] + batch_forward(inputs) @ coef[:, 1:]`` in float32 torch.  This is
+        the path that MATERIALISES the ``(pop, D, G)`` outputs: use it for a handful of trees, not for a population."""
+        coef = check_tensor(coef, self.batch_node_value.device)
+        if coef.shape != (self.pop_size, 1 + self.output_len):
+            raise ValueError(f"coef shape should be ({self.pop_size}, {1 + self.output_len}), but got {tuple(coef.shape)}")
+        coef = coef.to(torch.float32)
+        genes = self.batch_forward(inputs)   # (pop, D, G)
+        return coef[:, :1] + torch.einsum("pdg,pg->pd", genes, coef[:, 1:])
 
     # ---- interval arithmetic --------------------------------------------------------------------
     def _box(self, lower, upper):

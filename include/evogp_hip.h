@@ -531,6 +531,41 @@ int evogp_hip_wrap_linear(unsigned pop_size, unsigned gp_len, unsigned out_gp_le
                           const int16_t *size, const float *coef, float *out_value, int16_t *out_type, int16_t *out_size,
                           unsigned char *applied, evogp_stream_t stream);
 
+/* Multi-gene SR fitness (GPTIPS; Arnaldo et al. 2014 "MRGP"; no counterpart in the reference): linear scaling above generalised from one
+ * column to G.  The G = out_len outputs of a tree are FEATURES g_1 .. g_G, the model is  yhat = b0 + sum_j w_j g_j(x)  with the
+ * least-squares b0, w of every tree, and the loss is its mean squared error (csrc/sr_genes.hip): one pass over the dataset per tree,
+ * G(G+5)/2 sums, no (pop, D, G) matrix.  1 <= G <= EVOGP_GENES_MAX, else EVOGP_E_UNSUPPORTED; labels is (D,).
+ * g_jd is the float32 value evogp_hip_batch_evaluate stores in output j on row d: for G = 1 the tree's value, for G > 1 the
+ * multi-output conventions (the sum of the nodes flagged for output j, 0 when none is, an output index >= G ignored).  ybar,
+ * v_d = (double)y_d - ybar and Syy = sum v_d^2 are those of linear scaling, bit for bit.
+ * Moments, float64:  m_j = mean_d g_j,  C_ij = mean_d (g_i - m_i)(g_j - m_j),  c_j = mean_d (g_j - m_j) v_d;  per gene also the float32
+ * minimum and maximum and "some value is not finite".  They are taken in one pass as SHIFTED sums: every wave that accumulates on
+ * its own subtracts from gene j the value a_j the gene has on the first row the wave sees before it multiplies and adds (a row past D
+ * contributes exactly 0: the shifted value is masked), and the waves' (n, mean, M2, co-moments) are merged in wave order by the pairwise
+ * update of Chan, Golub & LeVeque (1983).  The uncentred Spp/D - (Sp/D)^2 of linear scaling is not good enough here: a gene that is a
+ * constant plus float32 rounding noise has mean(g^2)/var up to 1e16.
+ * Rules, one thread per tree, float64:
+ *   malformed tree, or a gene value that is not finite            loss and every coefficient NaN
+ *   gene j with min_d == max_d (exactly), C_jj <= 0, or D == 1    FLAT: weight exactly 0, no part in the solve
+ *   the other genes, in index order, through an unrolled LDL^T    d_j = C_jj - sum over kept k < j of l_jk^2 d_k;  gene j is KEPT iff
+ *                                                                 d_j > EVOGP_GENES_PIVOT_TOL * C_jj, else its weight is exactly 0 and
+ *                                                                 it is left out of the later columns: it is collinear with the
+ *                                                                 earlier genes up to float32 rounding
+ *   kept set K                                                    C_KK w = c_K;  b0 = ybar - sum w_j m_j;
+ *                                                                 loss = max(0, Syy/D - sum_K w_j c_j);  K empty: b0 = ybar, loss = Syy/D
+ * rounded once to float32; if a rounded coefficient is not finite every output of the tree is NaN.  The tolerance is part of the
+ * definition, not a tuning knob: an untruncated least-squares fit spends weights on rounding noise.
+ * loss (pop,);  coef (pop, 1 + G): the intercept, then the weights;  moments (pop, G(G+5)/2) float64 or NULL: the means, the row-major
+ * upper triangle of C, then c -- the very values the solve read.  A malformed tree has a NaN loss and a zero moments row.
+ * Bit-identical from run to run; a tree's result does not depend on the other rows of the forest or on its position; nothing
+ * synchronises with the host, and the call can be captured into a HIP graph once one eager call on the stream has been made.
+ * Any gp_len <= 1024, var_len and data_points. */
+#define EVOGP_GENES_MAX 8
+#define EVOGP_GENES_PIVOT_TOL 9.313225746154785e-10 /* 2^-30 */
+int evogp_hip_sr_gene_fitness(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                              const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                              const float *labels, float *loss, float *coef, double *moments /* nullable */, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -612,7 +647,7 @@ int evogp_hip_get_sr_division(void);
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
- * then evogp_hip_tree_derivative_intervals were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
