@@ -549,6 +549,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_derivative_inter
     return {vlo, vhi, vflags, dlo, dhi, dflags};
 }
 
+// (units int32 (pop, gp_len, n_dims), flags uint8 (pop, gp_len), violations int32 (pop,)): the unit of every subtree, the variables carrying
+// var_units (var_len, n_dims) and, with check_root, the root held to label_units (n_dims,) (evogp_hip_tree_dimensions)
+std::tuple<Tensor, Tensor, Tensor> tree_dimensions(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &var_units,
+                                                   const Tensor &label_units, bool check_root) {
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(var_units.dim() == 2 && var_units.size(0) > 0 && var_units.size(1) >= 1 && var_units.size(1) <= EVOGP_DIM_MAX_DIMS,
+                "var_units must be a (var_len, n_dims) tensor with var_len > 0 and 1 <= n_dims <= ", EVOGP_DIM_MAX_DIMS, ", but got shape ",
+                var_units.sizes());
+    const int64_t var_len = var_units.size(0), K = var_units.size(1);
+    check_tensor(var_units, {var_len, K}, "var_units", f.dev, at::kInt);
+    check_tensor(label_units, {K}, "label_units", f.dev, at::kInt);
+    c10::DeviceGuard guard(f.dev);
+    Tensor units = empty({f.pop, f.gp_len, K}, at::kInt, f.dev), flags = empty({f.pop, f.gp_len}, at::kByte, f.dev);
+    Tensor violations = empty({f.pop}, at::kInt, f.dev);
+    check_rc(evogp_hip_tree_dimensions((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)var_len, (unsigned)K, f.value, f.type, f.size,
+                                       var_units.data_ptr<int>(), label_units.data_ptr<int>(), check_root ? 1 : 0, units.data_ptr<int>(),
+                                       flags.data_ptr<uint8_t>(), violations.data_ptr<int>(), current_stream(f.dev)),
+             "tree_dimensions");
+    return {units, flags, violations};
+}
+
 // int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
 // workspace comes from torch's caching allocator
 Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
@@ -1016,6 +1037,7 @@ TORCH_LIBRARY(evogp_hip, m) {
           " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
     m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
     m.def("tree_derivative_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper, Tensor wrt) -> (Tensor vlo, Tensor vhi, Tensor vflags, Tensor dlo, Tensor dhi, Tensor dflags)");
+    m.def("tree_dimensions(Tensor value, Tensor node_type, Tensor subtree_size, Tensor var_units, Tensor label_units, bool check_root) -> (Tensor units, Tensor flags, Tensor violations)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -1057,4 +1079,5 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_wrap_linear", &tree_wrap_linear);
     m.impl("tree_intervals", &tree_intervals);
     m.impl("tree_derivative_intervals", &tree_derivative_intervals);
+    m.impl("tree_dimensions", &tree_dimensions);
 }

@@ -49,3 +49,12 @@ def tree_derivative_intervals(value, node_type, subtree_size, lower, upper, wrt)
     derivative in variable ``wrt[k]`` (int32 ``(K,)`` tensor on the forest's device, each entry in [0, var_len)); dflags bit 0 = the
     subtree may be discontinuous in that variable, bit 1 = the row is malformed, bit 2 = the variable occurs in it"""
     return torch.ops.evogp_hip.tree_derivative_intervals(value, node_type, subtree_size, lower, upper, wrt)
+
+
+def tree_dimensions(value, node_type, subtree_size, var_units, label_units, check_root):
+    """``(units, flags, violations)``: ``torch.ops.evogp_hip.tree_dimensions`` (csrc/sr_dims.hip), dimensional analysis of every
+    single-output tree.  ``var_units`` int32 ``(var_len, K)`` and ``label_units`` int32 ``(K,)`` on the forest's device: numerators over
+    25200, ``1 <= K <= 8``; ``check_root``: hold the root to ``label_units``.  ``units`` int32 (pop, gp_len, K): the unit of every subtree
+    (of a consistent tree: under one consistent assignment of units to its constants); ``flags`` uint8 (pop, gp_len): 1 = free, 2 =
+    violation, 4 = the row is malformed, 8 = root mismatch; ``violations`` int32 (pop,): 0 = consistent, -1 = malformed"""
+    return torch.ops.evogp_hip.tree_dimensions(value, node_type, subtree_size, var_units, label_units, check_root)

@@ -4,12 +4,14 @@ strings; every kernel mode maps onto the one fused HIP kernel, ``"torch"`` evalu
 ``Forest.batch_forward`` (the non-replicating batch op) and reduces in torch."""
 from __future__ import annotations
 
+from fractions import Fraction
 from typing import Callable, Optional
 
 import torch
 from torch import Tensor
 
 from ..tree import Forest, default_device
+from ..tree.utils import DIM_DEN, check_units
 from .base import BaseProblem
 
 _MODES = ["torch", "hybrid parallel", "data parallel", "tree parallel", "auto"]
@@ -21,7 +23,8 @@ class SymbolicRegression(BaseProblem):
                  lower_bounds=-1, upper_bounds=1, execute_mode: str = "auto", const_opt_steps: int = 0,
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
                  dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
-                 input_margin: float = 0.0, monotonic=None, multigene: bool = False):
+                 input_margin: float = 0.0, monotonic=None, multigene: bool = False, input_units=None, label_units=None,
+                 dimension_penalty: Optional[float] = None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -48,7 +51,15 @@ class SymbolicRegression(BaseProblem):
         (``Forest.SR_gene_fitness``, which honours ``dedup``); ``gene_model(forest)`` returns the losses and the coefficients, and
         StandardPipeline keeps those of its best tree in ``best_coef``.  It contains linear scaling, and the single-output passes do not
         apply to it: ``ValueError`` together with ``linear_scaling``, ``const_opt_steps`` > 0, ``simplify_every`` > 0,
-        ``interval_check`` or ``monotonic``, and from ``evaluate`` / ``scores`` with ``use_MSE=False``."""
+        ``interval_check`` or ``monotonic``, and from ``evaluate`` / ``scores`` with ``use_MSE=False``.
+        ``input_units`` (dimensional analysis; labels of shape ``(D, 1)``): ``(num_inputs, K)`` exponents of K base dimensions for every
+        input, ``label_units`` ``(K,)`` those of the target or None to leave the root free (``Forest.SR_dimensions``; a constant may carry
+        any unit).  ``dimension_penalty=None``: a tree that cannot be made dimensionally consistent gets NaN from ``evaluate`` and -inf
+        from ``scores`` (on top of the box masks where those are on), the others keep their values bit for bit; ``dimension_penalty=p``
+        with ``p >= 0``: its fitness falls by ``p`` times the number of violating nodes instead (a malformed row still gets NaN / -inf).
+        With ``linear_scaling`` the root is not held to ``label_units``: slope and intercept are free constants that carry whatever
+        unit converts the tree's; violations inside the tree still count.  ``ValueError`` with ``multigene``, and for ``label_units`` or
+        ``dimension_penalty`` without ``input_units``."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -101,8 +112,26 @@ class SymbolicRegression(BaseProblem):
                              ("monotonic", self.monotonic is not None)):
                 if on:
                     raise ValueError(f"multigene cannot be combined with {name}: that pass works on single-output trees")
+        self.input_units, self.label_units, self.dimension_penalty = None, None, None
+        if input_units is None:
+            if label_units is not None or dimension_penalty is not None:
+                raise ValueError("label_units and dimension_penalty need input_units")
+        else:
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with input_units: dimensional analysis works on single-output trees")
+            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+                raise ValueError(f"input_units works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+            if dimension_penalty is not None:
+                if isinstance(dimension_penalty, bool) or not float(dimension_penalty) >= 0.0:
+                    raise ValueError(f"dimension_penalty should be None or a float >= 0, but got {dimension_penalty!r}")
+                self.dimension_penalty = float(dimension_penalty)
+            # checked here, on the host, so that a wrong shape or exponent fails at construction; kept as exact Fractions
+            var, label, has_label = check_units(input_units, label_units, self.datapoints.shape[1])
+            self.input_units = [[Fraction(n, DIM_DEN) for n in row] for row in var]
+            self.label_units = [Fraction(n, DIM_DEN) for n in label] if has_label else None
         self._sign_constrained = self.monotonic is not None and any(isinstance(c, int) for c in self.monotonic.values())
         self._box_check = self.interval_check or self.monotonic is not None
+        self._constrained = self._box_check or self.input_units is not None
 
     def _input_box(self, input_bounds, margin: float):
         """the box of admissible inputs as two float32 ``(num_inputs,)`` tensors"""
@@ -131,9 +160,31 @@ class SymbolicRegression(BaseProblem):
             raise ValueError("this problem has no monotonic constraints")
         return forest.monotone_mask(self.input_lower, self.input_upper, self.monotonic)
 
+    def dimensions(self, forest: Forest):
+        """``(units, flags, violations)``: ``Forest.SR_dimensions`` under this problem's ``input_units`` and ``label_units`` (the
+        root is left free under ``linear_scaling``)"""
+        if self.input_units is None:
+            raise ValueError("this problem has no input_units")
+        return forest.SR_dimensions(self.input_units, None if self.linear_scaling else self.label_units)
+
+    def dimension_mask(self, forest: Forest) -> Tensor:
+        """(pop,) bool: the tree is dimensionally consistent under this problem's units (``dimensions``: ``violations == 0``)"""
+        return self.dimensions(forest)[2] == 0
+
     def _masked(self, forest: Forest, fitness: Tensor, fill: float) -> Tensor:
-        mask = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
-        return torch.where(mask.to(fitness.device), fitness, torch.full_like(fitness, fill))
+        mask = None
+        if self._box_check:
+            mask = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
+            mask = mask.to(fitness.device)
+        if self.input_units is not None:
+            viol = self.dimensions(forest)[2].to(fitness.device)
+            if self.dimension_penalty is None:
+                ok = viol == 0
+            else:   # (a malformed row, -1, is treated as in the hard case)
+                ok = viol >= 0
+                fitness = torch.where(viol > 0, fitness - self.dimension_penalty * viol.to(fitness.dtype), fitness)
+            mask = ok if mask is None else mask & ok
+        return torch.where(mask, fitness, torch.full_like(fitness, fill))
 
     @staticmethod
     def generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds):
@@ -247,13 +298,13 @@ class SymbolicRegression(BaseProblem):
 
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         fitness = self._evaluate(forest, use_MSE)
-        return self._masked(forest, fitness, float("nan")) if self._box_check else fitness
+        return self._masked(forest, fitness, float("nan")) if self._constrained else fitness
 
     def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
         on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
         fitness = self._scores(forest, use_MSE)
-        return self._masked(forest, fitness, float("-inf")) if self._box_check else fitness
+        return self._masked(forest, fitness, float("-inf")) if self._constrained else fitness
 
     def _evaluate(self, forest: Forest, use_MSE: bool) -> Tensor:
         if self.multigene:

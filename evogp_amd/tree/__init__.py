@@ -4,7 +4,7 @@ from .descriptor import GenerateDescriptor
 from .tree import Tree
 from .forest import Forest
 from .combined import CombinedForest, CombinedTree
-from .utils import MAX_STACK, randint, NType, set_default_device, default_device
+from .utils import MAX_STACK, randint, NType, set_default_device, default_device, str_unit, unit_numerators
 
 __all__ = ["GenerateDescriptor", "Tree", "Forest", "CombinedForest", "CombinedTree", "MAX_STACK", "randint", "NType", "set_default_device",
-           "default_device"]
+           "default_device", "str_unit", "unit_numerators"]

@@ -13,7 +13,9 @@ descent or Levenberg-Marquardt on the constants, no counterpart in the reference
 scaling: the loss under the least-squares slope and intercept, and the tree that carries them) and ``SR_intervals`` / ``safe_mask`` (interval
 arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it) and
 ``SR_derivative_intervals`` / ``monotone_mask`` (bounds of every subtree's partial derivatives over the box, and the trees proven monotone) and
-``SR_gene_fitness`` / ``SR_gene_moments`` / ``gene_predict`` (multi-gene regression: the outputs of a tree as features of a least-squares model).  Every heavy method is one call into
+``SR_gene_fitness`` / ``SR_gene_moments`` / ``gene_predict`` (multi-gene regression: the outputs of a tree as features of a least-squares model) and
+``SR_dimensions`` / ``dimension_mask`` (dimensional analysis: the physical unit of every subtree, and the trees whose constants can be given units
+that make them consistent).  Every heavy method is one call into
 ``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
 reference, all deliberate:
 
@@ -34,7 +36,7 @@ from torch import Tensor
 from . import utils as _utils
 from .descriptor import GenerateDescriptor
 from .tree import Tree
-from .utils import NType, check_tensor
+from .utils import NType, check_tensor, check_units
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
@@ -580,6 +582,29 @@ class Forest:
         for k, (dmin, dmax) in enumerate(want):
             ok = ok & ((dfl[k, :, 0] & 3) == 0) & (dlo[k, :, 0] >= dmin) & (dhi[k, :, 0] <= dmax)
         return ok
+
+    # ---- dimensional analysis --------------------------------------------------------------------
+    def SR_dimensions(self, input_units, label_units=None):
+        """``(units, flags, violations)``: dimensional analysis of every tree (csrc/sr_dims.hip, one lane per tree, no dataset, no host
+        synchronisation beyond the conversion of the units).  ``input_units``: ``(input_len, K)`` exponents of the K base dimensions
+        (1 .. 8) for every input -- ints, floats or ``Fraction``s, each a multiple of 1/25200; ``label_units``: ``(K,)``, or None to leave
+        the root free.  A constant may carry whatever unit makes its tree consistent.  ``violations`` (pop,) int32: 0 iff the constants
+        can be given units under which every operation is consistent and the root has ``label_units`` (always sound; complete but for
+        trees with a ``pow`` whose base is free, such as a product with a constant), otherwise the number of violating nodes, -1 for a malformed row.
+        ``units`` (pop, max_tree_len, K) int32: the unit of every node as numerators over 25200 -- of a consistent tree under one
+        consistent assignment, ``tree.utils.str_unit`` prints a row; ``flags`` (pop, max_tree_len) uint8: 1 = the node is free,
+        2 = violation, 4 = malformed row, 8 = the root's unit is not the label's.  ``ValueError`` for an exponent that is no multiple
+        of 1/25200 or beyond 2^24 / 25200 in magnitude, a wrong shape, or a multi-output forest."""
+        if self.output_len != 1:
+            raise ValueError(f"SR_dimensions works on single-output trees only, but output_len is {self.output_len}")
+        var, label, check_root = check_units(input_units, label_units, self.input_len)   # int numerators over 25200
+        dev = self.batch_node_value.device
+        return torch.ops.evogp_hip.tree_dimensions(*self._tensors(), torch.tensor(var, dtype=torch.int32).to(dev),
+                                                   torch.tensor(label, dtype=torch.int32).to(dev), check_root)
+
+    def dimension_mask(self, input_units, label_units=None) -> Tensor:
+        """(pop,) bool: the tree is dimensionally consistent (``SR_dimensions``: ``violations == 0``)"""
+        return self.SR_dimensions(input_units, label_units)[2] == 0
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

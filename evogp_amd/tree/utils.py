@@ -125,3 +125,68 @@ def decode_func(value, node_type):
         bits = torch.as_tensor(value, dtype=torch.float32).view(torch.int32).item()
         return bits & 0xFFFF, (bits >> 16) & 0xFFFF
     return int(value), -1
+
+
+# ---- physical units (dimensional analysis, csrc/sr_dims.hip) ----
+DIM_DEN = 25200          # EVOGP_DIM_DEN: every exponent is a numerator over 2^4 3^2 5^2 7
+DIM_MAX_NUM = 1 << 24    # EVOGP_DIM_MAX_NUM: a numerator is in range when |n| <= 2^24
+DIM_MAX_DIMS = 8         # EVOGP_DIM_MAX_DIMS
+
+
+def unit_numerators(exponents, what: str = "a unit"):
+    """Exponents (ints, floats or ``Fraction``s, any nesting) -> the same nesting of int numerators over ``DIM_DEN``, exactly;
+    ``ValueError`` for an exponent of another type (a string, a bool), one that is no multiple of 1/25200 or one whose numerator
+    leaves the range."""
+    from fractions import Fraction
+
+    if isinstance(exponents, torch.Tensor):
+        exponents = exponents.tolist()
+    elif hasattr(exponents, "tolist"):
+        exponents = exponents.tolist()
+    if isinstance(exponents, (list, tuple)):
+        return [unit_numerators(e, what) for e in exponents]
+    if isinstance(exponents, bool) or not isinstance(exponents, (int, float, Fraction)):
+        raise ValueError(f"{what} holds {exponents!r}: an exponent is an int, a float or a Fraction")
+    try:
+        n = Fraction(exponents) * DIM_DEN
+    except (ValueError, OverflowError) as e:
+        raise ValueError(f"{what} holds {exponents!r}, which is no finite number") from e
+    if n.denominator != 1 or abs(n.numerator) > DIM_MAX_NUM:
+        raise ValueError(f"{what} holds the exponent {exponents!r}: times {DIM_DEN} it must be an integer of magnitude <= {DIM_MAX_NUM}")
+    return int(n.numerator)
+
+
+def check_units(input_units, label_units, input_len: int):
+    """``(var, label, has_label)``: ``input_units`` as ``input_len`` rows of K numerators and ``label_units`` as K numerators (zeros for
+    None), checked: ``ValueError`` for a wrong shape, K outside 1 .. ``DIM_MAX_DIMS`` or an exponent ``unit_numerators`` refuses"""
+    def flat(row):
+        return isinstance(row, list) and len(row) > 0 and all(isinstance(n, int) for n in row)
+
+    var = unit_numerators(input_units, "input_units")
+    if not (isinstance(var, list) and len(var) == input_len and all(flat(r) and len(r) == len(var[0]) for r in var)):
+        raise ValueError(f"input_units should hold one row of K exponents for each of the {input_len} inputs")
+    K = len(var[0])
+    if K > DIM_MAX_DIMS:
+        raise ValueError(f"a unit has 1 .. {DIM_MAX_DIMS} base dimensions, but input_units has {K}")
+    label = [0] * K if label_units is None else unit_numerators(label_units, "label_units")
+    if not (flat(label) and len(label) == K):
+        raise ValueError(f"label_units should hold {K} exponents, one for each base dimension of input_units")
+    return var, label, label_units is not None
+
+
+def str_unit(unit, names=None) -> str:
+    """One unit row (K numerators over ``DIM_DEN``) as text, e.g. ``m s^-2`` or ``m^1/2``; ``1`` for the dimensionless unit.  ``names``: the
+    K base names (default ``d0, d1, ..``).  The exponents are exact fractions in lowest terms."""
+    from fractions import Fraction
+
+    unit = [int(n) for n in (unit.tolist() if hasattr(unit, "tolist") else unit)]
+    names = [f"d{k}" for k in range(len(unit))] if names is None else list(names)
+    if len(names) != len(unit):
+        raise ValueError(f"{len(unit)} base dimensions, but {len(names)} names")
+    parts = []
+    for name, n in zip(names, unit):
+        if n == 0:
+            continue
+        e = Fraction(n, DIM_DEN)
+        parts.append(name if e == 1 else f"{name}^{e}")
+    return " ".join(parts) if parts else "1"

@@ -468,6 +468,34 @@ int evogp_hip_tree_derivative_intervals(unsigned pop, unsigned gp_len, unsigned 
                                         float *vlo, float *vhi, unsigned char *vflags, float *dlo, float *dhi, unsigned char *dflags,
                                         evogp_stream_t stream);
 
+/* Dimensional analysis over single-output trees (physical units; no counterpart in the reference; csrc/sr_dims.hip).  A unit is n_dims
+ * int32 numerators over the fixed denominator EVOGP_DIM_DEN (2^4 3^2 5^2 7: four nested square roots and two cube roots of integer powers
+ * stay exact); a numerator is in range when |n| <= EVOGP_DIM_MAX_NUM; all zeros is "dimensionless".  Variables carry var_units[v], a CONST
+ * node is FREE: it may carry whatever unit makes the tree consistent.  violations[t] == 0 iff the constants of tree t can be given units
+ * such that every operation is dimensionally consistent and (check_root != 0) the root has label_units -- always sound; complete for every
+ * tree without a pow / loose_pow over a free base, within the in-range units -- and units[t][i][:] then holds the unit of every node i of
+ * one such assignment (that of a CONST node is the unit of the constant).  Otherwise violations[t] counts the violating nodes (plus one
+ * for a root mismatch) and units holds pass 1's: the fixed units, 0 at free and violating nodes.  flags[t][i]: EVOGP_DIM_FREE (the node
+ * was free in pass 1), EVOGP_DIM_VIOLATION, EVOGP_DIM_MALFORMED, EVOGP_DIM_ROOT_MISMATCH (node 0 only).  The complete rule set -- pass 1
+ * bottom-up, pass 2 top-down -- is the integer restatement tests/dimension_ref.py, which the kernel reproduces word for word.
+ * A malformed row (evogp_hip_tree_intervals's rule) has flags EVOGP_DIM_MALFORMED and unit 0 on every live word (on word 0 when it has
+ * none) and violations = -1.  Words past the live prefix are 0 in units and flags.
+ * var_units: int32[var_len][n_dims], label_units: int32[n_dims], on the device, every numerator in range (the caller checks); label_units
+ * is read only when check_root != 0 but must not be null.  units: int32[pop][gp_len][n_dims], flags: uint8[pop][gp_len], violations:
+ * int32[pop].  One lane per tree, both passes in one launch, no dataset, no workspace, no atomics, nothing synchronises with the host;
+ * bit-identical from run to run.  Any gp_len <= 1024, var_len >= 1, 1 <= n_dims <= EVOGP_DIM_MAX_DIMS.  The outputs must not alias the
+ * inputs or one another. */
+#define EVOGP_DIM_DEN 25200
+#define EVOGP_DIM_MAX_NUM 16777216
+#define EVOGP_DIM_MAX_DIMS 8
+#define EVOGP_DIM_FREE 1
+#define EVOGP_DIM_VIOLATION 2
+#define EVOGP_DIM_MALFORMED 4
+#define EVOGP_DIM_ROOT_MISMATCH 8
+int evogp_hip_tree_dimensions(unsigned pop, unsigned gp_len, unsigned var_len, unsigned n_dims, const float *value, const int16_t *type,
+                              const int16_t *size, const int *var_units, const int *label_units, int check_root, int *units,
+                              unsigned char *flags, int *violations, evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -647,7 +675,7 @@ int evogp_hip_get_sr_division(void);
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
- * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
