@@ -67,6 +67,10 @@ PROTOTYPES = {
     "evogp_hip_tree_hash": [_u, _u, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_tree_classes_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_tree_classes": [_u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_semantic_hash_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_sr_semantic_hash": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_semantic_classes_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_sr_semantic_classes": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_linear_scaling": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_gene_fitness": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_wrap_linear":[_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -41,16 +41,22 @@ class ParetoFront:
 class GeneticProgramming:
     def __init__(self, initial_forest: Forest, crossover: BaseCrossover, mutation: BaseMutation,
                  selection: BaseSelection, enable_pareto_front: bool = False,
-                 regenerate_duplicates: Optional[GenerateDescriptor] = None):
+                 regenerate_duplicates: Optional[GenerateDescriptor] = None, duplicate_classes=None):
         """``regenerate_duplicates`` (no counterpart in the reference): a descriptor from which ``step`` replaces every tree of the new
         forest that is a structural duplicate of an earlier row (``Forest.duplicate_classes``) by a fresh random tree -- one round, so
         a fresh tree may again equal another.  The elites are the first rows and a class keeps its first row, so an elite goes only when
-        an equal elite stands before it.  No host synchronisation."""
+        an equal elite stands before it.  No host synchronisation.
+        ``duplicate_classes``: an optional callable ``forest -> (class_id, is_first)`` that decides which rows are duplicates in place
+        of ``Forest.duplicate_classes`` -- ``SymbolicRegression.semantic_classes`` makes it "predicts the same on every datapoint";
+        the rows whose ``is_first`` is False are the ones replaced.  None: structural duplicates, as before."""
         if regenerate_duplicates is not None:
             d, f = regenerate_duplicates, initial_forest
             assert (d.max_tree_len, d.input_len, d.output_len) == (f.max_tree_len, f.input_len, f.output_len), (
                 "regenerate_duplicates must describe trees of the forest's max_tree_len, input_len and output_len")
+        if duplicate_classes is not None and not callable(duplicate_classes):
+            raise TypeError(f"duplicate_classes should be None or a callable forest -> (class_id, is_first), but got {duplicate_classes!r}")
         self.regenerate_duplicates = regenerate_duplicates
+        self.duplicate_classes = duplicate_classes
         self.forest = initial_forest
         self.pop_size = initial_forest.pop_size
         self.crossover = crossover
@@ -71,7 +77,8 @@ class GeneticProgramming:
     def _regenerate_duplicates(self, d: GenerateDescriptor) -> None:
         """rows that are not the first of their class become fresh trees of ``d``: one masked generation launch and three selects"""
         f = self.forest
-        _, is_first = f.duplicate_classes()
+        classes = getattr(self, "duplicate_classes", None)
+        _, is_first = f.duplicate_classes() if classes is None else classes(f)
         dev = is_first.device
         word = torch.where(is_first, 2**31 - 1, 0).to(torch.int32)   # a tree is generated where (unsigned)word < 1
         try:   # two 32-bit keys from torch's generator of the device, as Forest.random_generate draws them

@@ -18,6 +18,7 @@
 // Only equality decides a class; the hashes decide which rows get compared.  The result is the same partition for any hash_in in which
 // equal rows carry equal hashes.  Without a collision the first comparison decides; a run of r colliding distinct rows costs O(r^2)
 // comparisons of up to n words each.
+#include "dedup.hpp"
 #include "evogp_defs.hpp"
 #include "group_sort.hpp"
 #include "launch.hpp"
@@ -25,16 +26,6 @@
 namespace evogp {
 
 constexpr unsigned kDedupWaves = 4;   // waves (trees) per workgroup
-constexpr unsigned long long kDedupGold = 0x9E3779B97F4A7C15ull;
-
-__device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kDedupWaves * 64) void tree_hash_kernel(const float *value, const int16_t *type, const int16_t *size, unsigned pop,
                                                                      unsigned gp_len, unsigned long long *hash) {
@@ -119,6 +110,26 @@ static hipError_t dedup_workspace(unsigned pop, Arena &a, DedupWorkspace *w) {
     return hipSuccess;
 }
 
+hipError_t dedup_sorted_runs(const unsigned long long *hash_in, unsigned pop, void *workspace, const unsigned **members, const unsigned **seg,
+                             hipStream_t stream) {
+    Arena a{(char *)workspace};
+    DedupWorkspace w;
+    hipError_t e = dedup_workspace(pop, a, &w);
+    if (e != hipSuccess) return e;
+    const dim3 grid((pop + 255u) / 256u), block(256);
+    hipLaunchKernelGGL(dedup_pairs_kernel, grid, block, 0, stream, hash_in, pop, w.keys_a, w.vals_a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    bool in_b;
+    if ((e = sort_buffers(w.temp, w.temp_bytes, w.keys_a, w.keys_b, w.vals_a, w.vals_b, pop, &in_b, stream)) != hipSuccess) return e;
+    const unsigned long long *key = in_b ? w.keys_b : w.keys_a;
+    *members = in_b ? w.vals_b : w.vals_a;
+    hipLaunchKernelGGL(dedup_heads_kernel, grid, block, 0, stream, key, pop, w.head_pos);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = scan_max(w.temp, w.temp_bytes, w.head_pos, w.seg, pop, stream)) != hipSuccess) return e;
+    *seg = w.seg;
+    return hipSuccess;
+}
+
 }  // namespace evogp
 
 using namespace evogp;
@@ -148,22 +159,10 @@ extern "C" int evogp_hip_tree_classes(unsigned pop, unsigned gp_len, const float
     if (pop == 0 || pop > 0x7FFFFFFFu || gp_len == 0 || gp_len > (unsigned)kMaxStack) return EVOGP_E_BADARG;
     if (!value || !type || !size || !hash_in || !class_id_out || !workspace) return EVOGP_E_NULLPTR;
     const hipStream_t stream = (hipStream_t)stream_;
-    Arena a{(char *)workspace};
-    DedupWorkspace w;
-    hipError_t e = dedup_workspace(pop, a, &w);
+    const unsigned *members, *seg;
+    const hipError_t e = dedup_sorted_runs(hash_in, pop, workspace, &members, &seg, stream);
     if (e != hipSuccess) return (int)e;
-    const dim3 grid((pop + 255u) / 256u), block(256);
-
-    hipLaunchKernelGGL(dedup_pairs_kernel, grid, block, 0, stream, hash_in, pop, w.keys_a, w.vals_a);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    bool in_b;
-    if ((e = sort_buffers(w.temp, w.temp_bytes, w.keys_a, w.keys_b, w.vals_a, w.vals_b, pop, &in_b, stream)) != hipSuccess) return (int)e;
-    const unsigned long long *key = in_b ? w.keys_b : w.keys_a;
-    const unsigned *members = in_b ? w.vals_b : w.vals_a;
-    hipLaunchKernelGGL(dedup_heads_kernel, grid, block, 0, stream, key, pop, w.head_pos);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    if ((e = scan_max(w.temp, w.temp_bytes, w.head_pos, w.seg, pop, stream)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(tree_classes_kernel, dim3((pop + kDedupWaves - 1u) / kDedupWaves), dim3(kDedupWaves * 64), 0, stream, value, type, size,
-                       members, (const unsigned *)w.seg, pop, gp_len, class_id_out);
+                       members, seg, pop, gp_len, class_id_out);
     return (int)hipGetLastError();
 }

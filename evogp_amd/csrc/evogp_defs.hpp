@@ -147,4 +147,18 @@ __device__ inline float wave_sum(float x) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// ---- position-keyed hashes (dedup.hip over the nodes of a tree, sr_semantic.hip over the rows of its predictions) --------------------
+// hash = mix64((sum_i mix64(w_i ^ ((i + 1) * kDedupGold))) + n) mod 2^64: the order in which the terms are added does not matter
+constexpr unsigned long long kDedupGold = 0x9E3779B97F4A7C15ull;
+
+// sum of the 64 lanes mod 2^64, in every lane
+__device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
 } // namespace evogp

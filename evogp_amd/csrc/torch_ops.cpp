@@ -586,6 +586,52 @@ Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size,
     return class_id;
 }
 
+// the prologue of the semantic ops: a single-output forest and the rows of a dataset, no labels; returns variables' pointer
+const float *check_semantic(const char *op, const Forest &f, int64_t data_points, int64_t var_len, int64_t out_len, const Tensor &variables) {
+    TORCH_CHECK(var_len > 0, "var_len must be larger than 0, but got ", var_len);
+    TORCH_CHECK(out_len == 1, op, ": single-output trees only (out_len must be 1), but got ", out_len);
+    TORCH_CHECK(data_points > 0, "data_points must be larger than 0, but got ", data_points);
+    TORCH_CHECK(f.pop <= 0x7FFFFFFF && data_points <= 0x7FFFFFFF, "pop_size and data_points must be below 2^31, but got ", f.pop, " and ", data_points);
+    check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
+    return variables.data_ptr<float>();
+}
+
+// int64[pop]: the bits of the 64-bit signature of every tree's predictions on the rows of `variables` (evogp_hip_sr_semantic_hash);
+// the workspace comes from torch's caching allocator
+Tensor tree_SR_semantic_hash(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                             const Tensor &type, const Tensor &size, const Tensor &variables) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    const float *X = check_semantic("tree_SR_semantic_hash", f, data_points, var_len, out_len, variables);
+    c10::DeviceGuard guard(f.dev);
+    Tensor sig = empty({pop_size}, at::kLong, f.dev);
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_semantic_hash_workspace_bytes((unsigned)pop_size, &bytes), "tree_SR_semantic_hash");
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_sr_semantic_hash((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value,
+                                        f.type, f.size, X, (unsigned long long *)sig.data_ptr<int64_t>(), ws.data_ptr(), current_stream(f.dev)),
+             "tree_SR_semantic_hash");
+    return sig;
+}
+
+// int32[pop]: the smallest index of a tree whose predictions equal those of tree t on every row (evogp_hip_sr_semantic_classes); `hash`
+// decides which trees are compared; the workspace comes from torch's caching allocator
+Tensor tree_SR_semantic_classes(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                                const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &hash) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    const float *X = check_semantic("tree_SR_semantic_classes", f, data_points, var_len, out_len, variables);
+    check_tensor(hash, {pop_size}, "hash", f.dev, at::kLong);
+    c10::DeviceGuard guard(f.dev);
+    Tensor class_id = empty({pop_size}, at::kInt, f.dev);
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_semantic_classes_workspace_bytes((unsigned)pop_size, &bytes), "tree_SR_semantic_classes");
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_sr_semantic_classes((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                           f.value, f.type, f.size, X, (const unsigned long long *)hash.data_ptr<int64_t>(),
+                                           class_id.data_ptr<int>(), ws.data_ptr(), current_stream(f.dev)),
+             "tree_SR_semantic_classes");
+    return class_id;
+}
+
 // (front int32, crowding float32, order int32) of a population on (err, cx) (evogp_hip_pareto_rank); the workspace comes from torch's
 // caching allocator
 Tensor3 pareto_rank(const Tensor &err, const Tensor &cx, int64_t cx_bound) {
@@ -1027,6 +1073,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor(d!) normal, Tensor loss_cand, Tensor normal_cand, Tensor(e!) damping) -> ()");
     m.def("tree_hash(Tensor value, Tensor node_type, Tensor subtree_size) -> Tensor");
     m.def("tree_classes(Tensor value, Tensor node_type, Tensor subtree_size, Tensor hash) -> Tensor");
+    m.def("tree_SR_semantic_hash(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor variables) -> Tensor");
+    m.def("tree_SR_semantic_classes(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor variables, Tensor hash) -> Tensor");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_gene_fitness(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
@@ -1073,6 +1123,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_lm_step", &tree_SR_lm_step);
     m.impl("tree_hash", &tree_hash);
     m.impl("tree_classes", &tree_classes);
+    m.impl("tree_SR_semantic_hash", &tree_SR_semantic_hash);
+    m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_gene_fitness", &tree_SR_gene_fitness);
     m.impl("tree_SR_gene_moments", &tree_SR_gene_moments);

@@ -58,3 +58,18 @@ def tree_dimensions(value, node_type, subtree_size, var_units, label_units, chec
     (of a consistent tree: under one consistent assignment of units to its constants); ``flags`` uint8 (pop, gp_len): 1 = free, 2 =
     violation, 4 = the row is malformed, 8 = root mismatch; ``violations`` int32 (pop,): 0 = consistent, -1 = malformed"""
     return torch.ops.evogp_hip.tree_dimensions(value, node_type, subtree_size, var_units, label_units, check_root)
+
+
+def tree_SR_semantic_hash(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables):
+    """int64 ``(pop,)``: ``torch.ops.evogp_hip.tree_SR_semantic_hash`` (csrc/sr_semantic.hip), the bits of the 64-bit signature of every
+    single-output tree's float32 predictions on the rows of ``variables`` ``(data_points, var_len)`` (-0.0 as +0.0, every NaN as one);
+    trees that predict the same value on every row carry the same signature, a malformed row carries 0"""
+    return torch.ops.evogp_hip.tree_SR_semantic_hash(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables)
+
+
+def tree_SR_semantic_classes(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables, hash):
+    """int32 ``(pop,)``: ``torch.ops.evogp_hip.tree_SR_semantic_classes``, the smallest index of a well-formed tree whose predictions
+    equal those of tree t on every row; a malformed row is a class of its own.  ``hash`` int64 ``(pop,)`` only decides which trees are
+    compared and may be any tensor in which equal trees carry equal words (``tree_SR_semantic_hash``'s, normally)"""
+    return torch.ops.evogp_hip.tree_SR_semantic_classes(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size,
+                                                        variables, hash)

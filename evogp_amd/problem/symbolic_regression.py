@@ -24,7 +24,7 @@ class SymbolicRegression(BaseProblem):
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
                  dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
                  input_margin: float = 0.0, monotonic=None, multigene: bool = False, input_units=None, label_units=None,
-                 dimension_penalty: Optional[float] = None):
+                 dimension_penalty: Optional[float] = None, semantic_dedup: bool = False, semantic_keep: str = "smallest"):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -59,7 +59,14 @@ class SymbolicRegression(BaseProblem):
         with ``p >= 0``: its fitness falls by ``p`` times the number of violating nodes instead (a malformed row still gets NaN / -inf).
         With ``linear_scaling`` the root is not held to ``label_units``: slope and intercept are free constants that carry whatever
         unit converts the tree's; violations inside the tree still count.  ``ValueError`` with ``multigene``, and for ``label_units`` or
-        ``dimension_penalty`` without ``input_units``."""
+        ``dimension_penalty`` without ``input_units``.
+        ``semantic_dedup`` (single-output problems): trees that predict the same value on every datapoint are one candidate
+        (``Forest.semantic_classes``: ``x0 + x1`` and ``x1 + x0``, ``x0 * 1`` and ``x0``, every tree that is NaN on all rows).  A tree
+        that is not the representative of its class gets NaN from ``evaluate`` and -inf from ``scores``; every representative keeps
+        its value bit for bit, so each behaviour competes once -- under ``semantic_keep="smallest"`` as its smallest tree, under
+        ``"first"`` as its first.  ``semantic_classes(forest)`` returns the classes, also with ``semantic_dedup=False``.  With
+        ``linear_scaling`` the UNSCALED predictions are compared: trees that are equal only up to an affine map (``x0`` and
+        ``2 * x0 + 1``, which linear scaling scores alike) are NOT merged.  ``ValueError`` with ``multigene``."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -131,7 +138,16 @@ class SymbolicRegression(BaseProblem):
             self.label_units = [Fraction(n, DIM_DEN) for n in label] if has_label else None
         self._sign_constrained = self.monotonic is not None and any(isinstance(c, int) for c in self.monotonic.values())
         self._box_check = self.interval_check or self.monotonic is not None
-        self._constrained = self._box_check or self.input_units is not None
+        self.semantic_dedup = bool(semantic_dedup)
+        if semantic_keep not in ("first", "smallest"):
+            raise ValueError(f"semantic_keep should be 'first' or 'smallest', but got {semantic_keep!r}")
+        self.semantic_keep = semantic_keep
+        if self.semantic_dedup:
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with semantic_dedup: semantic classes compare single-output trees")
+            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+                raise ValueError(f"semantic_dedup works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+        self._constrained = self._box_check or self.input_units is not None or self.semantic_dedup
 
     def _input_box(self, input_bounds, margin: float):
         """the box of admissible inputs as two float32 ``(num_inputs,)`` tensors"""
@@ -171,11 +187,19 @@ class SymbolicRegression(BaseProblem):
         """(pop,) bool: the tree is dimensionally consistent under this problem's units (``dimensions``: ``violations == 0``)"""
         return self.dimensions(forest)[2] == 0
 
+    def semantic_classes(self, forest: Forest, keep: Optional[str] = None):
+        """``(class_id, is_representative)``: ``Forest.semantic_classes`` on this problem's datapoints; ``keep``: None takes the
+        problem's ``semantic_keep``.  The signature ``GeneticProgramming(duplicate_classes=)`` takes."""
+        return forest.semantic_classes(self.datapoints, self.semantic_keep if keep is None else keep)
+
     def _masked(self, forest: Forest, fitness: Tensor, fill: float) -> Tensor:
         mask = None
+        if self.semantic_dedup:
+            mask = self.semantic_classes(forest)[1].to(fitness.device)
         if self._box_check:
-            mask = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
-            mask = mask.to(fitness.device)
+            box = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
+            box = box.to(fitness.device)
+            mask = box if mask is None else mask & box
         if self.input_units is not None:
             viol = self.dimensions(forest)[2].to(fitness.device)
             if self.dimension_penalty is None:

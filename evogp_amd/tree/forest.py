@@ -354,8 +354,60 @@ class Forest:
                         func_mask=self.func_mask)
         return forest, loss
 
-    def _single_output(self, what: str):
+    def _single_output(self, what: str, error=None):
+        if error is not None and self.output_len != 1:
+            raise error(f"{what} works on single-output trees only, but output_len is {self.output_len}")
         assert self.output_len == 1, f"{what} works on single-output trees only, but output_len is {self.output_len}"
+
+    # ---- semantic duplicates -------------------------------------------------------------------
+    def _semantic_rows(self, what: str, inputs: Tensor) -> Tensor:
+        self._single_output(what, ValueError)
+        inputs = check_tensor(inputs, self.batch_node_value.device)
+        if inputs.dim() != 2 or inputs.shape[0] < 1 or inputs.shape[1] != self.input_len:
+            raise ValueError(f"inputs shape should be (D, {self.input_len}) with D >= 1, but got {tuple(inputs.shape)}")
+        return inputs.contiguous().to(torch.float32)
+
+    def semantic_hash(self, inputs: Tensor) -> Tensor:
+        """(pop,) int64: the bits of a 64-bit signature of every tree's float32 predictions on the rows of ``inputs`` ``(D, input_len)``
+        -- ``batch_forward``'s bits with -0.0 taken as +0.0 and every NaN as one (csrc/sr_semantic.hip, include/evogp_hip.h
+        evogp_hip_sr_semantic_hash).  Trees that predict the same on every row have equal signatures; a malformed row has 0.  The
+        predictions are never stored.  Deterministic, no host synchronisation; single-output forests (``ValueError`` otherwise)."""
+        inputs = self._semantic_rows("semantic_hash", inputs)
+        return torch.ops.evogp_hip.tree_SR_semantic_hash(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
+                                                         *self._tensors(), inputs)
+
+    def semantic_classes(self, inputs: Tensor, keep: str = "first"):
+        """``(class_id, is_representative)``: two well-formed trees are in one class when their predictions on ``inputs`` agree on every
+        row (``+0.0 == -0.0``, NaN equals NaN, everything else by bits), whatever they look like: ``x0 + x1`` and ``x1 + x0``,
+        ``x0 * 1`` and ``x0``, any two trees that are NaN everywhere.  A malformed row is a class of its own.  ``class_id`` (pop,) int32
+        names the representative of tree t's class, ``is_representative`` (pop,) bool marks the representatives.  ``keep="first"``: the
+        member of smallest index; ``keep="smallest"``: the member with the fewest nodes, ties to the smallest index.  Exact: the
+        signatures of ``semantic_hash`` only choose which trees are compared.  No host synchronisation."""
+        if keep not in ("first", "smallest"):
+            raise ValueError(f"keep should be 'first' or 'smallest', but got {keep!r}")
+        inputs = self._semantic_rows("semantic_classes", inputs)
+        shape = (self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len)
+        tensors = self._tensors()
+        sig = torch.ops.evogp_hip.tree_SR_semantic_hash(*shape, *tensors, inputs)
+        class_id = torch.ops.evogp_hip.tree_SR_semantic_classes(*shape, *tensors, inputs, sig)
+        index = torch.arange(self.pop_size, dtype=torch.int64, device=class_id.device)
+        if keep == "smallest":
+            # per first-index class the minimum of size * pop + index: integers, exact, and the order of the scatter does not matter
+            first = class_id.to(torch.int64)
+            word = tensors[2][:, 0].to(torch.int64).clamp(0, self.max_tree_len) * self.pop_size + index
+            best = torch.full_like(word, torch.iinfo(torch.int64).max).scatter_reduce(0, first, word, "amin", include_self=True)
+            class_id = (best[first] % self.pop_size).to(torch.int32)
+        return class_id, class_id.to(torch.int64) == index
+
+    def semantic_unique(self, inputs: Tensor, keep: str = "first"):
+        """``(forest, inverse, counts)``, shaped like ``unique``: the representatives of ``semantic_classes(inputs, keep)`` in ascending
+        index order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` predicting what tree t predicts on every row, and
+        ``counts`` (int64) the number of trees per representative.  ONE host synchronisation."""
+        class_id, is_rep = self.semantic_classes(inputs, keep)
+        rank = torch.cumsum(is_rep.to(torch.int64), 0) - 1
+        inverse = rank[class_id.to(torch.int64)]
+        reps = torch.nonzero(is_rep).squeeze(1)   # (the host sync)
+        return self[reps], inverse, torch.bincount(inverse, minlength=reps.numel())
 
     def SR_subtree_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(node_err, node_const)``, both (pop, max_tree_len): ``node_err[t, i]`` is the loss the subtree rooted at node i of tree t

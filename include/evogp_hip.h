@@ -420,6 +420,36 @@ int evogp_hip_tree_classes_workspace_bytes(unsigned pop, unsigned long long *byt
 int evogp_hip_tree_classes(unsigned pop, unsigned gp_len, const float *value, const int16_t *type, const int16_t *size,
                            const unsigned long long *hash_in, int *class_id_out, void *workspace, evogp_stream_t stream);
 
+/* Semantic duplicates of a single-output forest on a dataset (no counterpart in the reference; csrc/sr_semantic.hip): different trees
+ * that are the same model.  p[t][d] is the float32 prediction of tree t on row d of variables (data_points, var_len), the bits
+ * evogp_hip_batch_evaluate stores.  Its KEY is that bit pattern with -0.0 -> +0.0 and every NaN -> 0x7FC00000 (+-inf and everything else
+ * keep their bits).  A row is WELL FORMED when the structural pre-pass of the SR kernels accepts it (the rows for which
+ * evogp_hip_sr_linear_scaling evaluates anything: length clamped to [0, gp_len], not empty, no stack underflow, one value left).
+ * Two trees are EQUAL when both are well formed and their keys agree on every row; a malformed row is a class of its own.
+ *     sig(t) = mix64((sum_{d<D} mix64((uint64)key[t][d] ^ ((d + 1) * 0x9E3779B97F4A7C15))) + D)  mod 2^64,   sig = 0 for a malformed row
+ * with the mix64 of evogp_hip_tree_hash.  The sum is position-keyed and modular: no order of lanes, tiles or waves changes it.
+ * evogp_hip_sr_semantic_hash writes sig_out u64[pop]: the kernels of evogp_hip_sr_linear_scaling (register interpreter, LEAN then FULL
+ * build, then the scratch-stack kernel for deep trees and for var_len > 32) with an integer epilogue; the (pop, D) predictions are never
+ * stored.  workspace: evogp_hip_sr_semantic_hash_workspace_bytes(pop) bytes (a mark byte per tree; no zeroing needed).
+ * evogp_hip_sr_semantic_classes writes class_id_out i32[pop]: class_id[t] = the SMALLEST index of a tree equal to tree t (class_id[t] <= t,
+ * class_id[class_id[t]] == class_id[t]).  hash_in u64[pop] only decides which trees are compared -- equality alone decides a class -- and
+ * may be any array in which equal trees carry equal words (evogp_hip_sr_semantic_hash's, normally): the result does not depend on it.
+ * Trees are compared inside a run of equal hash words, each with the trees before it in ascending index order, and the first equal one
+ * wins.  A comparison first compares the live prefixes word for word (equal programs are equal models: no evaluation), and otherwise
+ * evaluates both trees 64 rows at a time and stops at the first chunk with a differing key.  Without a collision every member of a class
+ * pays one comparison; a run of r distinct colliding trees costs O(r^2) comparisons of up to 2 D tree evaluations each.  workspace:
+ * evogp_hip_sr_semantic_classes_workspace_bytes(pop) bytes (what evogp_hip_tree_classes takes).
+ * Both: deterministic and bit-identical from run to run, no float atomics, everything on the caller's stream, nothing synchronises with
+ * the host, the engine allocates nothing.  Any gp_len <= 1024, var_len and data_points; out_len != 1 returns EVOGP_E_UNSUPPORTED. */
+int evogp_hip_sr_semantic_hash_workspace_bytes(unsigned pop_size, unsigned long long *bytes);
+int evogp_hip_sr_semantic_hash(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                               const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                               unsigned long long *sig_out, void *workspace, evogp_stream_t stream);
+int evogp_hip_sr_semantic_classes_workspace_bytes(unsigned pop_size, unsigned long long *bytes);
+int evogp_hip_sr_semantic_classes(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                  const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                  const unsigned long long *hash_in, int *class_id_out, void *workspace, evogp_stream_t stream);
+
 /* Interval arithmetic over single-output trees (Keijzer 2003; no counterpart in the reference; csrc/sr_interval.hip).  For every node i
  * of the live prefix (n = size[t][0] clamped to [0, gp_len]) of every tree: lo[t][i], hi[t][i] (float32 in [-inf, +inf]) and flags[t][i]
  * (bit 0 EVOGP_ITV_MAY_NAN, bit 1 EVOGP_ITV_MALFORMED) such that for ANY float32 input x with lower[v] <= x[v] <= upper[v] the float32
@@ -675,7 +705,8 @@ int evogp_hip_get_sr_division(void);
  * evogp_hip_lexicase_select; 8: evogp_hip_pareto_rank_workspace_bytes, evogp_hip_pareto_rank, evogp_hip_nsga2_select;
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
- * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
+ * _workspace_bytes were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
