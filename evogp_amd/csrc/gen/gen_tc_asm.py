@@ -41,6 +41,9 @@ DESIGN.md section 3.1 and docs/DESIGN_history_r01_r03.md have the numbers):
     that do not prefetch (NOPF_TWINS: the compiler names them where the next word has no variable operand); end_cls judges segments of
     lanes against a scalar label (the launch stages the rows in label order); a wide-stack build of the 8-row variant (13 entries);
     pow / sinh / cosh / exp / log run over row pairs (gen/pair_rows.py packs the transcribed bodies and proves the packed body equal);
+  * END_LEAN is END for the common launch (single output, MSE, no ragged tile, not in pieces: the host names it, sr_tc.hip
+    TcCompileParams::end_id): its slot holds the whole path from a full tile's rows to the dispatch of the next pass, the rows over row
+    pairs, "NEXT moved the window" as one flag bit; LEAF_C / LEAF_V are the whole program of a tree of one leaf and run all its tiles;
   * constants enter + - * and PUSH_C through packed instructions (one SGPR source for two rows per issue slot, PKCONST);
   * the dataset lives in LDS, transposed so that a lane's rows of one variable are one ds_read_b128 per four rows.
     Variable operands are PREFETCHED one instruction ahead: every handler starts by issuing the LDS reads for the NEXT
@@ -91,7 +94,7 @@ DIVR = ("SV", "VV", "CV")   # divisions by a variable through the launch's recip
 # address, two LDS reads
 NOPF_TWINS = tuple(f"{op}_{form}" for op in ("add", "sub", "mul") for form in FORMS) + ("push_c", "push_v") \
     + tuple(f"divip_{f}" for f in DIVIP) + tuple(f"divr_{f}" for f in DIVR)
-NHF = 37 + 2 * len(UNARY) + 8 + 2 + 4 + len(DIVIP) + 1 + 1 + len(DIVR) + len(NOPF_TWINS) + 1  # handlers per flavour: ... + generic binary forms + generic unary S/V + if, acc, mo_begin, end_mo + in-place divisions + end_cls + swap + divisions by reciprocal columns + twins + nan_tree
+NHF = 37 + 2 * len(UNARY) + 8 + 2 + 4 + len(DIVIP) + 1 + 1 + len(DIVR) + len(NOPF_TWINS) + 1 + 3  # handlers per flavour: ... + generic binary forms + generic unary S/V + if, acc, mo_begin, end_mo + in-place divisions + end_cls + swap + divisions by reciprocal columns + twins + nan_tree + end_lean, leaf_c, leaf_v
 
 
 NOPF = False  # EVOGP_TC_GEN_NOPF=1: drop the operand prefetch (timing experiment, wrong results)
@@ -117,10 +120,11 @@ CNDE64 = False  # EVOGP_TC_GEN_CNDE64=1: every VOP2 v_cndmask_b32 ..., vcc in it
 KWARM = False  # scalar-cache warm-up of the next record (EVOGP_TC_GEN_KWARM=1 at generation time enables it): +1.5 % in round 2, -0.5 % since the division was rebuilt (profiles/r03E_div_range_ab.log)
 
 
-def count_path(L, start, taken, idx_on=True):
+def count_path(L, start, taken, idx_on=True, stop=()):
     """Instruction counts along the usual path of one handler: from its label to the jump to the next handler, following
     unconditional branches; of the conditional ones only those to a label in `taken` (END: a full tile, then the next tile
-    of the same tree).  bench.py multiplies the counts by the handler histogram of a population
+    of the same tree; LEAF_C / LEAF_V, which run every tile themselves: up to a label in `stop`, the first tile and the handler's entry).
+    bench.py multiplies the counts by the handler histogram of a population
     (evogp_hip_debug_tc_histogram) to state how much of the VALU issue rate the interpreter uses."""
     idx = {line[:-1]: i for i, line in enumerate(L) if line.endswith(":")}
     c = {"valu": 0, "trans": 0, "salu": 0, "lds": 0, "vmem": 0, "smem": 0, "valu_clk": 0}
@@ -129,6 +133,8 @@ def count_path(L, start, taken, idx_on=True):
         steps += 1
         line = L[i]
         i += 1
+        if line.endswith(":") and line[:-1] in stop:
+            break
         if line.endswith(":") or line.startswith("."):
             continue
         w = line.split()
@@ -234,7 +240,8 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     for i, name in enumerate(NOPF_TWINS):
         hid[name + "_np"] = nh + 14 + len(DIVIP) + 2 + len(DIVR) + i
     hid["nan_tree"] = nh + 14 + len(DIVIP) + 2 + len(DIVR) + len(NOPF_TWINS)
-    assert NHF == hid["nan_tree"] + 1 and 2 * NHF * SLOT <= 65536
+    hid["end_lean"], hid["leaf_c"], hid["leaf_v"] = (hid["nan_tree"] + 1 + i for i in range(3))
+    assert NHF == hid["leaf_v"] + 1 and 2 * NHF * SLOT <= 65536
     twin = [False]   # True while a no-prefetch twin is being generated (begin, entry, prefetch, wait_cur look at it)
 
     # cycle accounting (stats build only); counters live in the top operand-stack slot
@@ -1050,7 +1057,10 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"s_add_u32 s{sREC}, s{sREC}, s{sA}")
         a(f"s_addc_u32 s{sREC + 1}, s{sREC + 1}, 0")
         load_window()
-        # (sREC now points at the overflow block: the tile loop sees that and reloads the first block for the next pass)
+        # (sREC now points at the overflow block: the tile loop sees that and reloads the first block for the next pass; END_LEAN is
+        # told by flags bit 31, which it clears when it has brought the first block back and tree_done clears for every tree -- a bit
+        # left standing by a tree that bails out costs the wave's next tree one reload, no more)
+        a("s_bitset1_b32 s17, 31")
         a("s_waitcnt lgkmcnt(0)")
         a(f"s_pack_lh_b32_b16 s{sPC}, s{W}, {BASE}")
         a(f"s_lshr_b32 {PF}, s{W}, 24")
@@ -1261,6 +1271,45 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"s_bitset1_b64 s[{sOK}:{sOK + 1}], s{sB}")
         a(f"v_writelane_b32 v7, s{T1}, m0")
         a(f"s_branch {lab('next_tree')}")
+        # END_LEAN: END of a launch that is single-output, MSE, without a ragged tile and not in pieces (the host names it for such a launch,
+        # TcCompileParams::end_id) -- what END decides again on every tile is decided there.  The slot holds the usual path, a full tile
+        # followed by the next tile of the same tree, from the rows to the dispatch of the next pass's first word; the tree's last tile
+        # (lean_last: the early record fetch, the rows, tree_done) and a program of two blocks (lean_moved: NEXT left its overflow block in
+        # the window and said so in flags bit 31) leave the slot.  Differences and squares over row pairs: a - b is a + (-b) bit for bit,
+        # the K additions into v6 keep their order.  The next pass's first operand is sent for under the squares and sums.
+        begin("end_lean", fl)
+        a("s_set_gpr_idx_off")
+        a(f"s_add_u32 s{sTILE}, s{sTILE}, 1")
+        a(f"s_cmp_lt_u32 s{sTILE}, s15")
+        a("s_waitcnt lgkmcnt(0)")
+        a(f"s_cbranch_scc0 {lab(f'lean_last{fl}')}")
+        rows_op("sub", S0, cur, S0)
+        a("s_bitcmp1_b32 s17, 31")
+        a(f"s_cbranch_scc1 {lab(f'lean_moved{fl}')}")
+        a(f"s_mul_i32 s{T1}, s{sTILE}, {G * 1024}")
+        a(f"v_add_u32 v2, s{T1}, v1")
+        a(f"s_lshr_b32 {PF}, s{W}, 24")
+        a(f"v_lshl_add_u32 v4, {PF}, 10, v2")
+        read_bank(P[0], 4)     # (bank 0 may be END's own label bank: its rows were read by the differences above)
+        a("v_add_u32 v3, s14, v2")
+        rows_op("mul", S0, S0, S0)
+        for k in range(K):
+            a(f"v_add_f32 v6, v6, v{S0 + k}")
+        a(f"s_mov_b32 s{sH}, 0")
+        a(f"s_mov_b32 s{sJ}, 0")
+        a(f"s_set_gpr_idx_on s{sJ}, 0")
+        a(f"s_pack_lh_b32_b16 s{sPC}, s{W}, {BASE}")
+        a(f"s_setpc_b64 s[{sPC}:{sPC + 1}]")
+        # LEAF_C / LEAF_V: the whole program of a tree that is one constant / one variable (word 0: always flavour 0), all its tiles run by
+        # the handler itself (leaf_body below).  The pass's set-up has sent for the word's variable (bank 0, tile 0); the labels follow here
+        if fl == 0:
+            for leaf in ("leaf_c", "leaf_v"):
+                begin(leaf, fl)
+                a("s_set_gpr_idx_off")
+                if leaf == "leaf_c":
+                    a(f"s_mov_b32 s{sA}, s{W + 1}")
+                read_bank(T, 3)
+                a(f"s_branch {lab(leaf + '_p0')}")
     a(f".org {lab('hbase')}+{SLOT * 2 * NHF}")
 
     # In-place division bodies.  The gather forms above copy the operands into fixed banks because the division's temporaries
@@ -2277,6 +2326,85 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     a(f"s_add_u32 s{T1}, s{sTILE}, 1")
     a(f"s_branch {lab('end_acc')}")
 
+    def early_record(tag):
+        """the tree's last tile, nothing in flight: send for the record of the batch's next tree (END below; flags bit 10 tells tree_done)"""
+        if not EARLYREC or stats:
+            return
+        a(f"s_add_u32 s{T2}, s{sB}, 1")
+        a(f"s_cmp_lt_u32 s{T2}, s{sNB}")
+        a(f"s_cbranch_scc0 {lab('no_early_' + tag)}")
+        if not fused:
+            a(f"s_add_u32 s{T2}, s{T2}, s{sT0}")
+        rec_addr(sREC, sREC + 1, f"s{T2}", T2)
+        load_window()
+        a(f"{lab('no_early_' + tag)}:")
+
+    def mse_rows(y, x):
+        """v6 += (y - x)^2 over the K rows, the differences and squares in the label bank's registers: END's operations in END's order
+        (x: a bank, or None for the constant in sA)"""
+        if x is not None:
+            rows_op("sub", y, y, x)
+        elif PKCONST and K >= 2:
+            for k in range(0, K, 2):
+                a(f"v_pk_add_f32 v[{y + k}:{y + k + 1}], v[{y + k}:{y + k + 1}], s[{sA}:{sA + 1}] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]")
+        else:
+            for k in range(K):
+                a(f"v_subrev_f32 v{y + k}, s{sA}, v{y + k}")
+        rows_op("mul", y, y, y)
+        for k in range(K):
+            a(f"v_add_f32 v6, v6, v{y + k}")
+
+    # END_LEAN outside its slot.  The last tile of a tree: the next tree's record goes out first, as in END
+    for fl in (0, 1):
+        a(f"{lab(f'lean_last{fl}')}:")
+        early_record(f"lean{fl}")
+        rows_op("sub", S0, P[fl], S0)
+        rows_op("mul", S0, S0, S0)
+        for k in range(K):
+            a(f"v_add_f32 v6, v6, v{S0 + k}")
+        a(f"s_branch {lab('tree_done')}")
+        # ... and a pass that ended in the overflow block: the first block comes back before the next pass
+        a(f"{lab(f'lean_moved{fl}')}:")
+        a("s_bitset0_b32 s17, 31")
+        if fused:
+            rec_addr(sREC, sREC + 1, f"s{sB}", T1)
+        else:
+            a(f"s_add_u32 s{T1}, s{sT0}, s{sB}")
+            rec_addr(sREC, sREC + 1, f"s{T1}", T1)
+        load_window()
+        rows_op("mul", S0, S0, S0)
+        for k in range(K):
+            a(f"v_add_f32 v6, v6, v{S0 + k}")
+        a("s_waitcnt lgkmcnt(0)")
+        a(f"s_branch {lab('tile')}")
+    # LEAF_C / LEAF_V: a tree of one leaf, every tile here -- no dispatch and no END per tile.  Two sets of banks take turns (variable: P0 /
+    # P1, labels: T / Q): a tile's rows run while the next tile's operands are on their way (LDS answers in order, so the wait counts what
+    # was sent after them; the record of the next tree is sent for once the last tile's operands have landed, since scalar loads share the
+    # counter and answer in any order).  v4 and v3 walk the tiles: the pass's set-up left them at tile 0 of the variable and of the labels
+    for leaf in ("leaf_c", "leaf_v"):
+        var = leaf == "leaf_v"
+        Xb, Yb = ((P[0], P[1]) if var else (None, None)), (T, Q)
+        for ph in (0, 1):
+            a(f"{lab(f'{leaf}_p{ph}')}:")
+            a(f"s_add_u32 s{sTILE}, s{sTILE}, 1")
+            a(f"s_cmp_lt_u32 s{sTILE}, s15")
+            a(f"s_cbranch_scc0 {lab(f'{leaf}_last{ph}')}")
+            if var:
+                a(f"v_add_u32 v4, {G * 1024}, v4")
+                read_bank(Xb[1 - ph], 4)
+            a(f"v_add_u32 v3, {G * 1024}, v3")
+            read_bank(Yb[1 - ph], 3)
+            a(f"s_waitcnt lgkmcnt({(2 if var else 1) * G})")
+            mse_rows(Yb[ph], Xb[ph])
+            if ph == 1:
+                a(f"s_branch {lab(f'{leaf}_p0')}")
+        for ph in (0, 1):
+            a(f"{lab(f'{leaf}_last{ph}')}:")
+            a("s_waitcnt lgkmcnt(0)")
+            early_record(f"{leaf}{ph}")
+            mse_rows(Yb[ph], Xb[ph])
+            a(f"s_branch {lab('tree_done')}")
+
     # end of the program: fold this tile's errors into the accumulator.  The labels of the tile were prefetched by the
     # last instruction of the program (the compiler gives END the LDS offset of y as its "variable"), so they sit in
     # the current operand bank of END's flavour.
@@ -2371,6 +2499,7 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     a("s_waitcnt lgkmcnt(0)")
     a(f"s_branch {lab('tile')}")
     a(f"{lab('tree_done')}:")
+    a("s_bitset0_b32 s17, 31")   # (a tree of several blocks leaves "NEXT moved the window" standing, whichever END it has)
     # the tree is finished: fixed-order sum of the 64 lanes, lane b of v7 receives it
     for ctl in ("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0", "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0",
                 "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0", "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0",
@@ -2511,7 +2640,8 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
 
     if info is not None:
         info["K"], info["depth"], info["nhandlers"], info["slot"] = K, DEPTH, NHF, SLOT
-        info["handlers"] = {n: dict(id=i, **count_path(L, lab("h0_" + n), {lab("end_full0"), lab("tile")}, idx_on=not n.startswith("end")))
+        info["handlers"] = {n: dict(id=i, **count_path(L, lab("h0_" + n), {lab("end_full0"), lab("tile")}, idx_on=not n.startswith(("end", "leaf_")),
+                                                       stop={lab("leaf_c_p1"), lab("leaf_v_p1")}))
                             for n, i in hid.items()}
     body = "\n".join(f'    "{line}\\n\\t"' for line in L)
     clob = ['"memory"', '"vcc"', '"scc"'] + [f'"s{i}"' for i in range(8, 102)] + [f'"v{i}"' for i in range(0, NV)]

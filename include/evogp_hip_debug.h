@@ -49,6 +49,11 @@ int evogp_hip_debug_twins(int mode);
  * default / the environment (EVOGP_TC_FOLD = 0, 1 or 2 before the first call; unset: 2).  The fitness words do not depend on the choice
  * (tests/test_gpu_fold.py: 1 against 0, tests/test_gpu_zero_or_nan.py: 2 against 0). */
 int evogp_hip_debug_tc_fold(int mode);
+/* Whether a launch that is single-output, MSE, without a ragged tile and not in pieces ends its programs in END_LEAN and gives a tree that
+ * is one leaf the one-word program LEAF_C / LEAF_V: 1 = yes; 0 = no: END, and push + END for such a tree, as every
+ * other launch; -1 = back to the default / the environment (EVOGP_TC_END = 0 or 1 before the first call; unset: 1).  The fitness words do
+ * not depend on the choice (tests/test_gpu_tc_end.py compares them bit for bit). */
+int evogp_hip_debug_tc_end(int mode);
 
 /* Handler histogram of the program records the most recent evogp_hip_sr_fitness call on the current device compiled:
  * device_hist[flavour * N + id] = number of program words with that handler among the first `pop` trees, N =
