@@ -89,6 +89,8 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_twins": [_i],
     "evogp_hip_debug_tc_fold": [_i],
     "evogp_hip_debug_tc_end": [_i],
+    "evogp_hip_debug_tc_table": [_i],
+    "evogp_hip_debug_tc_table_entry": [_i, _i, C.POINTER(C.c_uint)],
     "evogp_hip_debug_profile": [_i],
     "evogp_hip_debug_profile_read": [C.POINTER(C.c_float), C.POINTER(C.c_int)],
     "evogp_hip_debug_tc_histogram": [_u, _vp, _i, _vp],

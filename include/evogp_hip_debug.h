@@ -54,6 +54,15 @@ int evogp_hip_debug_tc_fold(int mode);
  * other launch; -1 = back to the default / the environment (EVOGP_TC_END = 0 or 1 before the first call; unset: 1).  The fitness words do
  * not depend on the choice (tests/test_gpu_tc_end.py compares them bit for bit). */
 int evogp_hip_debug_tc_end(int mode);
+/* Whether the packed compiler's arithmetic line takes a word's handler, its twin, its in-place form, "kept", "uses a variable" and the stack
+ * delta from its word table -- one class code per lane, one LDS read (csrc/sr_tc.hip tc_table_entry) -- or from the
+ * selects of before: 1 = the table; 0 = the selects; -1 = back to the default / the environment (EVOGP_TC_TABLE = 0 or 1 before the first
+ * call; unset: 1).  The program words do not depend on the choice (tests/test_gpu_tc_table.py compares them bit for bit). */
+int evogp_hip_debug_tc_table(int mode);
+/* Entry `code` (0 .. 127) of the word table, of its half for launches without (recip = 0) or with (1) reciprocal columns, as the engine was
+ * built with it: entry[0] = the four handler ids, entry[1] = the other fields (host memory; tests/test_tc_word_table.py holds the table
+ * to a Python restatement of the selects). */
+int evogp_hip_debug_tc_table_entry(int recip, int code, unsigned *entry);
 
 /* Handler histogram of the program records the most recent evogp_hip_sr_fitness call on the current device compiled:
  * device_hist[flavour * N + id] = number of program words with that handler among the first `pop` trees, N =
