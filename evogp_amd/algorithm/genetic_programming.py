@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 
 from ..tree import Forest, GenerateDescriptor
+from ..tree.utils import draw_keys
 from .crossover import BaseCrossover
 from .mutation import BaseMutation
 from .selection import BaseSelection
@@ -79,15 +80,10 @@ class GeneticProgramming:
         f = self.forest
         classes = getattr(self, "duplicate_classes", None)
         _, is_first = f.duplicate_classes() if classes is None else classes(f)
-        dev = is_first.device
         word = torch.where(is_first, 2**31 - 1, 0).to(torch.int32)   # a tree is generated where (unsigned)word < 1
-        try:   # two 32-bit keys from torch's generator of the device, as Forest.random_generate draws them
-            keys = torch.randint(low=0, high=1000000, size=(2,), dtype=torch.uint32, device=dev)
-        except RuntimeError:  # back ends without a uint32 randint
-            keys = torch.randint(0, 1000000, (2,), device=dev).to(torch.uint32)
         fresh = torch.ops.evogp_hip.tree_generate_masked(f.pop_size, f.max_tree_len, d.input_len, d.output_len, d.const_samples.shape[0],
-                                                         d.out_prob, d.const_prob, keys, d.depth2leaf_probs, d.roulette_funcs,
-                                                         d.const_samples, 0, word, 1)
+                                                         d.out_prob, d.const_prob, draw_keys(is_first.device), d.depth2leaf_probs,
+                                                         d.roulette_funcs, d.const_samples, 0, word, 1)
         keep = is_first[:, None]
         value, ntype, size = (torch.where(keep, old, new) for old, new in zip(f._tensors(), fresh))
         self.forest = Forest(f.input_len, f.output_len, value, ntype, size, func_mask=Forest.join_masks(f.func_mask, d.func_mask))

@@ -7,10 +7,9 @@ reference's extension module does (src/evogp/tree/__init__.py:2, torch_wrapper.c
   ``TORCH_LIBRARY_IMPL(evogp_cuda, CUDA)`` — ``tree_generate / tree_mutate / tree_crossover / tree_evaluate /
   tree_SR_fitness`` — so code written against them runs unchanged.  ROCm builds of PyTorch dispatch HIP tensors on the
   ``CUDA`` key; there is deliberately no CPU implementation (the reference has none, torch_wrapper.cu:301) and no fallback;
-* the extra ops of this engine in the ``evogp_hip`` namespace (no counterpart in the reference):
-  ``tree_generate_offset`` (tree-index offset for sharded populations), ``tree_generate_masked`` and ``breed_default`` /
-  ``breed_default_rows`` (the default generation step in two launches), ``tree_batch_evaluate``
-  (non-replicating ``Forest.batch_forward``), ``tree_batch_argmax_count`` (fused classification accuracy).
+* the extra ops of this engine in the ``evogp_hip`` namespace (no counterpart in the reference).  The list lives in
+  csrc/torch_ops.cpp, one schema per op in its ``TORCH_LIBRARY(evogp_hip)`` block; evogp_amd/tree/forest.py says which
+  method calls which.  The five functions below spell out five of them for callers that hold raw tensors, not a Forest.
 
 Every implementation validates like the reference's wrapper, allocates its outputs and calls the C ABI of
 include/evogp_hip.h (``libevogp_hip.so``, loaded by ``_lib``) on torch's current stream; no Python runs per call.

@@ -11,7 +11,7 @@ import torch
 from torch import Tensor
 
 from ..tree import Forest, default_device
-from ..tree.utils import DIM_DEN, check_units
+from ..tree.utils import DIM_DEN, box_side, check_units, parse_monotonic
 from .base import BaseProblem
 
 _MODES = ["torch", "hybrid parallel", "data parallel", "tree parallel", "auto"]
@@ -85,35 +85,24 @@ class SymbolicRegression(BaseProblem):
             assert func is not None and num_inputs is not None, (
                 "func and num_inputs, must be provided when datapoints and labels are not provided")
             self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
-        if self.linear_scaling and (self.labels.dim() != 2 or self.labels.shape[1] != 1):
-            raise ValueError(f"linear_scaling works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+        # the checks fire in this order: scaling, interval, monotonic, multigene, units, semantic_keep, semantic_dedup
+        if self.linear_scaling:
+            self._one_label_column("linear_scaling")
         self.interval_check = bool(interval_check)
         if self.interval_check:
-            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
-                raise ValueError(f"interval_check works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
-            self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
-        self.monotonic = None
+            self._one_label_column("interval_check")
+        self.monotonic, self._sign_constrained = None, False
         if monotonic is not None:
-            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
-                raise ValueError(f"monotonic works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
-            self.monotonic = {}
-            for v, c in dict(monotonic).items():
-                if not isinstance(v, int) or not 0 <= v < self.datapoints.shape[1]:
-                    raise ValueError(f"monotonic names variable {v!r}, but the inputs are 0 .. {self.datapoints.shape[1] - 1}")
-                if isinstance(c, (tuple, list)) and len(c) == 2 and float(c[0]) <= float(c[1]):
-                    self.monotonic[v] = (float(c[0]), float(c[1]))
-                elif not isinstance(c, (tuple, list)) and c in (1, -1):
-                    self.monotonic[v] = int(c)
-                else:
-                    raise ValueError(f"a monotonic constraint must be +1, -1 or a (dmin, dmax) pair, but variable {v} has {c!r}")
-            if not self.monotonic:
-                raise ValueError("monotonic must constrain at least one variable")
-            if not self.interval_check:
-                self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
+            self._one_label_column("monotonic")
+            variables, bounds, signs = parse_monotonic(monotonic, self.datapoints.shape[1])
+            self.monotonic = {v: s if s else b for v, b, s in zip(variables, bounds, signs)}   # +1 | -1 | (dmin, dmax), normalised
+            self._sign_constrained = any(signs)
+        self._box_check = self.interval_check or self.monotonic is not None
+        if self._box_check:
+            self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
         self.multigene = bool(multigene)
         if self.multigene:
-            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
-                raise ValueError(f"multigene fits one label column, (D, 1), but the labels have shape {tuple(self.labels.shape)}")
+            self._one_label_column("multigene", "fits one label column, (D, 1)")
             for name, on in (("linear_scaling", self.linear_scaling), ("const_opt_steps > 0", self.const_opt_steps > 0),
                              ("simplify_every > 0", self.simplify_every > 0), ("interval_check", self.interval_check),
                              ("monotonic", self.monotonic is not None)):
@@ -126,8 +115,7 @@ class SymbolicRegression(BaseProblem):
         else:
             if self.multigene:
                 raise ValueError("multigene cannot be combined with input_units: dimensional analysis works on single-output trees")
-            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
-                raise ValueError(f"input_units works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+            self._one_label_column("input_units")
             if dimension_penalty is not None:
                 if isinstance(dimension_penalty, bool) or not float(dimension_penalty) >= 0.0:
                     raise ValueError(f"dimension_penalty should be None or a float >= 0, but got {dimension_penalty!r}")
@@ -136,8 +124,6 @@ class SymbolicRegression(BaseProblem):
             var, label, has_label = check_units(input_units, label_units, self.datapoints.shape[1])
             self.input_units = [[Fraction(n, DIM_DEN) for n in row] for row in var]
             self.label_units = [Fraction(n, DIM_DEN) for n in label] if has_label else None
-        self._sign_constrained = self.monotonic is not None and any(isinstance(c, int) for c in self.monotonic.values())
-        self._box_check = self.interval_check or self.monotonic is not None
         self.semantic_dedup = bool(semantic_dedup)
         if semantic_keep not in ("first", "smallest"):
             raise ValueError(f"semantic_keep should be 'first' or 'smallest', but got {semantic_keep!r}")
@@ -145,9 +131,12 @@ class SymbolicRegression(BaseProblem):
         if self.semantic_dedup:
             if self.multigene:
                 raise ValueError("multigene cannot be combined with semantic_dedup: semantic classes compare single-output trees")
-            if self.labels.dim() != 2 or self.labels.shape[1] != 1:
-                raise ValueError(f"semantic_dedup works on single-output problems only, but the labels have shape {tuple(self.labels.shape)}")
+            self._one_label_column("semantic_dedup")
         self._constrained = self._box_check or self.input_units is not None or self.semantic_dedup
+
+    def _one_label_column(self, feature: str, claim: str = "works on single-output problems only"):
+        if self.labels.dim() != 2 or self.labels.shape[1] != 1:
+            raise ValueError(f"{feature} {claim}, but the labels have shape {tuple(self.labels.shape)}")
 
     def _input_box(self, input_bounds, margin: float):
         """the box of admissible inputs as two float32 ``(num_inputs,)`` tensors"""
@@ -157,10 +146,7 @@ class SymbolicRegression(BaseProblem):
             x = self.datapoints.detach().to(torch.float32)
             lower, upper = x.min(dim=0).values, x.max(dim=0).values
         else:
-            lower, upper = input_bounds
-            n = self.datapoints.shape[1]
-            lower, upper = (torch.full((n,), float(b)) if isinstance(b, (int, float)) else torch.as_tensor(b, dtype=torch.float32).reshape(-1)
-                            for b in (lower, upper))
+            lower, upper = (box_side(b, self.datapoints.shape[1]) for b in input_bounds)
         if margin != 0.0:
             pad = margin * (upper - lower)
             lower, upper = lower - pad, upper + pad
@@ -320,44 +306,33 @@ class SymbolicRegression(BaseProblem):
         return (torch.where(bad, torch.full_like(loss, nan), loss).to(torch.float32),
                 torch.where(bad[:, None], torch.full_like(coef, nan), coef))
 
+    def _loss(self, forest: Forest, use_MSE: bool):
+        """``(loss, on_device)``: the positive loss of every tree under this problem's model, and whether a HIP pass over a device
+        forest computed it (``scores`` then finishes it in one launch)"""
+        on_device = self.execute_mode != "torch" and forest.batch_node_value.is_cuda
+        if self.multigene or self.linear_scaling:
+            self._check_scaling(use_MSE)
+            return (self.gene_model(forest) if self.multigene else self.scaled_fitness(forest))[0], on_device
+        if self.execute_mode == "torch":
+            pred = forest.batch_forward(self.datapoints)  # (pop, D, out)
+            err = pred - self.labels[None, :, :]
+            # mean over datapoints AND outputs, as the reference's torch mode (symbolic_regression.py:76-80)
+            return torch.mean(err**2 if use_MSE else err.abs(), dim=(1, 2)), False
+        return forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode), on_device
+
     def evaluate(self, forest: Forest, use_MSE: bool = True) -> Tensor:
-        fitness = self._evaluate(forest, use_MSE)
+        fitness = -self._loss(forest, use_MSE)[0]
         return self._masked(forest, fitness, float("nan")) if self._constrained else fitness
 
     def scores(self, forest: Forest, use_MSE: bool = True) -> Tensor:
         """``evaluate`` with the NaN entries already at -inf (what StandardPipeline.step makes of them, pipeline/standard.py:41-43):
         on the device the sign and the scrub are ONE launch behind the fitness pass instead of four torch launches"""
-        fitness = self._scores(forest, use_MSE)
+        loss, on_device = self._loss(forest, use_MSE)
+        if on_device:
+            fitness = torch.ops.evogp_hip.fitness_scores(loss, True)
+        else:
+            fitness = torch.where(torch.isnan(loss), torch.full_like(loss, float("-inf")), -loss)
         return self._masked(forest, fitness, float("-inf")) if self._constrained else fitness
-
-    def _evaluate(self, forest: Forest, use_MSE: bool) -> Tensor:
-        if self.multigene:
-            self._check_scaling(use_MSE)
-            return -self.gene_model(forest)[0]
-        if self.linear_scaling:
-            self._check_scaling(use_MSE)
-            return -self.scaled_fitness(forest)[0]
-        if self.execute_mode == "torch":
-            pred = forest.batch_forward(self.datapoints)  # (pop, D, out)
-            err = pred - self.labels[None, :, :]
-            # mean over datapoints AND outputs, as the reference's torch mode (symbolic_regression.py:76-80)
-            return -torch.mean(err**2 if use_MSE else err.abs(), dim=(1, 2))
-        return -forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
-
-    def _scores(self, forest: Forest, use_MSE: bool) -> Tensor:
-        if self.multigene:
-            self._check_scaling(use_MSE)
-            if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
-                return torch.ops.evogp_hip.fitness_scores(self.gene_model(forest)[0], True)
-        elif self.linear_scaling:
-            self._check_scaling(use_MSE)
-            if self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
-                return torch.ops.evogp_hip.fitness_scores(self.scaled_fitness(forest)[0], True)
-        elif self.execute_mode != "torch" and forest.batch_node_value.is_cuda:
-            err = forest.SR_fitness(self.datapoints, self.labels, use_MSE, self.execute_mode)
-            return torch.ops.evogp_hip.fitness_scores(err, True)
-        f = self._evaluate(forest, use_MSE)
-        return torch.where(torch.isnan(f), torch.full_like(f, float("-inf")), f)
 
     def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:
         """``forest`` simplified (``Forest.simplify``, on every ``simplify_every``-th call) and then with its constants tuned by
@@ -368,11 +343,8 @@ class SymbolicRegression(BaseProblem):
                 forest = forest.simplify(self.datapoints, self.labels, use_MSE, dedup=self.dedup)[0]
         if self.const_opt_steps <= 0:
             return forest
-        more = {"dedup": True} if self.dedup else {}
-        if self.const_opt_method == "descent":
-            return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE, **more)[0]
         return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE,
-                                         method=self.const_opt_method, **more)[0]
+                                         method=self.const_opt_method, dedup=self.dedup)[0]
 
     @property
     def problem_dim(self):

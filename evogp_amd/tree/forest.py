@@ -4,26 +4,28 @@
     batch_node_type    int16   (pop, max_tree_len)   NType, bit 7 = OUT_NODE
     batch_subtree_size int16   (pop, max_tree_len)   subtree sizes, [:, 0] = live tree length
 
-API surface follows src/evogp/tree/forest.py:11-499 (constructor, ``random_generate``,
-``zero_generate``, ``forward``, ``batch_forward``, ``mutate``, ``crossover``, ``SR_fitness``,
-indexing, concatenation, iteration, pickling), plus ``structure_hash`` / ``duplicate_classes`` / ``unique`` (structural duplicates,
-csrc/dedup.hip; ``optimize_constants`` and ``simplify`` take ``dedup=True`` to run their dataset passes once per distinct tree), ``SR_gradient`` / ``SR_normal_equations`` / ``optimize_constants`` (gradient
-descent or Levenberg-Marquardt on the constants, no counterpart in the reference), ``SR_case_errors`` (per-case errors for lexicase selection), ``SR_subtree_errors`` / ``simplify``
-(the loss of every subtree, and the rewrite into a smaller tree that is no worse) and ``SR_scaled_fitness`` / ``apply_scaling`` (linear
-scaling: the loss under the least-squares slope and intercept, and the tree that carries them) and ``SR_intervals`` / ``safe_mask`` (interval
-arithmetic: bounds of every subtree over a box of inputs, and the trees that are defined and finite on all of it) and
-``SR_derivative_intervals`` / ``monotone_mask`` (bounds of every subtree's partial derivatives over the box, and the trees proven monotone) and
-``SR_gene_fitness`` / ``SR_gene_moments`` / ``gene_predict`` (multi-gene regression: the outputs of a tree as features of a least-squares model) and
-``SR_dimensions`` / ``dimension_mask`` (dimensional analysis: the physical unit of every subtree, and the trees whose constants can be given units
-that make them consistent).  Every heavy method is one call into
-``torch.ops.evogp_cuda.*`` (evogp_amd/ops.py), i.e. one HIP kernel.  Differences from the
-reference, all deliberate:
+The constructor, generation, evaluation, the genetic operators and the container protocol follow src/evogp/tree/forest.py:11-499; the
+rest has no counterpart in the reference.  Every heavy method is one call into ``torch.ops.evogp_cuda.*`` / ``evogp_hip.*``
+(evogp_amd/ops.py), i.e. one HIP kernel.
 
-* ``batch_forward`` does NOT replicate the forest ``batch`` times (forest.py:151-161: three
-  ``repeat_interleave`` copies + ``x.repeat``): it calls the non-replicating
-  ``evogp_hip::tree_batch_evaluate`` and returns the same ``(pop, batch, out)`` tensor;
-* ``random_generate`` accepts ``tree_index_offset`` / ``keys`` so a sharded population can be made
-  bit-identical to the single-device one.
+    construction          random_generate, zero_generate
+    evaluation            forward, batch_forward, prepare_forward, SR_fitness, SR_case_errors (per case, for lexicase selection)
+    constants             SR_gradient, SR_normal_equations, optimize_constants (gradient descent or Levenberg-Marquardt)
+    structural duplicates structure_hash, duplicate_classes, unique (csrc/dedup.hip); ``dedup=True`` elsewhere runs once per class
+    semantic duplicates   semantic_hash, semantic_classes, semantic_unique: trees equal on every data row
+    subtrees              SR_subtree_errors, simplify: the loss of every subtree; the smaller tree that is no worse
+    linear scaling        SR_scaled_fitness, apply_scaling: the loss under the least-squares slope and intercept; the tree with them
+    multi-gene            SR_gene_fitness, SR_gene_moments, gene_predict: a tree's outputs as features of a least-squares model
+    intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
+    derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
+    dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
+    genetic operators     mutate, crossover
+    container, pickling   indexing, iteration, ``+``, ``__getstate__`` / ``__setstate__``
+
+Two deliberate differences from the reference: ``batch_forward`` does NOT replicate the forest ``batch`` times (forest.py:151-161:
+three ``repeat_interleave`` copies + ``x.repeat``) but calls the non-replicating ``evogp_hip::tree_batch_evaluate`` and returns the same
+``(pop, batch, out)`` tensor; ``random_generate`` accepts ``tree_index_offset`` / ``keys`` so that a sharded population can be made
+bit-identical to the single-device one.
 """
 from __future__ import annotations
 
@@ -36,13 +38,28 @@ from torch import Tensor
 from . import utils as _utils
 from .descriptor import GenerateDescriptor
 from .tree import Tree
-from .utils import NType, check_tensor, check_units
+from .utils import NType, box_side, check_tensor, check_units, draw_keys, parse_monotonic
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
+
+
+def _symmetric(packed: Tensor, K: int) -> Tensor:
+    """``(pop, K (K + 1) / 2)`` upper triangles in row-major order, as the kernels pack them -> the mirrored ``(pop, K, K)`` matrices"""
+    iu = torch.triu_indices(K, K, device=packed.device)
+    full = packed.new_zeros((packed.shape[0], K, K))
+    full[:, iu[0], iu[1]] = packed
+    full[:, iu[1], iu[0]] = packed
+    return full
+
+
+def _root_safe(lo: Tensor, hi: Tensor, flags: Tensor, max_abs: float) -> Tensor:
+    """(pop,) bool from per-node enclosures: the root can not be a NaN, both its bounds are finite and neither exceeds ``max_abs``"""
+    lo, hi = lo[:, 0], hi[:, 0]
+    return (flags[:, 0] == 0) & torch.isfinite(lo) & torch.isfinite(hi) & (torch.maximum(lo.abs(), hi.abs()) <= max_abs)
 
 
 class Forest:
@@ -88,11 +105,7 @@ class Forest:
                         tree_index_offset: int = 0) -> "Forest":
         assert isinstance(pop_size, int) and pop_size > 0, "pop_size should be a positive integer"
         if keys is None:
-            # two 32-bit keys from torch's generator of the device (forest.py:51-58)
-            try:
-                keys = torch.randint(low=0, high=1000000, size=(2,), dtype=torch.uint32, device=_utils.default_device())
-            except RuntimeError:  # back ends without a uint32 randint
-                keys = torch.randint(0, 1000000, (2,), device=_utils.default_device()).to(torch.uint32)
+            keys = draw_keys()
         args = (pop_size, descriptor.max_tree_len, descriptor.input_len, descriptor.output_len,
                 descriptor.const_samples.shape[0], descriptor.out_prob, descriptor.const_prob, keys,
                 descriptor.depth2leaf_probs, descriptor.roulette_funcs, descriptor.const_samples)
@@ -169,31 +182,10 @@ class Forest:
         x = check_tensor(x, self.batch_node_value.device)
         assert x.dim() == 2 and x.shape[1] == self.input_len, (
             f"x shape[1] should be {self.input_len}, but got {tuple(x.shape)}")
-        return torch.ops.evogp_hip.tree_batch_evaluate(self.pop_size, x.shape[0], self.max_tree_len, self.input_len,
-                                                       self.output_len, *self._tensors(),
-                                                       x.contiguous().to(torch.float32))
-
-    def SR_fitness(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, execute_mode: str = "auto") -> Tensor:
-        """Mean squared / absolute error of every tree over the dataset: (pop,), positive."""
-        inputs, labels = check_tensor(inputs, self.batch_node_value.device), check_tensor(labels, self.batch_node_value.device)
-        n = inputs.shape[0]
-        assert inputs.shape == (n, self.input_len), (
-            f"inputs shape should be ({n}, {self.input_len}), but got {inputs.shape}")
-        assert labels.shape == (n, self.output_len), (
-            f"outputs shape should be ({n}, {self.output_len}), but got {labels.shape}")
-        assert execute_mode in _SR_MODES, f"execute_mode should be one of {list(_SR_MODES)}, but got {execute_mode}"
-        mask = self.func_mask
-        if inputs.is_cuda and mask:
-            # what this object knows beyond the tensors: the function set of the trees (the descriptors they came from)
-            return torch.ops.evogp_hip.tree_SR_fitness_masked(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len, use_MSE,
-                                                              *self._tensors(), inputs.contiguous().to(torch.float32),
-                                                              labels.contiguous().to(torch.float32), _SR_MODES[execute_mode], mask)
-        return torch.ops.evogp_cuda.tree_SR_fitness(self.pop_size, n, self.max_tree_len, self.input_len,
-                                                    self.output_len, use_MSE, *self._tensors(),
-                                                    inputs.contiguous().to(torch.float32),
-                                                    labels.contiguous().to(torch.float32), _SR_MODES[execute_mode])
+        return torch.ops.evogp_hip.tree_batch_evaluate(*self._shape(x), *self._tensors(), x.contiguous().to(torch.float32))
 
     def _sr_data(self, inputs: Tensor, labels: Tensor):
+        """the dataset as the kernels take it: on the forest's device, shapes checked, contiguous float32"""
         inputs, labels = check_tensor(inputs, self.batch_node_value.device), check_tensor(labels, self.batch_node_value.device)
         n = inputs.shape[0]
         assert inputs.shape == (n, self.input_len), (
@@ -202,6 +194,27 @@ class Forest:
             f"outputs shape should be ({n}, {self.output_len}), but got {labels.shape}")
         return inputs.contiguous().to(torch.float32), labels.contiguous().to(torch.float32)
 
+    def _shape(self, inputs: Tensor):
+        """the five integers every dataset op starts with: (pop_size, data rows, max_tree_len, input_len, output_len)"""
+        return self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len
+
+    def _single_output(self, what: str, error=AssertionError):
+        """the one guard of the single-output methods; ``error``: the type the method is documented to raise"""
+        if self.output_len != 1:
+            raise error(f"{what} works on single-output trees only, but output_len is {self.output_len}")
+
+    def SR_fitness(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, execute_mode: str = "auto") -> Tensor:
+        """Mean squared / absolute error of every tree over the dataset: (pop,), positive."""
+        inputs, labels = self._sr_data(inputs, labels)
+        assert execute_mode in _SR_MODES, f"execute_mode should be one of {list(_SR_MODES)}, but got {execute_mode}"
+        mask = self.func_mask
+        if inputs.is_cuda and mask:
+            # what this object knows beyond the tensors: the function set of the trees (the descriptors they came from)
+            return torch.ops.evogp_hip.tree_SR_fitness_masked(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels,
+                                                              _SR_MODES[execute_mode], mask)
+        return torch.ops.evogp_cuda.tree_SR_fitness(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels,
+                                                    _SR_MODES[execute_mode])
+
     def SR_case_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True) -> Tensor:
         """Per-case errors ``(pop, D)``: entry ``[t, d]`` is the squared (``use_MSE``) or absolute error of tree t on row d, averaged
         over the outputs, in float32 (NaN stays NaN).  The predictions are ``batch_forward``'s, bit for bit.  The tensor is the transposed
@@ -209,16 +222,13 @@ class Forest:
         selection reads it (csrc/lexicase.hip).  Its mean over the rows is what ``SR_fitness`` returns, up to the fitness path's order
         of summation."""
         inputs, labels = self._sr_data(inputs, labels)
-        errors = torch.ops.evogp_hip.tree_SR_case_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
-                                                         use_MSE, *self._tensors(), inputs, labels)
-        return errors.t()
+        return torch.ops.evogp_hip.tree_SR_case_errors(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels).t()
 
     def SR_gradient(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(loss, grad)``: ``loss`` (pop,) is what ``SR_fitness`` returns, ``grad`` (pop, max_tree_len) is d loss / d value at every
         constant node and exactly 0 elsewhere (one reverse-mode HIP pass, csrc/sr_grad.hip).  Malformed trees: NaN loss, zero row."""
         inputs, labels = self._sr_data(inputs, labels)
-        return torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
-                                                    use_MSE, *self._tensors(), inputs, labels)
+        return torch.ops.evogp_hip.tree_SR_gradient(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels)
 
     def SR_normal_equations(self, inputs: Tensor, labels: Tensor):
         """``(loss, A, b, const_index)`` of the Gauss-Newton model of the MSE loss in each tree's OPTIMISED constants: its first
@@ -230,15 +240,10 @@ class Forest:
         self._single_output("SR_normal_equations")
         inputs, labels = self._sr_data(inputs, labels)
         value, ntype, size = self._tensors()
-        loss, normal = torch.ops.evogp_hip.tree_SR_normal_eq(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
-                                                             value, ntype, size, inputs, labels)
+        loss, normal = torch.ops.evogp_hip.tree_SR_normal_eq(*self._shape(inputs), value, ntype, size, inputs, labels)
         K = LM_MAX_CONSTS
-        iu = torch.triu_indices(K, K, device=normal.device)   # row-major upper triangle: the packed order
-        tri = normal[:, :iu.shape[1]]
-        A = normal.new_zeros((self.pop_size, K, K))
-        A[:, iu[0], iu[1]] = tri
-        A[:, iu[1], iu[0]] = tri
-        b = normal[:, iu.shape[1]:].clone()
+        T = K * (K + 1) // 2
+        A, b = _symmetric(normal[:, :T], K), normal[:, T:].clone()
         L = self.max_tree_len
         pos = torch.arange(L, device=value.device)[None, :]
         is_c = (ntype == NType.CONST) & (pos < size[:, :1].clamp(0, L))
@@ -267,10 +272,12 @@ class Forest:
         """``(forest, inverse, counts)``, shaped like ``torch.unique``: the representatives of ``duplicate_classes`` in ascending index
         order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` equal to tree t on its live prefix, and ``counts``
         (int64) the number of trees per representative.  ONE host synchronisation (the number of representatives sizes the result)."""
-        class_id, is_first = self.duplicate_classes()
-        rank = torch.cumsum(is_first.to(torch.int64), 0) - 1
+        return self._unique(*self.duplicate_classes())
+
+    def _unique(self, class_id: Tensor, is_rep: Tensor):
+        rank = torch.cumsum(is_rep.to(torch.int64), 0) - 1
         inverse = rank[class_id.to(torch.int64)]
-        reps = torch.nonzero(is_first).squeeze(1)   # (the host sync)
+        reps = torch.nonzero(is_rep).squeeze(1)   # (the host sync)
         return self[reps], inverse, torch.bincount(inverse, minlength=reps.numel())
 
     def _first_rows_only(self):
@@ -281,6 +288,14 @@ class Forest:
         size = size.clone()
         size[:, 0] = torch.where(is_first, size[:, 0], torch.zeros_like(size[:, 0]))
         return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), class_id.to(torch.int64)
+
+    def _once_per_class(self, dedup: bool):
+        """``(forest, gather)`` for a dataset pass that honours ``dedup``: the forest to run the pass on and the function that hands
+        every row of a result its own entry -- ``_first_rows_only`` and ``t -> t[class_id]``, or this forest and the identity"""
+        if not dedup:
+            return self, lambda t: t
+        firsts, class_id = self._first_rows_only()
+        return firsts, lambda t: t[class_id]
 
     def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True,
                            method: str = "descent", damping: float = 1e-3, dedup: bool = False):
@@ -301,63 +316,41 @@ class Forest:
         assert steps >= 0, f"steps should be >= 0, but got {steps}"
         if method not in ("descent", "lm"):
             raise ValueError(f"method should be 'descent' or 'lm', but got {method!r}")
-        if dedup:
-            firsts, class_id = self._first_rows_only()
-            tuned, loss = firsts.optimize_constants(inputs, labels, steps, step_size, use_MSE, method, damping)
-            # constants live in the prefix, which the rows of a class share; every row keeps its own tail words
-            L = self.max_tree_len
-            live = torch.arange(L, device=class_id.device)[None, :] < self.batch_subtree_size[:, :1]
-            value = torch.where(live, tuned.batch_node_value[class_id], tuned.batch_node_value)
-            forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
-                            func_mask=self.func_mask)
-            return forest, loss[class_id]
+        source, gather = self._once_per_class(dedup)
         if method == "lm":
             if not use_MSE:
                 raise ValueError("method='lm' minimises the mean squared error: use_MSE must be True")
-            if self.output_len != 1:
-                raise ValueError(f"method='lm' works on single-output trees only, but output_len is {self.output_len}")
-            return self._optimize_constants_lm(inputs, labels, steps, damping)
+            self._single_output("method='lm'", ValueError)
         inputs, labels = self._sr_data(inputs, labels)
-        n = inputs.shape[0]
-        value, ntype, size = self._tensors()
-        value = value.clone()
-        loss, grad = torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len, use_MSE,
-                                                          value, ntype, size, inputs, labels)
-        if steps > 0:
-            cand = torch.empty_like(value)
-            step = torch.full((self.pop_size,), float(step_size), dtype=torch.float32, device=value.device)
-            step_op = torch.ops.evogp_hip.tree_SR_const_step
-            step_op(2, self.output_len, value, ntype, size, cand, loss, grad, loss, grad, step)
-            for k in range(steps):
-                loss_c, grad_c = torch.ops.evogp_hip.tree_SR_gradient(self.pop_size, n, self.max_tree_len, self.input_len, self.output_len,
-                                                                      use_MSE, cand, ntype, size, inputs, labels)
-                step_op(3 if k + 1 < steps else 1, self.output_len, value, ntype, size, cand, loss, grad, loss_c, grad_c, step)
+        shape, hip = self._shape(inputs), torch.ops.evogp_hip
+        if method == "lm":   # the model is the packed normal equations, the per-tree scalar is lambda
+            value, loss = source._tune(steps, damping, lambda *tree: hip.tree_SR_normal_eq(*shape, *tree, inputs, labels), hip.tree_SR_lm_step)
+        else:                # the model is the gradient, the per-tree scalar is the step length
+            value, loss = source._tune(steps, step_size, lambda *tree: hip.tree_SR_gradient(*shape, use_MSE, *tree, inputs, labels),
+                                       lambda phase, *rest: hip.tree_SR_const_step(phase, self.output_len, *rest))
+        if dedup:   # constants live in the prefix, which the rows of a class share; every row keeps its own tail words
+            live = torch.arange(self.max_tree_len, device=value.device)[None, :] < self.batch_subtree_size[:, :1]
+            value = torch.where(live, gather(value), value)
         forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
                         func_mask=self.func_mask)
-        return forest, loss
+        return forest, gather(loss)
 
-    def _optimize_constants_lm(self, inputs: Tensor, labels: Tensor, steps: int, damping: float):
-        inputs, labels = self._sr_data(inputs, labels)
+    def _tune(self, steps: int, start: float, evaluate, propose):
+        """``(value, loss)``: the accept/reject loop of both optimisers on a copy of the node values.  ``evaluate(value, ntype, size)``
+        is the dataset pass, ``(loss, model)``; ``propose(phase, value, ntype, size, cand, loss, model, loss_c, model_c, scalar)`` is
+        the step op: phase 2 writes the first candidate, phase 3 accepts or rejects one and writes the next, phase 1 only accepts or
+        rejects.  ``scalar`` (pop,) starts at ``start``."""
         value, ntype, size = self._tensors()
         value = value.clone()
-        shape = (self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len)
-        normal_eq, step_op = torch.ops.evogp_hip.tree_SR_normal_eq, torch.ops.evogp_hip.tree_SR_lm_step
-        loss, normal = normal_eq(*shape, value, ntype, size, inputs, labels)
+        loss, model = evaluate(value, ntype, size)
         if steps > 0:
             cand = torch.empty_like(value)
-            lam = torch.full((self.pop_size,), float(damping), dtype=torch.float32, device=value.device)
-            step_op(2, value, ntype, size, cand, loss, normal, loss, normal, lam)
+            scalar = torch.full((self.pop_size,), float(start), dtype=torch.float32, device=value.device)
+            propose(2, value, ntype, size, cand, loss, model, loss, model, scalar)
             for k in range(steps):
-                loss_c, normal_c = normal_eq(*shape, cand, ntype, size, inputs, labels)
-                step_op(3 if k + 1 < steps else 1, value, ntype, size, cand, loss, normal, loss_c, normal_c, lam)
-        forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
-                        func_mask=self.func_mask)
-        return forest, loss
-
-    def _single_output(self, what: str, error=None):
-        if error is not None and self.output_len != 1:
-            raise error(f"{what} works on single-output trees only, but output_len is {self.output_len}")
-        assert self.output_len == 1, f"{what} works on single-output trees only, but output_len is {self.output_len}"
+                loss_c, model_c = evaluate(cand, ntype, size)
+                propose(3 if k + 1 < steps else 1, value, ntype, size, cand, loss, model, loss_c, model_c, scalar)
+        return value, loss
 
     # ---- semantic duplicates -------------------------------------------------------------------
     def _semantic_rows(self, what: str, inputs: Tensor) -> Tensor:
@@ -373,8 +366,7 @@ class Forest:
         evogp_hip_sr_semantic_hash).  Trees that predict the same on every row have equal signatures; a malformed row has 0.  The
         predictions are never stored.  Deterministic, no host synchronisation; single-output forests (``ValueError`` otherwise)."""
         inputs = self._semantic_rows("semantic_hash", inputs)
-        return torch.ops.evogp_hip.tree_SR_semantic_hash(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
-                                                         *self._tensors(), inputs)
+        return torch.ops.evogp_hip.tree_SR_semantic_hash(*self._shape(inputs), *self._tensors(), inputs)
 
     def semantic_classes(self, inputs: Tensor, keep: str = "first"):
         """``(class_id, is_representative)``: two well-formed trees are in one class when their predictions on ``inputs`` agree on every
@@ -386,8 +378,7 @@ class Forest:
         if keep not in ("first", "smallest"):
             raise ValueError(f"keep should be 'first' or 'smallest', but got {keep!r}")
         inputs = self._semantic_rows("semantic_classes", inputs)
-        shape = (self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len)
-        tensors = self._tensors()
+        shape, tensors = self._shape(inputs), self._tensors()
         sig = torch.ops.evogp_hip.tree_SR_semantic_hash(*shape, *tensors, inputs)
         class_id = torch.ops.evogp_hip.tree_SR_semantic_classes(*shape, *tensors, inputs, sig)
         index = torch.arange(self.pop_size, dtype=torch.int64, device=class_id.device)
@@ -403,11 +394,7 @@ class Forest:
         """``(forest, inverse, counts)``, shaped like ``unique``: the representatives of ``semantic_classes(inputs, keep)`` in ascending
         index order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` predicting what tree t predicts on every row, and
         ``counts`` (int64) the number of trees per representative.  ONE host synchronisation."""
-        class_id, is_rep = self.semantic_classes(inputs, keep)
-        rank = torch.cumsum(is_rep.to(torch.int64), 0) - 1
-        inverse = rank[class_id.to(torch.int64)]
-        reps = torch.nonzero(is_rep).squeeze(1)   # (the host sync)
-        return self[reps], inverse, torch.bincount(inverse, minlength=reps.numel())
+        return self._unique(*self.semantic_classes(inputs, keep))
 
     def SR_subtree_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(node_err, node_const)``, both (pop, max_tree_len): ``node_err[t, i]`` is the loss the subtree rooted at node i of tree t
@@ -417,8 +404,7 @@ class Forest:
         tree over every row (csrc/sr_subtree.hip); single-output forests only."""
         self._single_output("SR_subtree_errors")
         inputs, labels = self._sr_data(inputs, labels)
-        return torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, self.output_len,
-                                                          use_MSE, *self._tensors(), inputs, labels)
+        return torch.ops.evogp_hip.tree_SR_subtree_errors(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels)
 
     def simplify(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, hoist: bool = True, fold_constants: bool = True,
                  dedup: bool = False):
@@ -435,16 +421,10 @@ class Forest:
         self._single_output("simplify")
         inputs, labels = self._sr_data(inputs, labels)
         value, ntype, size = self._tensors()
-        if dedup:
-            firsts, class_id = self._first_rows_only()
-            node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
-                                                                              self.output_len, use_MSE, *firsts._tensors(), inputs, labels)
-            node_err, node_const = node_err[class_id], node_const[class_id]
-        else:
-            node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
-                                                                              self.output_len, use_MSE, value, ntype, size, inputs, labels)
+        source, gather = self._once_per_class(dedup)
+        node_err, node_const = torch.ops.evogp_hip.tree_SR_subtree_errors(*self._shape(inputs), use_MSE, *source._tensors(), inputs, labels)
         value, ntype, size, _, loss = torch.ops.evogp_hip.tree_prune(self.output_len, bool(hoist), bool(fold_constants), value, ntype, size,
-                                                                     node_err, node_const)
+                                                                     gather(node_err), gather(node_const))
         # (a rewritten tree's functions are a subset of the old tree's)
         return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), loss
 
@@ -461,11 +441,9 @@ class Forest:
         as empty trees and taking the result of their class's first row."""
         self._single_output("SR_scaled_fitness")
         inputs, labels = self._sr_data(inputs, labels)
-        source, class_id = self._first_rows_only() if dedup else (self, None)
-        loss, coef = torch.ops.evogp_hip.tree_SR_linear_scaling(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
-                                                                self.output_len, *source._tensors(), inputs, labels)
-        if dedup:
-            loss, coef = loss[class_id], coef[class_id]
+        source, gather = self._once_per_class(dedup)
+        loss, coef = torch.ops.evogp_hip.tree_SR_linear_scaling(*self._shape(inputs), *source._tensors(), inputs, labels)
+        loss, coef = gather(loss), gather(coef)
         return loss, coef[:, 1], coef[:, 0]
 
     def apply_scaling(self, slope: Tensor, intercept: Tensor, grow: bool = False):
@@ -509,26 +487,19 @@ class Forest:
 
         ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
         inputs, labels = self._gene_data("SR_gene_fitness", inputs, labels)
-        source, class_id = self._first_rows_only() if dedup else (self, None)
-        loss, coef = torch.ops.evogp_hip.tree_SR_gene_fitness(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len,
-                                                              self.output_len, *source._tensors(), inputs, labels)
-        if dedup:
-            loss, coef = loss[class_id], coef[class_id]
-        return loss, coef
+        source, gather = self._once_per_class(dedup)
+        loss, coef = torch.ops.evogp_hip.tree_SR_gene_fitness(*self._shape(inputs), *source._tensors(), inputs, labels)
+        return gather(loss), gather(coef)
 
     def SR_gene_moments(self, inputs: Tensor, labels: Tensor):
         """``(mean (pop, G), cov (pop, G, G), cov_y (pop, G))``, float64: the moments ``SR_gene_fitness`` solves from -- the mean of
         every gene, the covariance of the genes (the kernel's upper triangle, mirrored) and their covariance with the labels, all
         with divisor D.  A malformed tree has zeros."""
         inputs, labels = self._gene_data("SR_gene_moments", inputs, labels)
+        _, _, m = torch.ops.evogp_hip.tree_SR_gene_moments(*self._shape(inputs), *self._tensors(), inputs, labels)
         G = self.output_len
-        _, _, m = torch.ops.evogp_hip.tree_SR_gene_moments(self.pop_size, inputs.shape[0], self.max_tree_len, self.input_len, G,
-                                                           *self._tensors(), inputs, labels)
-        iu = torch.triu_indices(G, G, device=m.device)
-        cov = torch.zeros(self.pop_size, G, G, dtype=m.dtype, device=m.device)
-        cov[:, iu[0], iu[1]] = m[:, G:G + iu.shape[1]]
-        cov[:, iu[1], iu[0]] = m[:, G:G + iu.shape[1]]
-        return m[:, :G], cov, m[:, G + iu.shape[1]:]
+        T = G * (G + 1) // 2
+        return m[:, :G], _symmetric(m[:, G:G + T], G), m[:, G + T:]
 
     def gene_predict(self, inputs: Tensor, coef: Tensor) -> Tensor:
         """``(pop, D)`` float32: the multi-gene model ``coef[:, 0] + batch_forward(inputs) @ coef[:, 1:]`` in float32 torch.  This is
@@ -544,16 +515,10 @@ class Forest:
     def _box(self, lower, upper):
         """the box as two float32 ``(input_len,)`` tensors on the forest's device, checked on the host"""
         dev = self.batch_node_value.device
-
-        def side(b, name):
-            if isinstance(b, (int, float)):
-                return torch.full((self.input_len,), float(b), dtype=torch.float32)
-            b = torch.as_tensor(b).detach().to("cpu", torch.float32).reshape(-1)
+        lower, upper = box_side(lower, self.input_len), box_side(upper, self.input_len)
+        for name, b in (("lower", lower), ("upper", upper)):
             if b.shape[0] != self.input_len:
                 raise ValueError(f"{name} should hold {self.input_len} bounds, but got {b.shape[0]}")
-            return b
-
-        lower, upper = side(lower, "lower"), side(upper, "upper")
         if not bool(torch.isfinite(lower).all() and torch.isfinite(upper).all()):
             raise ValueError("the bounds of the box must be finite")
         if bool((lower > upper).any()):
@@ -567,17 +532,13 @@ class Forest:
         beyond the check of the bounds).  ``flags`` bit 0 (1): the value may be a NaN; bit 1 (2): the row is malformed (all its live
         nodes then hold NaN bounds).  Words past a tree's length are 0.  ``lower`` / ``upper``: floats or ``(input_len,)`` tensors,
         finite, ``lower <= upper`` (``ValueError`` otherwise); single-output forests only."""
-        if self.output_len != 1:
-            raise ValueError(f"SR_intervals works on single-output trees only, but output_len is {self.output_len}")
-        lower, upper = self._box(lower, upper)
-        return torch.ops.evogp_hip.tree_intervals(*self._tensors(), lower, upper)
+        self._single_output("SR_intervals", ValueError)
+        return torch.ops.evogp_hip.tree_intervals(*self._tensors(), *self._box(lower, upper))
 
     def safe_mask(self, lower, upper, max_abs: float = float("inf")) -> Tensor:
         """(pop,) bool: the tree is defined and bounded on the whole box -- its root can not be a NaN, both root bounds are finite and
         neither exceeds ``max_abs`` in magnitude (``SR_intervals``)"""
-        lo, hi, flags = self.SR_intervals(lower, upper)
-        lo, hi = lo[:, 0], hi[:, 0]
-        return (flags[:, 0] == 0) & torch.isfinite(lo) & torch.isfinite(hi) & (torch.maximum(lo.abs(), hi.abs()) <= max_abs)
+        return _root_safe(*self.SR_intervals(lower, upper), max_abs)
 
     # ---- derivative bounds --------------------------------------------------------------------
     def _wrt(self, wrt):
@@ -592,9 +553,8 @@ class Forest:
                 raise ValueError(f"wrt holds variable {v}, but the trees have variables 0 .. {self.input_len - 1}")
         return idx
 
-    def _derivative_op(self, lower, upper, idx):
-        if self.output_len != 1:
-            raise ValueError(f"derivative bounds work on single-output trees only, but output_len is {self.output_len}")
+    def _derivative_op(self, what: str, lower, upper, idx):
+        self._single_output(what, ValueError)
         lower, upper = self._box(lower, upper)
         wrt = torch.tensor(idx, dtype=torch.int32).to(self.batch_node_value.device)
         return torch.ops.evogp_hip.tree_derivative_intervals(*self._tensors(), lower, upper, wrt)
@@ -609,28 +569,15 @@ class Forest:
         subtree without it has exactly [0, 0]).  Where bit 0 is clear and the subtree is safe (``SR_intervals``), ``dlo >= 0`` proves
         it nondecreasing and ``dhi <= 0`` nonincreasing.  The box is checked as in ``SR_intervals``; ``ValueError`` for an index
         outside [0, input_len), an empty ``wrt`` or a multi-output forest."""
-        return tuple(self._derivative_op(lower, upper, self._wrt(wrt))[3:])
+        return tuple(self._derivative_op("SR_derivative_intervals", lower, upper, self._wrt(wrt))[3:])
 
     def monotone_mask(self, lower, upper, constraints, max_abs: float = float("inf")) -> Tensor:
         """(pop,) bool: the tree is safe on the box (``safe_mask``'s rule on the enclosure of its real value) and obeys every
         constraint of ``{variable: +1 | -1 | (dmin, dmax)}``: the bounds of its partial derivative in that variable lie within
         [0, +inf], [-inf, 0] or [dmin, dmax] and it is known to be continuous in it.  One call of the op."""
-        idx, want = [], []
-        for v, c in dict(constraints).items():
-            if isinstance(c, (tuple, list)):
-                dmin, dmax = float(c[0]), float(c[1])
-                if not dmin <= dmax:
-                    raise ValueError(f"the derivative bounds of variable {v} must satisfy dmin <= dmax, but got {c!r}")
-            elif c in (1, -1):
-                dmin, dmax = (0.0, float("inf")) if c == 1 else (float("-inf"), 0.0)
-            else:
-                raise ValueError(f"a constraint must be +1, -1 or a (dmin, dmax) pair, but variable {v} has {c!r}")
-            idx.append(v)
-            want.append((dmin, dmax))
-        idx = self._wrt(idx)
-        vlo, vhi, vfl, dlo, dhi, dfl = self._derivative_op(lower, upper, idx)
-        vlo, vhi = vlo[:, 0], vhi[:, 0]
-        ok = (vfl[:, 0] == 0) & torch.isfinite(vlo) & torch.isfinite(vhi) & (torch.maximum(vlo.abs(), vhi.abs()) <= max_abs)
+        idx, want, _ = parse_monotonic(constraints)
+        vlo, vhi, vfl, dlo, dhi, dfl = self._derivative_op("monotone_mask", lower, upper, self._wrt(idx))
+        ok = _root_safe(vlo, vhi, vfl, max_abs)
         for k, (dmin, dmax) in enumerate(want):
             ok = ok & ((dfl[k, :, 0] & 3) == 0) & (dlo[k, :, 0] >= dmin) & (dhi[k, :, 0] <= dmax)
         return ok
@@ -647,8 +594,7 @@ class Forest:
         consistent assignment, ``tree.utils.str_unit`` prints a row; ``flags`` (pop, max_tree_len) uint8: 1 = the node is free,
         2 = violation, 4 = malformed row, 8 = the root's unit is not the label's.  ``ValueError`` for an exponent that is no multiple
         of 1/25200 or beyond 2^24 / 25200 in magnitude, a wrong shape, or a multi-output forest."""
-        if self.output_len != 1:
-            raise ValueError(f"SR_dimensions works on single-output trees only, but output_len is {self.output_len}")
+        self._single_output("SR_dimensions", ValueError)
         var, label, check_root = check_units(input_units, label_units, self.input_len)   # int numerators over 25200
         dev = self.batch_node_value.device
         return torch.ops.evogp_hip.tree_dimensions(*self._tensors(), torch.tensor(var, dtype=torch.int32).to(dev),

@@ -105,6 +105,23 @@ def randint(size, low, high, dtype=torch.int32, device=None, requires_grad=False
     return (low + u * (high - low)).to(dtype=dtype)
 
 
+def draw_keys(device=None) -> torch.Tensor:
+    """the two 32-bit keys of a generation launch, from torch's generator of ``device`` (forest.py:51-58)"""
+    device = default_device() if device is None else device
+    try:
+        return torch.randint(low=0, high=1000000, size=(2,), dtype=torch.uint32, device=device)
+    except RuntimeError:  # back ends without a uint32 randint
+        return torch.randint(0, 1000000, (2,), device=device).to(torch.uint32)
+
+
+def box_side(bound, n: int) -> torch.Tensor:
+    """one side of a box of inputs -- a float for all ``n`` variables, or one value each -- as a flat float32 tensor on the host (the
+    caller checks its length)"""
+    if isinstance(bound, (int, float)):
+        return torch.full((n,), float(bound), dtype=torch.float32)
+    return torch.as_tensor(bound).detach().to("cpu", torch.float32).reshape(-1)
+
+
 def str_tree(value, node_type, subtree_size) -> str:
     """Prefix listing of the live nodes of one tree."""
     out = []
@@ -172,6 +189,29 @@ def check_units(input_units, label_units, input_len: int):
     if not (flat(label) and len(label) == K):
         raise ValueError(f"label_units should hold {K} exponents, one for each base dimension of input_units")
     return var, label, label_units is not None
+
+
+def parse_monotonic(constraints, input_len=None):
+    """``{variable: +1 | -1 | (dmin, dmax)}`` -> ``(variables, bounds, signs)``, three lists in the dictionary's order: the keys, the
+    admissible range of the partial derivative as a pair of floats ([0, inf] for +1, [-inf, 0] for -1) and the sign itself (0 for a
+    pair).  ``ValueError`` for any other constraint.  ``input_len``: also hold every key to an int in [0, input_len) and the
+    dictionary to at least one entry; without it the caller checks the variables (``Forest._wrt``)."""
+    variables, bounds, signs = [], [], []
+    for v, c in dict(constraints).items():
+        if input_len is not None and (not isinstance(v, int) or not 0 <= v < input_len):
+            raise ValueError(f"monotonic names variable {v!r}, but the inputs are 0 .. {input_len - 1}")
+        pair = isinstance(c, (tuple, list))
+        if pair and len(c) == 2 and float(c[0]) <= float(c[1]):
+            bounds.append((float(c[0]), float(c[1])))
+        elif not pair and c in (1, -1):
+            bounds.append((0.0, float("inf")) if c == 1 else (float("-inf"), 0.0))
+        else:
+            raise ValueError(f"a monotonic constraint must be +1, -1 or a (dmin, dmax) pair with dmin <= dmax, but variable {v} has {c!r}")
+        variables.append(v)
+        signs.append(0 if pair else int(c))
+    if input_len is not None and not variables:
+        raise ValueError("monotonic must constrain at least one variable")
+    return variables, bounds, signs
 
 
 def str_unit(unit, names=None) -> str:
