@@ -77,6 +77,7 @@ PROTOTYPES = {
     "evogp_hip_tree_intervals": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_tree_derivative_intervals": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_tree_dimensions": [_u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "evogp_hip_tree_structure": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 # include/evogp_hip_debug.h: measurement and test hooks (bench.py, scripts/, tests/); nothing in this package calls them

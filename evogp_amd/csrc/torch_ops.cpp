@@ -570,6 +570,38 @@ std::tuple<Tensor, Tensor, Tensor> tree_dimensions(const Tensor &value, const Te
     return {units, flags, violations};
 }
 
+// (complexity int32, height int16, depth int16, each (pop, gp_len); nest uint8 (pop, gp_len, R); flags uint8 (pop, gp_len); violations
+// int32 (pop,)): the structural pass under cost (32,), operand_limit (32, 3) and R <= 8 nesting rules (rule_outer, rule_inner, rule_limit,
+// (R,) each; R == 0: empty tensors); max_depth, max_complexity: -1 for none (evogp_hip_tree_structure)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_structure(const Tensor &value, const Tensor &type, const Tensor &size,
+                                                                        const Tensor &cost, const Tensor &operand_limit,
+                                                                        const Tensor &rule_outer, const Tensor &rule_inner,
+                                                                        const Tensor &rule_limit, int64_t max_depth, int64_t max_complexity) {
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(cost, {EVOGP_STRUCT_SYMBOLS}, "cost", f.dev, at::kInt);
+    check_tensor(operand_limit, {EVOGP_STRUCT_SYMBOLS, 3}, "operand_limit", f.dev, at::kInt);
+    TORCH_CHECK(rule_outer.dim() == 1 && rule_outer.size(0) <= EVOGP_STRUCT_MAX_RULES, "rule_outer must be a (R,) tensor with 0 <= R <= ",
+                EVOGP_STRUCT_MAX_RULES, ", but got shape ", rule_outer.sizes());
+    const int64_t R = rule_outer.size(0);
+    check_tensor(rule_outer, {R}, "rule_outer", f.dev, at::kInt);
+    check_tensor(rule_inner, {R}, "rule_inner", f.dev, at::kInt);
+    check_tensor(rule_limit, {R}, "rule_limit", f.dev, at::kInt);
+    TORCH_CHECK(max_depth >= -1 && max_depth <= 0x7FFFFFFF, "max_depth must be -1 (none) or >= 0, but got ", max_depth);
+    TORCH_CHECK(max_complexity >= -1 && max_complexity <= 0x7FFFFFFF, "max_complexity must be -1 (none) or >= 0, but got ", max_complexity);
+    c10::DeviceGuard guard(f.dev);
+    Tensor complexity = empty({f.pop, f.gp_len}, at::kInt, f.dev), height = empty({f.pop, f.gp_len}, at::kShort, f.dev);
+    Tensor depth = empty({f.pop, f.gp_len}, at::kShort, f.dev), nest = empty({f.pop, f.gp_len, R}, at::kByte, f.dev);
+    Tensor flags = empty({f.pop, f.gp_len}, at::kByte, f.dev), violations = empty({f.pop}, at::kInt, f.dev);
+    check_rc(evogp_hip_tree_structure((unsigned)f.pop, (unsigned)f.gp_len, (unsigned)R, f.value, f.type, f.size, cost.data_ptr<int>(),
+                                      operand_limit.data_ptr<int>(), R ? rule_outer.data_ptr<int>() : nullptr,
+                                      R ? rule_inner.data_ptr<int>() : nullptr, R ? rule_limit.data_ptr<int>() : nullptr, (int)max_depth,
+                                      (int)max_complexity, complexity.data_ptr<int>(), height.data_ptr<int16_t>(), depth.data_ptr<int16_t>(),
+                                      R ? nest.data_ptr<uint8_t>() : nullptr, flags.data_ptr<uint8_t>(), violations.data_ptr<int>(),
+                                      current_stream(f.dev)),
+             "tree_structure");
+    return {complexity, height, depth, nest, flags, violations};
+}
+
 // int32[pop]: the smallest tree index whose row equals row t (evogp_hip_tree_classes); `hash` decides which rows are compared; the
 // workspace comes from torch's caching allocator
 Tensor tree_classes(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &hash) {
@@ -1088,6 +1120,8 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
     m.def("tree_derivative_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper, Tensor wrt) -> (Tensor vlo, Tensor vhi, Tensor vflags, Tensor dlo, Tensor dhi, Tensor dflags)");
     m.def("tree_dimensions(Tensor value, Tensor node_type, Tensor subtree_size, Tensor var_units, Tensor label_units, bool check_root) -> (Tensor units, Tensor flags, Tensor violations)");
+    m.def("tree_structure(Tensor value, Tensor node_type, Tensor subtree_size, Tensor cost, Tensor operand_limit, Tensor rule_outer, Tensor rule_inner, Tensor rule_limit, int max_depth, int max_complexity)"
+          " -> (Tensor complexity, Tensor height, Tensor depth, Tensor nest, Tensor flags, Tensor violations)");
 }
 
 TORCH_LIBRARY_IMPL(evogp_hip, CompositeExplicitAutograd, m) { m.impl("random_words", &random_words); }  // no tensor argument to dispatch on
@@ -1132,4 +1166,5 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_intervals", &tree_intervals);
     m.impl("tree_derivative_intervals", &tree_derivative_intervals);
     m.impl("tree_dimensions", &tree_dimensions);
+    m.impl("tree_structure", &tree_structure);
 }

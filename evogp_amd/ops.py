@@ -9,7 +9,7 @@ reference's extension module does (src/evogp/tree/__init__.py:2, torch_wrapper.c
   ``CUDA`` key; there is deliberately no CPU implementation (the reference has none, torch_wrapper.cu:301) and no fallback;
 * the extra ops of this engine in the ``evogp_hip`` namespace (no counterpart in the reference).  The list lives in
   csrc/torch_ops.cpp, one schema per op in its ``TORCH_LIBRARY(evogp_hip)`` block; evogp_amd/tree/forest.py says which
-  method calls which.  The five functions below spell out five of them for callers that hold raw tensors, not a Forest.
+  method calls which.  The six functions below spell out six of them for callers that hold raw tensors, not a Forest.
 
 Every implementation validates like the reference's wrapper, allocates its outputs and calls the C ABI of
 include/evogp_hip.h (``libevogp_hip.so``, loaded by ``_lib``) on torch's current stream; no Python runs per call.
@@ -57,6 +57,18 @@ def tree_dimensions(value, node_type, subtree_size, var_units, label_units, chec
     (of a consistent tree: under one consistent assignment of units to its constants); ``flags`` uint8 (pop, gp_len): 1 = free, 2 =
     violation, 4 = the row is malformed, 8 = root mismatch; ``violations`` int32 (pop,): 0 = consistent, -1 = malformed"""
     return torch.ops.evogp_hip.tree_dimensions(value, node_type, subtree_size, var_units, label_units, check_root)
+
+
+def tree_structure(value, node_type, subtree_size, cost, operand_limit, rule_outer, rule_inner, rule_limit, max_depth, max_complexity):
+    """``(complexity, height, depth, nest, flags, violations)``: ``torch.ops.evogp_hip.tree_structure`` (csrc/sr_structure.hip), the
+    structural pass over every single-output tree.  int32 tensors on the forest's device: ``cost`` ``(32,)`` per symbol (function ids
+    0 .. 28, 29 = variable, 30 = constant, 31 = unknown id), each in [0, 65535]; ``operand_limit`` ``(32, 3)``, -1 = none; ``rule_outer``,
+    ``rule_inner`` ``(R,)`` sets of symbols (bit s = symbol s) and ``rule_limit`` ``(R,)`` in [0, 254], ``0 <= R <= 8``
+    (``tree.utils.parse_structure`` makes them from dictionaries); ``max_depth``, ``max_complexity``: -1 = none.  ``complexity`` int32,
+    ``height`` and ``depth`` int16, each (pop, gp_len); ``nest`` uint8 (pop, gp_len, R); ``flags`` uint8 (pop, gp_len): 1 = nesting, 2 =
+    operand, 4 = the row is malformed, 8 = depth, 16 = complexity; ``violations`` int32 (pop,): 0 = passes, -1 = malformed"""
+    return torch.ops.evogp_hip.tree_structure(value, node_type, subtree_size, cost, operand_limit, rule_outer, rule_inner, rule_limit,
+                                              max_depth, max_complexity)
 
 
 def tree_SR_semantic_hash(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables):

@@ -11,7 +11,7 @@ import torch
 from torch import Tensor
 
 from ..tree import Forest, default_device
-from ..tree.utils import DIM_DEN, box_side, check_units, parse_monotonic
+from ..tree.utils import DIM_DEN, box_side, check_units, parse_monotonic, parse_structure
 from .base import BaseProblem
 
 _MODES = ["torch", "hybrid parallel", "data parallel", "tree parallel", "auto"]
@@ -24,7 +24,9 @@ class SymbolicRegression(BaseProblem):
                  const_step_size: float = 0.1, simplify_every: int = 0, const_opt_method: str = "descent",
                  dedup: bool = False, linear_scaling: bool = False, interval_check: bool = False, input_bounds="data",
                  input_margin: float = 0.0, monotonic=None, multigene: bool = False, input_units=None, label_units=None,
-                 dimension_penalty: Optional[float] = None, semantic_dedup: bool = False, semantic_keep: str = "smallest"):
+                 dimension_penalty: Optional[float] = None, semantic_dedup: bool = False, semantic_keep: str = "smallest",
+                 max_depth: Optional[int] = None, max_complexity: Optional[int] = None, complexity_of=None, nested_constraints=None,
+                 operand_constraints=None, structure_penalty: Optional[float] = None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -66,7 +68,17 @@ class SymbolicRegression(BaseProblem):
         its value bit for bit, so each behaviour competes once -- under ``semantic_keep="smallest"`` as its smallest tree, under
         ``"first"`` as its first.  ``semantic_classes(forest)`` returns the classes, also with ``semantic_dedup=False``.  With
         ``linear_scaling`` the UNSCALED predictions are compared: trees that are equal only up to an affine map (``x0`` and
-        ``2 * x0 + 1``, which linear scaling scores alike) are NOT merged.  ``ValueError`` with ``multigene``."""
+        ``2 * x0 + 1``, which linear scaling scores alike) are NOT merged.  ``ValueError`` with ``multigene``.
+        ``max_depth``, ``max_complexity``, ``nested_constraints``, ``operand_constraints`` (structural constraints; single-output
+        problems): the limits of ``Forest.SR_structure`` -- the nodes on the longest path from the root to a leaf, the summed cost of
+        the tree's nodes under ``complexity_of={name: cost}`` (1 where not given), ``{"sin": {"sin": 0, "cos": 0}}`` no sine or cosine
+        inside a sine, ``{"pow": (-1, 1)}`` an exponent of complexity 1 at most.  They are parsed and checked here.
+        ``structure_penalty=None``: a tree that breaks a limit gets NaN from ``evaluate`` and -inf from ``scores`` (on top of the other
+        masks), the others keep their values bit for bit; ``structure_penalty=p`` with ``p >= 0``: its fitness falls by ``p`` times the
+        number of violations instead (a malformed row still gets NaN / -inf).  ``structure(forest)`` and ``structure_mask(forest)``
+        return the pass and who obeys; ``complexity(forest)`` the (pop,) complexity under ``complexity_of``, with or without a limit --
+        the signature ``NSGA2Selection(complexity=, max_complexity=)`` takes.  ``ValueError`` with ``multigene``, and for
+        ``structure_penalty`` without one of the four limits."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -85,7 +97,7 @@ class SymbolicRegression(BaseProblem):
             assert func is not None and num_inputs is not None, (
                 "func and num_inputs, must be provided when datapoints and labels are not provided")
             self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
-        # the checks fire in this order: scaling, interval, monotonic, multigene, units, semantic_keep, semantic_dedup
+        # the checks fire in this order: scaling, interval, monotonic, multigene, units, semantic_keep, semantic_dedup, structure
         if self.linear_scaling:
             self._one_label_column("linear_scaling")
         self.interval_check = bool(interval_check)
@@ -132,7 +144,27 @@ class SymbolicRegression(BaseProblem):
             if self.multigene:
                 raise ValueError("multigene cannot be combined with semantic_dedup: semantic classes compare single-output trees")
             self._one_label_column("semantic_dedup")
-        self._constrained = self._box_check or self.input_units is not None or self.semantic_dedup
+        self.max_depth, self.max_complexity, self.structure_penalty = None, None, None
+        self._structural = any(o is not None for o in (max_depth, max_complexity, nested_constraints, operand_constraints))
+        if self._structural or complexity_of is not None:
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with structural constraints: that pass works on single-output trees")
+            self._one_label_column("structural constraints")
+        if structure_penalty is not None:
+            if not self._structural:
+                raise ValueError("structure_penalty needs max_depth, max_complexity, nested_constraints or operand_constraints")
+            if isinstance(structure_penalty, bool) or not float(structure_penalty) >= 0.0:
+                raise ValueError(f"structure_penalty should be None or a float >= 0, but got {structure_penalty!r}")
+            self.structure_penalty = float(structure_penalty)
+        for name, m in (("max_depth", max_depth), ("max_complexity", max_complexity)):
+            if m is not None:
+                if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m < 2 ** 31:
+                    raise ValueError(f"{name} should be None or an int >= 0, but got {m!r}")
+                setattr(self, name, m)
+        # parsed here, on the host, so that an unknown name or a limit out of range fails at construction
+        self._structure_tables = parse_structure(complexity_of, nested_constraints, operand_constraints)
+        self._cost_tables = (self._structure_tables[0], parse_structure()[1], [])   # complexity(): the costs, no limits
+        self._constrained = self._box_check or self.input_units is not None or self.semantic_dedup or self._structural
 
     def _one_label_column(self, feature: str, claim: str = "works on single-output problems only"):
         if self.labels.dim() != 2 or self.labels.shape[1] != 1:
@@ -173,6 +205,23 @@ class SymbolicRegression(BaseProblem):
         """(pop,) bool: the tree is dimensionally consistent under this problem's units (``dimensions``: ``violations == 0``)"""
         return self.dimensions(forest)[2] == 0
 
+    def structure(self, forest: Forest):
+        """``(complexity, height, depth, nest, flags, violations)``: ``Forest.SR_structure`` under this problem's structural options"""
+        if not self._structural:
+            raise ValueError("this problem has no structural constraints")
+        forest._single_output("structure", ValueError)
+        return forest._structure_op(self._structure_tables, self.max_depth, self.max_complexity)
+
+    def structure_mask(self, forest: Forest) -> Tensor:
+        """(pop,) bool: the tree obeys this problem's structural constraints (``structure``: ``violations == 0``)"""
+        return self.structure(forest)[5] == 0
+
+    def complexity(self, forest: Forest) -> Tensor:
+        """(pop,) int32: the complexity of every tree under this problem's ``complexity_of`` (the tree size without it; 0 for a
+        malformed row).  The signature ``NSGA2Selection(complexity=)`` takes."""
+        forest._single_output("complexity", ValueError)
+        return forest._structure_op(self._cost_tables)[0][:, 0]
+
     def semantic_classes(self, forest: Forest, keep: Optional[str] = None):
         """``(class_id, is_representative)``: ``Forest.semantic_classes`` on this problem's datapoints; ``keep``: None takes the
         problem's ``semantic_keep``.  The signature ``GeneticProgramming(duplicate_classes=)`` takes."""
@@ -186,13 +235,18 @@ class SymbolicRegression(BaseProblem):
             box = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
             box = box.to(fitness.device)
             mask = box if mask is None else mask & box
+        counted = []   # (violations, penalty) of the passes that count violations
         if self.input_units is not None:
-            viol = self.dimensions(forest)[2].to(fitness.device)
-            if self.dimension_penalty is None:
+            counted.append((self.dimensions(forest)[2], self.dimension_penalty))
+        if self._structural:
+            counted.append((self.structure(forest)[5], self.structure_penalty))
+        for viol, penalty in counted:
+            viol = viol.to(fitness.device)
+            if penalty is None:
                 ok = viol == 0
             else:   # (a malformed row, -1, is treated as in the hard case)
                 ok = viol >= 0
-                fitness = torch.where(viol > 0, fitness - self.dimension_penalty * viol.to(fitness.dtype), fitness)
+                fitness = torch.where(viol > 0, fitness - penalty * viol.to(fitness.dtype), fitness)
             mask = ok if mask is None else mask & ok
         return torch.where(mask, fitness, torch.full_like(fitness, fill))
 

@@ -19,6 +19,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
+    structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
     genetic operators     mutate, crossover
     container, pickling   indexing, iteration, ``+``, ``__getstate__`` / ``__setstate__``
 
@@ -38,7 +39,7 @@ from torch import Tensor
 from . import utils as _utils
 from .descriptor import GenerateDescriptor
 from .tree import Tree
-from .utils import NType, box_side, check_tensor, check_units, draw_keys, parse_monotonic
+from .utils import NType, box_side, check_tensor, check_units, draw_keys, parse_monotonic, parse_structure
 
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
@@ -603,6 +604,52 @@ class Forest:
     def dimension_mask(self, input_units, label_units=None) -> Tensor:
         """(pop,) bool: the tree is dimensionally consistent (``SR_dimensions``: ``violations == 0``)"""
         return self.SR_dimensions(input_units, label_units)[2] == 0
+
+    # ---- structural constraints -----------------------------------------------------------------
+    def SR_structure(self, complexity_of=None, nested_constraints=None, operand_constraints=None, max_depth=None, max_complexity=None):
+        """``(complexity, height, depth, nest, flags, violations)``: the structural pass over every tree (csrc/sr_structure.hip, one lane
+        per tree, no dataset, no host synchronisation beyond the conversion of the tables).  The three dictionaries are
+        ``tree.utils.parse_structure``'s: ``complexity_of={"sin": 3}`` the cost of one node (1 where not given),
+        ``nested_constraints={"sin": {"sin": 0, "cos": 0}}`` at most ``limit`` inner nodes on any path below an outer node (R rules,
+        one per pair, at most 8), ``operand_constraints={"pow": (-1, 1)}`` the largest complexity of each operand.  ``max_depth``: the
+        largest number of nodes on a path from the root to a leaf (a single leaf has 1), ``max_complexity``: the largest complexity of
+        the tree; None for no limit.  ``complexity`` (pop, max_tree_len) int32: the summed cost of every subtree (with unit costs its
+        size); ``height`` int16: nodes on the longest path down from the node; ``depth`` int16: edges up to the root; ``nest`` (pop,
+        max_tree_len, R) uint8: the inner nodes of rule r on the fullest path from the node down, the node included, saturating at
+        255; ``flags`` uint8: 1 = a nesting rule fails at this node, 2 = an operand of this node is too complex, 4 = malformed row,
+        8 = too deep (node 0), 16 = too complex (node 0); ``violations`` (pop,) int32: the nodes with flag 1 or 2, plus one each for
+        8 and 16; 0 = the tree passes, -1 = malformed row.  ``ValueError`` for what ``parse_structure`` refuses, a limit that is no
+        int >= 0, or a multi-output forest."""
+        self._single_output("SR_structure", ValueError)
+        return self._structure_op(parse_structure(complexity_of, nested_constraints, operand_constraints), max_depth, max_complexity)
+
+    def _structure_op(self, tables, max_depth=None, max_complexity=None):
+        """the op under ``parse_structure``'s tables"""
+        limits = []
+        for name, m in (("max_depth", max_depth), ("max_complexity", max_complexity)):
+            if m is not None and (isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) < 2 ** 31):
+                raise ValueError(f"{name} should be None or an int >= 0, but got {m!r}")
+            limits.append(-1 if m is None else int(m))
+        cost, operand_limit, rules = tables
+        dev = self.batch_node_value.device
+
+        def words(x, shape):   # (a set that holds symbol 31 is a negative int32 word)
+            return torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in x], dtype=torch.int32).reshape(shape).to(dev)
+
+        return torch.ops.evogp_hip.tree_structure(
+            *self._tensors(), words(cost, (32,)), words([l for row in operand_limit for l in row], (32, 3)),
+            words([r[0] for r in rules], (len(rules),)), words([r[1] for r in rules], (len(rules),)),
+            words([r[2] for r in rules], (len(rules),)), *limits)
+
+    def structure_mask(self, complexity_of=None, nested_constraints=None, operand_constraints=None, max_depth=None,
+                       max_complexity=None) -> Tensor:
+        """(pop,) bool: the tree obeys every structural constraint (``SR_structure``: ``violations == 0``)"""
+        return self.SR_structure(complexity_of, nested_constraints, operand_constraints, max_depth, max_complexity)[5] == 0
+
+    def complexity(self, complexity_of=None) -> Tensor:
+        """(pop,) int32: the weighted complexity of every tree (``SR_structure``: ``complexity[:, 0]``; 0 for a malformed row).  With
+        ``complexity_of=None`` the tree size."""
+        return self.SR_structure(complexity_of)[0][:, 0]
 
     # ---- genetic operators --------------------------------------------------------------------
     def mutate(self, replace_pos: Tensor, new_sub_forest: "Forest") -> "Forest":

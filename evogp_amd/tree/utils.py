@@ -191,6 +191,72 @@ def check_units(input_units, label_units, input_len: int):
     return var, label, label_units is not None
 
 
+# ---- structural constraints (csrc/sr_structure.hip) ----
+STRUCT_SYMBOLS = 32        # EVOGP_STRUCT_SYMBOLS: the function ids 0 .. 28, then
+STRUCT_NAMES = FUNCS_NAMES + ["var", "const", "unknown"]   # 29 a variable, 30 a constant, 31 a function node with an unknown id
+STRUCT_MAX_RULES = 8       # EVOGP_STRUCT_MAX_RULES
+STRUCT_MAX_COST = 65535    # of one node
+STRUCT_MAX_NEST = 254      # the largest limit of a nesting rule (the counters saturate at 255)
+STRUCT_MAX_OPERAND = (1 << 31) - 1
+
+
+def _struct_symbol(name, what: str) -> int:
+    if not isinstance(name, str) or name not in STRUCT_NAMES:
+        raise ValueError(f"{what} names {name!r}, but the symbols are {STRUCT_NAMES}")
+    return STRUCT_NAMES.index(name)
+
+
+def _struct_int(x, lo: int, hi: int, what: str) -> int:
+    import numbers
+
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not lo <= int(x) <= hi:
+        raise ValueError(f"{what} should be an int in [{lo}, {hi}], but got {x!r}")
+    return int(x)
+
+
+def parse_structure(complexity_of=None, nested_constraints=None, operand_constraints=None):
+    """Dictionaries -> ``(cost, operand_limit, rules)``, the host tables of ``Forest.SR_structure``: ``cost`` 32 ints, ``operand_limit``
+    32 rows of 3 ints (-1: none) and ``rules`` a list of ``(outer_mask, inner_mask, limit)`` with the masks as sets of symbols (bit s).
+    The keys are ``FUNCS_NAMES`` plus ``"var"``, ``"const"`` and ``"unknown"`` (a function node whose id is none of its class).
+    ``complexity_of={"sin": 3, "const": 2}``: the cost of one node, 1 where not given, each in [0, 65535].
+    ``nested_constraints={"sin": {"sin": 0, "cos": 0}, "pow": {"pow": 1}}``: one rule per (outer, inner) pair -- on every path below an
+    ``outer`` node at most ``limit`` (0 .. 254) ``inner`` nodes; at most 8 rules.
+    ``operand_constraints={"pow": (-1, 1), "sin": 5}``: the largest complexity of each operand, -1 for none -- an int for a unary
+    function, a tuple of the function's arity otherwise (``"unknown"``: an int or a tuple of 1 or 2).
+    ``ValueError`` for an unknown name, a bool or another non-int, a value outside its range, a tuple of the wrong arity, a leaf in
+    ``operand_constraints``, or more than 8 rules."""
+    cost = [1] * STRUCT_SYMBOLS
+    for name, c in dict(complexity_of or {}).items():
+        cost[_struct_symbol(name, "complexity_of")] = _struct_int(c, 0, STRUCT_MAX_COST, f"the cost of {name!r}")
+    rules = []
+    for outer, inners in dict(nested_constraints or {}).items():
+        so = _struct_symbol(outer, "nested_constraints")
+        if not isinstance(inners, dict):
+            raise ValueError(f"nested_constraints[{outer!r}] should be a dictionary {{inner: limit}}, but got {inners!r}")
+        for inner, limit in inners.items():
+            si = _struct_symbol(inner, f"nested_constraints[{outer!r}]")
+            rules.append((1 << so, 1 << si, _struct_int(limit, 0, STRUCT_MAX_NEST, f"the limit of {inner!r} inside {outer!r}")))
+    if len(rules) > STRUCT_MAX_RULES:
+        raise ValueError(f"nested_constraints holds {len(rules)} (outer, inner) pairs, but at most {STRUCT_MAX_RULES} rules are supported")
+    operand_limit = [[-1, -1, -1] for _ in range(STRUCT_SYMBOLS)]
+    for name, lim in dict(operand_constraints or {}).items():
+        s = _struct_symbol(name, "operand_constraints")
+        if s in (STRUCT_NAMES.index("var"), STRUCT_NAMES.index("const")):
+            raise ValueError(f"operand_constraints names {name!r}, which has no operands")
+        arities = (1, 2) if name == "unknown" else (func_arity(s),)
+        if isinstance(lim, (tuple, list)):
+            lims = list(lim)
+        elif 1 in arities:
+            lims = [lim]
+        else:
+            raise ValueError(f"operand_constraints[{name!r}] should be a tuple of {arities[0]} limits, but got {lim!r}")
+        if len(lims) not in arities:
+            raise ValueError(f"operand_constraints[{name!r}] should hold {' or '.join(map(str, arities))} limits, but got {len(lims)}")
+        for k, l in enumerate(lims):
+            operand_limit[s][k] = _struct_int(l, -1, STRUCT_MAX_OPERAND, f"the limit of operand {k} of {name!r}")
+    return cost, operand_limit, rules
+
+
 def parse_monotonic(constraints, input_len=None):
     """``{variable: +1 | -1 | (dmin, dmax)}`` -> ``(variables, bounds, signs)``, three lists in the dictionary's order: the keys, the
     admissible range of the partial derivative as a pair of floats ([0, inf] for +1, [-inf, 0] for -1) and the sign itself (0 for a

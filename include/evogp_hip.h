@@ -526,6 +526,40 @@ int evogp_hip_tree_dimensions(unsigned pop, unsigned gp_len, unsigned var_len, u
                               const int16_t *size, const int *var_units, const int *label_units, int check_root, int *units,
                               unsigned char *flags, int *violations, evogp_stream_t stream);
 
+/* Structural constraints over single-output trees (depth, weighted complexity, operand limits, nesting limits; no counterpart in the
+ * reference; csrc/sr_structure.hip).  Every live node has a symbol in [0, EVOGP_STRUCT_SYMBOLS): the function ids 0 .. 28 (a ternary-typed
+ * node is IF, 0, whatever its id), EVOGP_STRUCT_SYM_VAR, EVOGP_STRUCT_SYM_CONST, and EVOGP_STRUCT_SYM_UNKNOWN for a unary or binary node
+ * whose id is no function of its class.  Bottom-up: complexity[t][i] = cost[s_i] + the children's; height[t][i] = 1 + the largest child
+ * height (a leaf: 1); for rule r, below = the largest nest[..][r] of the children and nest[t][i][r] = min(255, below + [s_i in
+ * rule_inner[r]]); node i gets EVOGP_STRUCT_NEST when s_i is in rule_outer[r] and below > rule_limit[r] for some r, and
+ * EVOGP_STRUCT_OPERAND when operand_limit[s_i][k] >= 0 and the complexity of operand k exceeds it (operand order as the interpreters').
+ * Node 0 gets EVOGP_STRUCT_DEPTH when max_depth >= 0 and height[t][0] > max_depth, EVOGP_STRUCT_COMPLEXITY when max_complexity >= 0 and
+ * complexity[t][0] > max_complexity.  Top-down: depth[t][0] = 0, a child's depth is its parent's + 1.  violations[t] = the nodes with
+ * NEST or OPERAND (each once) + [DEPTH] + [COMPLEXITY].  The complete rule set is the integer restatement tests/structure_ref.py, which
+ * the kernel reproduces word for word.  A malformed row (evogp_hip_tree_intervals's rule) has flags EVOGP_STRUCT_MALFORMED on every live
+ * word (on word 0 when it has none), 0 in every other output and violations = -1.  Words past the live prefix are 0 in every output.
+ * cost: int32[32], each in [0, 65535]; operand_limit: int32[32][3], -1 for none; rule_outer, rule_inner: int32[n_rules], sets of symbols
+ * (bit s = symbol s); rule_limit: int32[n_rules], each in [0, 254] -- on the device, the caller checks the ranges; the three rule
+ * pointers and nest may be null only when n_rules == 0, and nest must then be 8-byte aligned (EVOGP_E_BADARG otherwise: the counters of
+ * a node are accessed as one word); n_rules <= EVOGP_STRUCT_MAX_RULES; max_depth, max_complexity: -1 for none.
+ * complexity: int32[pop][gp_len], height, depth: int16[pop][gp_len], nest: uint8[pop][gp_len][n_rules], flags: uint8[pop][gp_len],
+ * violations: int32[pop].  One lane per tree, both passes in one launch, no dataset, no workspace, no atomics, nothing synchronises
+ * with the host; bit-identical from run to run.  Any gp_len <= 1024.  The outputs must not alias the inputs or one another. */
+#define EVOGP_STRUCT_SYMBOLS 32
+#define EVOGP_STRUCT_SYM_VAR 29
+#define EVOGP_STRUCT_SYM_CONST 30
+#define EVOGP_STRUCT_SYM_UNKNOWN 31
+#define EVOGP_STRUCT_MAX_RULES 8
+#define EVOGP_STRUCT_NEST 1
+#define EVOGP_STRUCT_OPERAND 2
+#define EVOGP_STRUCT_MALFORMED 4
+#define EVOGP_STRUCT_DEPTH 8
+#define EVOGP_STRUCT_COMPLEXITY 16
+int evogp_hip_tree_structure(unsigned pop, unsigned gp_len, unsigned n_rules, const float *value, const int16_t *type, const int16_t *size,
+                             const int *cost, const int *operand_limit, const int *rule_outer, const int *rule_inner,
+                             const int *rule_limit, int max_depth, int max_complexity, int *complexity, int16_t *height, int16_t *depth,
+                             unsigned char *nest, unsigned char *flags, int *violations, evogp_stream_t stream);
+
 /* Non-replicating batch evaluation (replaces the repeat_interleave + tree_evaluate
  * composition of src/evogp/tree/forest.py:143-176): results[t][d][:] = tree_t(variables[d][:]),
  * variables: f32[D][var_len], results: f32[pop][D][out_len]. */
@@ -706,7 +740,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
