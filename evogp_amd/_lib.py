@@ -72,6 +72,7 @@ PROTOTYPES = {
     "evogp_hip_sr_semantic_classes_workspace_bytes": [_u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_sr_semantic_classes": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_linear_scaling": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_weighted_loss": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _u, _i, C.c_double, _vp, _vp],
     "evogp_hip_sr_gene_fitness": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_wrap_linear":[_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_tree_intervals": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -25,6 +25,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -343,6 +344,36 @@ std::tuple<Tensor, Tensor> tree_SR_linear_scaling(int64_t pop_size, int64_t data
                                          d.type, d.size, d.X, d.y, loss.data_ptr<float>(), coef.data_ptr<float>(), current_stream(d.dev)),
              "tree_SR_linear_scaling");
     return {loss, coef};
+}
+
+// weighted / robust / held-out losses (evogp_hip_sr_weighted_loss): loss (pop, K) for weights (K, D), (pop, 1) without weights
+Tensor tree_SR_weighted_loss(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                             const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
+                             const c10::optional<Tensor> &weights, int64_t loss_kind, double loss_param) {
+    const Dataset d = check_dataset("tree_SR_weighted_loss", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    TORCH_CHECK(loss_kind >= EVOGP_LOSS_MSE && loss_kind <= EVOGP_LOSS_LOGCOSH, "loss_kind must be in range [", EVOGP_LOSS_MSE, ", ",
+                EVOGP_LOSS_LOGCOSH, "], but got ", loss_kind);
+    TORCH_CHECK(loss_param == loss_param, "loss_param must not be NaN");
+    TORCH_CHECK(loss_kind != EVOGP_LOSS_HUBER || (loss_param > 0.0 && loss_param < HUGE_VAL),
+                "loss_param (the delta of the Huber loss) must be finite and larger than 0, but got ", loss_param);
+    TORCH_CHECK(loss_kind != EVOGP_LOSS_PINBALL || (loss_param > 0.0 && loss_param < 1.0),
+                "loss_param (the tau of the pinball loss) must lie in (0, 1), but got ", loss_param);
+    int64_t K = 1;
+    const float *w = nullptr;
+    if (weights.has_value()) {
+        TORCH_CHECK(weights->dim() == 2 && weights->size(0) >= 1 && weights->size(0) <= EVOGP_WLOSS_MAX_WEIGHTS,
+                    "weights must be a (K, data_points) tensor with K in range [1, ", EVOGP_WLOSS_MAX_WEIGHTS, "], but got shape ", weights->sizes());
+        K = weights->size(0);
+        check_tensor(*weights, {K, data_points}, "weights", d.dev, at::kFloat);
+        w = weights->data_ptr<float>();
+    }
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size, K}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_weighted_loss((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
+                                        d.type, d.size, d.X, d.y, w, (unsigned)K, (int)loss_kind, loss_param, loss.data_ptr<float>(),
+                                        current_stream(d.dev)),
+             "tree_SR_weighted_loss");
+    return loss;
 }
 
 // multi-gene fitness (evogp_hip_sr_gene_fitness): loss (pop,), coef (pop, 1 + out_len) = intercept, weights; with_moments: also the
@@ -1111,6 +1142,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor variables, Tensor hash) -> Tensor");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
+    m.def("tree_SR_weighted_loss(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights, int loss_kind, float loss_param) -> Tensor");
     m.def("tree_SR_gene_fitness(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_gene_moments(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
@@ -1160,6 +1193,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_semantic_hash", &tree_SR_semantic_hash);
     m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
+    m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
     m.impl("tree_SR_gene_fitness", &tree_SR_gene_fitness);
     m.impl("tree_SR_gene_moments", &tree_SR_gene_moments);
     m.impl("tree_wrap_linear", &tree_wrap_linear);

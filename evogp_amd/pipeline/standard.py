@@ -21,7 +21,9 @@ class BasePipeline:
 class StandardPipeline(BasePipeline):
     def __init__(self, algorithm: GeneticProgramming, problem: BaseProblem, fitness_target: float = None,
                  generation_limit: int = 100, time_limit: int = None, is_show_details: bool = True,
-                 valid_fitness_boundry: float = 1e8):
+                 valid_fitness_boundry: float = 1e8, validation_patience: int = None):
+        """``validation_patience`` (a problem with a ``validation_mask`` only): ``run`` stops after that many consecutive generations
+        without a new best validation fitness and returns ``best_validation_tree``, not ``best_tree``"""
         self.algorithm = algorithm
         self.problem = problem
         self.fitness_target = fitness_target
@@ -33,6 +35,18 @@ class StandardPipeline(BasePipeline):
         self.best_fitness = float("-inf")
         self.best_coef = None   # a multigene problem: the (1 + G,) coefficients of best_tree's model, on the host
         self.fitness = None
+        if validation_patience is not None:
+            if getattr(problem, "validation_mask", None) is None:
+                raise ValueError("validation_patience needs a problem with a validation_mask")
+            if isinstance(validation_patience, bool) or not isinstance(validation_patience, int) or validation_patience < 1:
+                raise ValueError(f"validation_patience should be None or an int >= 1, but got {validation_patience!r}")
+        self.validation_patience = validation_patience
+        if getattr(problem, "validation_mask", None) is not None:
+            # the tree with the highest score on the held-out rows among the trees whose training score is finite (the smaller index
+            # wins a tie), and the generations since it last changed
+            self.best_validation_tree = None
+            self.best_validation_fitness = float("-inf")
+            self.validation_stale = 0
 
     def step(self):
         """One generation.  Same result as the reference's loop (standard.py:41-52), but nothing waits on the device
@@ -50,6 +64,14 @@ class StandardPipeline(BasePipeline):
             fitness = self.problem.evaluate(forest)
             fitness = torch.where(torch.isnan(fitness), torch.full_like(fitness, float("-inf")), fitness)  # standard.py:43
         self.algorithm.step(fitness)
+        if getattr(self.problem, "validation_mask", None) is not None:
+            held = self.problem.validation_scores(forest, fitness).cpu()   # (the validation column of the pass behind `fitness`)
+            top = held.max()
+            self.validation_stale += 1
+            if top > self.best_validation_fitness:
+                self.best_validation_fitness = top
+                self.best_validation_tree = forest[int(torch.nonzero(held == top)[0])]
+                self.validation_stale = 0
         host = fitness.cpu()
         best = int(torch.argmax(host))
         if host[best] > self.best_fitness:
@@ -79,11 +101,15 @@ class StandardPipeline(BasePipeline):
             if self.time_limit is not None and time.time() - start > self.time_limit:
                 print(f"stopped: {self.time_limit} s time limit")
                 break
+            if self.validation_patience is not None and self.validation_stale >= self.validation_patience:
+                print(f"stopped: no better validation fitness than {float(self.best_validation_fitness):.6g} "
+                      f"for {self.validation_patience} generations")
+                break
             generation += 1
             if generation >= self.generation_limit:
                 print(f"stopped: {self.generation_limit} generations")
                 break
-        return self.best_tree
+        return self.best_tree if self.validation_patience is None else self.best_validation_tree
 
     def show_details(self, tic, generation, fitness):
         b = self.valid_fitness_boundry

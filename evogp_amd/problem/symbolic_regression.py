@@ -11,6 +11,7 @@ import torch
 from torch import Tensor
 
 from ..tree import Forest, default_device
+from ..tree.forest import check_loss
 from ..tree.utils import DIM_DEN, box_side, check_units, parse_monotonic, parse_structure
 from .base import BaseProblem
 
@@ -26,7 +27,9 @@ class SymbolicRegression(BaseProblem):
                  input_margin: float = 0.0, monotonic=None, multigene: bool = False, input_units=None, label_units=None,
                  dimension_penalty: Optional[float] = None, semantic_dedup: bool = False, semantic_keep: str = "smallest",
                  max_depth: Optional[int] = None, max_complexity: Optional[int] = None, complexity_of=None, nested_constraints=None,
-                 operand_constraints=None, structure_penalty: Optional[float] = None):
+                 operand_constraints=None, structure_penalty: Optional[float] = None, loss: Optional[str] = None,
+                 loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
+                 validation_mask: Optional[Tensor] = None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -78,7 +81,17 @@ class SymbolicRegression(BaseProblem):
         number of violations instead (a malformed row still gets NaN / -inf).  ``structure(forest)`` and ``structure_mask(forest)``
         return the pass and who obeys; ``complexity(forest)`` the (pop,) complexity under ``complexity_of``, with or without a limit --
         the signature ``NSGA2Selection(complexity=, max_complexity=)`` takes.  ``ValueError`` with ``multigene``, and for
-        ``structure_penalty`` without one of the four limits."""
+        ``structure_penalty`` without one of the four limits.
+        ``loss``, ``loss_param``, ``sample_weights``, ``validation_mask`` (labels of shape ``(D, 1)``; with all four left at None
+        nothing changes): the loss behind ``evaluate`` / ``scores`` becomes ``Forest.SR_weighted_loss`` -- ``loss`` one of ``"mse"``,
+        ``"mae"``, ``"huber"`` (``loss_param`` = delta), ``"pinball"`` (``loss_param`` = tau) or ``"logcosh"`` (None: what ``use_MSE``
+        says), every row weighted by ``sample_weights`` ``(D,)`` (non-negative, finite, not all 0).  ``validation_mask`` ``(D,)`` bool
+        holds rows out: the same pass scores every tree twice, on the rows where the mask is False -- the loss that is evolved, masked
+        and penalised as before -- and on the rows where it is True, kept on the device as ``last_validation_loss``;
+        ``validation_scores(forest)`` returns the latter as scores, and StandardPipeline tracks ``best_validation_tree`` with it.  A
+        tree need not be defined on a row it is not scored on.  ``ValueError`` together with ``linear_scaling``, ``multigene``,
+        ``const_opt_steps`` > 0 or ``simplify_every`` > 0 (those passes minimise the unweighted MSE / MAE), and from ``evaluate`` /
+        ``scores`` with ``use_MSE=False`` while ``loss`` is set."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -97,7 +110,8 @@ class SymbolicRegression(BaseProblem):
             assert func is not None and num_inputs is not None, (
                 "func and num_inputs, must be provided when datapoints and labels are not provided")
             self.datapoints, self.labels = self.generate_data(func, num_inputs, num_data, lower_bounds, upper_bounds)
-        # the checks fire in this order: scaling, interval, monotonic, multigene, units, semantic_keep, semantic_dedup, structure
+        # the checks fire in this order: scaling, interval, monotonic, multigene, units, semantic_keep, semantic_dedup, structure,
+        # then the loss options: combinations, label shape, loss and loss_param, sample_weights, validation_mask
         if self.linear_scaling:
             self._one_label_column("linear_scaling")
         self.interval_check = bool(interval_check)
@@ -165,6 +179,44 @@ class SymbolicRegression(BaseProblem):
         self._structure_tables = parse_structure(complexity_of, nested_constraints, operand_constraints)
         self._cost_tables = (self._structure_tables[0], parse_structure()[1], [])   # complexity(): the costs, no limits
         self._constrained = self._box_check or self.input_units is not None or self.semantic_dedup or self._structural
+        self.loss, self.loss_param, self.sample_weights, self.validation_mask = loss, loss_param, None, None
+        self.last_validation_loss = None   # (pop,): the loss on the held-out rows, of the forest scored last
+        self._loss_weights = None          # (K, D) float32 on the data's device: what SR_weighted_loss is called with
+        self._own_loss = any(o is not None for o in (loss, loss_param, sample_weights, validation_mask))
+        if self._own_loss:
+            for name, on in (("linear_scaling", self.linear_scaling), ("multigene", self.multigene),
+                             ("const_opt_steps > 0", self.const_opt_steps > 0), ("simplify_every > 0", self.simplify_every > 0)):
+                if on:
+                    raise ValueError(f"loss, loss_param, sample_weights and validation_mask cannot be combined with {name}: "
+                                     "that pass minimises the unweighted mean squared / absolute error")
+            self._one_label_column("loss, loss_param, sample_weights and validation_mask", "work on one label column, (D, 1)")
+            if loss is None and loss_param is not None:
+                raise ValueError(f"loss_param needs a loss, but got loss_param={loss_param!r} alone")
+            if loss is not None:
+                self.loss_param = check_loss(loss, loss_param)
+            dev, D = self.datapoints.device, self.datapoints.shape[0]
+            w = None
+            if sample_weights is not None:
+                if not isinstance(sample_weights, Tensor) or sample_weights.shape != (D,) or not sample_weights.dtype.is_floating_point:
+                    raise ValueError(f"sample_weights should be a ({D},) floating-point tensor, but got "
+                                     f"{tuple(sample_weights.shape) if isinstance(sample_weights, Tensor) else sample_weights!r}")
+                w = sample_weights.detach().to(dev).to(torch.float32)
+                if not bool((torch.isfinite(w) & (w >= 0)).all()) or not float(w.sum()) > 0.0:   # (the one host synchronisation)
+                    raise ValueError("sample_weights should be finite, non-negative and not all 0")
+                self.sample_weights = w
+            if validation_mask is not None:
+                if not isinstance(validation_mask, Tensor) or validation_mask.shape != (D,) or validation_mask.dtype != torch.bool:
+                    raise ValueError(f"validation_mask should be a ({D},) bool tensor, but got "
+                                     f"{(tuple(validation_mask.shape), validation_mask.dtype) if isinstance(validation_mask, Tensor) else validation_mask!r}")
+                m = validation_mask.detach().to(dev)
+                held = int(m.sum())
+                if held == 0 or held == D:
+                    raise ValueError(f"validation_mask should hold some rows out and leave some in, but {held} of {D} are True")
+                self.validation_mask = m
+                ones = torch.ones(D, dtype=torch.float32, device=dev) if w is None else w
+                self._loss_weights = torch.stack([ones * (~m), ones * m]).contiguous()   # training rows, validation rows
+            elif w is not None:
+                self._loss_weights = w[None, :].contiguous()
 
     def _one_label_column(self, feature: str, claim: str = "works on single-output problems only"):
         if self.labels.dim() != 2 or self.labels.shape[1] != 1:
@@ -360,10 +412,59 @@ class SymbolicRegression(BaseProblem):
         return (torch.where(bad, torch.full_like(loss, nan), loss).to(torch.float32),
                 torch.where(bad[:, None], torch.full_like(coef, nan), coef))
 
+    def weighted_loss(self, forest: Forest, loss: str, dedup: Optional[bool] = None) -> Tensor:
+        """``Forest.SR_weighted_loss`` on this problem's data with its ``loss_param`` and weight rows -- ``(pop,)``, or ``(pop, 2)``
+        under a ``validation_mask``: training rows, validation rows -- or under ``execute_mode="torch"`` the same definition from
+        ``batch_forward``'s predictions in float64 torch (which materialises them)"""
+        W = self._loss_weights
+        if self.execute_mode != "torch":
+            return forest.SR_weighted_loss(self.datapoints, self.labels, W if W is None or W.shape[0] > 1 else W[0], loss,
+                                           self.loss_param, dedup=self.dedup if dedup is None else bool(dedup))
+        p = forest.batch_forward(self.datapoints)[:, :, 0]   # (pop, D) float32
+        r = p.to(torch.float64) - self.labels.to(p.device)[:, 0].to(torch.float64)[None, :]
+        a, prm = r.abs(), self.loss_param
+        if loss == "mse":
+            rho = r * r
+        elif loss == "mae":
+            rho = a
+        elif loss == "huber":
+            rho = torch.where(a <= prm, r * r * 0.5, prm * (a - prm * 0.5))
+        elif loss == "pinball":
+            rho = torch.where(-r >= 0, prm * -r, (prm - 1.0) * -r)
+        else:
+            rho = a + torch.log1p(torch.exp(-2.0 * a)) - 0.6931471805599453
+        Wd = torch.ones(1, p.shape[1], dtype=torch.float64, device=p.device) if W is None else W.to(p.device).to(torch.float64)
+        on = (Wd != 0)[None, :, :]   # a row without weight is not looked at
+        s = torch.where(on, Wd[None, :, :] * rho[:, None, :], torch.zeros((), dtype=torch.float64, device=p.device)).sum(2)
+        bad = (on & ~torch.isfinite(p)[:, None, :]).any(2)
+        wsum = Wd.sum(1)
+        usable = (torch.isfinite(Wd) & (Wd >= 0)).all(1) & (wsum != 0)
+        out = torch.where(bad | ~usable[None, :], torch.full_like(s, float("nan")), s / wsum[None, :]).to(torch.float32)
+        return out[:, 0] if W is None or W.shape[0] == 1 else out
+
+    def validation_scores(self, forest: Forest, scores: Optional[Tensor] = None) -> Tensor:
+        """(pop,): minus the loss of every tree on the rows ``validation_mask`` holds out, -inf where it is NaN and wherever the
+        tree's training score is -inf (a tree that fails a constraint is no candidate on any rows).  ``scores``: None scores the
+        forest here; or what ``scores(forest)`` has just returned, and the validation column of that same pass is taken."""
+        if self.validation_mask is None:
+            raise ValueError("this problem has no validation_mask")
+        train = self.scores(forest) if scores is None else scores
+        held = self.last_validation_loss.to(train.device)
+        out = torch.where(torch.isnan(held), torch.full_like(held, float("-inf")), -held)
+        return torch.where(train == float("-inf"), torch.full_like(out, float("-inf")), out)
+
     def _loss(self, forest: Forest, use_MSE: bool):
         """``(loss, on_device)``: the positive loss of every tree under this problem's model, and whether a HIP pass over a device
         forest computed it (``scores`` then finishes it in one launch)"""
         on_device = self.execute_mode != "torch" and forest.batch_node_value.is_cuda
+        if self._own_loss:
+            if self.loss is not None and not use_MSE:
+                raise ValueError(f"this problem's loss is {self.loss!r}: use_MSE must be left True")
+            out = self.weighted_loss(forest, self.loss or ("mse" if use_MSE else "mae"))
+            if self.validation_mask is None:
+                return out, on_device
+            self.last_validation_loss = out[:, 1]
+            return out[:, 0].contiguous(), on_device
         if self.multigene or self.linear_scaling:
             self._check_scaling(use_MSE)
             return (self.gene_model(forest) if self.multigene else self.scaled_fitness(forest))[0], on_device

@@ -15,6 +15,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     semantic duplicates   semantic_hash, semantic_classes, semantic_unique: trees equal on every data row
     subtrees              SR_subtree_errors, simplify: the loss of every subtree; the smaller tree that is no worse
     linear scaling        SR_scaled_fitness, apply_scaling: the loss under the least-squares slope and intercept; the tree with them
+    weighted losses       SR_weighted_loss: sample weights, Huber / pinball / log-cosh, training and validation columns in one pass
     multi-gene            SR_gene_fitness, SR_gene_moments, gene_predict: a tree's outputs as features of a least-squares model
     intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
@@ -44,8 +45,28 @@ from .utils import NType, box_side, check_tensor, check_units, draw_keys, parse_
 _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") != "0"
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
+WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
+LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
+
+
+def check_loss(loss, param) -> Optional[float]:
+    """the parameter of ``SR_weighted_loss``'s ``loss`` as a float (None for a loss that has none), or ``ValueError``"""
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"loss should be one of {list(LOSS_KINDS)}, but got {loss!r}")
+    if loss not in ("huber", "pinball"):
+        if param is not None:
+            raise ValueError(f"loss={loss!r} takes no param, but got {param!r}")
+        return None
+    if param is None or isinstance(param, bool) or not isinstance(param, (int, float)):
+        raise ValueError(f"loss={loss!r} needs a float param, but got {param!r}")
+    param = float(param)
+    if loss == "huber" and not 0.0 < param < float("inf"):
+        raise ValueError(f"the delta of the huber loss should be finite and > 0, but got {param}")
+    if loss == "pinball" and not 0.0 < param < 1.0:
+        raise ValueError(f"the tau of the pinball loss should lie in (0, 1), but got {param}")
+    return param
 
 
 def _symmetric(packed: Tensor, K: int) -> Tensor:
@@ -464,6 +485,46 @@ class Forest:
         mask = self.func_mask
         return (Forest(self.input_len, self.output_len, value, ntype, size, func_mask=(mask | _WRAP_FUNCS) if mask else 0),
                 applied.to(torch.bool))
+
+    # ---- weighted, robust and held-out losses -----------------------------------------------------
+    def SR_weighted_loss(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor] = None, loss: str = "mse",
+                         param: Optional[float] = None, dedup: bool = False) -> Tensor:
+        """``(sum_d W[k, d] * rho(tree(x_d) - y_d)) / sum_d W[k, d]`` of every tree, float32, taken inside the evaluation kernel in one
+        pass (csrc/sr_wloss.hip): the ``(pop, D)`` predictions are never stored.  ``weights``: None (every weight 1) or ``(D,)`` gives
+        ``(pop,)``; ``(K, D)`` with ``1 <= K <= 8`` gives ``(pop, K)``, one column per weight row -- sample weights, a training and a
+        validation row of 0/1 masks, K folds -- for one interpretation of the trees.  ``loss``: ``"mse"``, ``"mae"``, ``"huber"``
+        (``param`` = delta > 0), ``"pinball"`` (``param`` = tau in (0, 1): the fit sits at the tau-quantile) or ``"logcosh"``; rho is
+        evaluated in float64 on the float32 predictions of ``batch_forward``.
+
+        A row with weight exactly 0 is not looked at in that column: the tree may be NaN or infinite there.  A column is NaN where a
+        row WITH weight has a non-finite prediction or the tree is malformed, and for every tree when its weight row holds a negative
+        or non-finite weight or sums to 0 (decided on the device: include/evogp_hip.h has the rules).  A column depends on its own
+        weight row only.  Deterministic from run to run, no host synchronisation; single-output forests.
+
+        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
+        self._single_output("SR_weighted_loss", ValueError)
+        param = check_loss(loss, param)
+        dev = self.batch_node_value.device
+        inputs, labels = check_tensor(inputs, dev), check_tensor(labels, dev)
+        n = inputs.shape[0]
+        if inputs.shape != (n, self.input_len):
+            raise ValueError(f"inputs shape should be ({n}, {self.input_len}), but got {tuple(inputs.shape)}")
+        if labels.shape != (n, 1):
+            raise ValueError(f"labels shape should be ({n}, 1), but got {tuple(labels.shape)}")
+        inputs, labels = inputs.contiguous().to(torch.float32), labels.contiguous().to(torch.float32)
+        flat = True
+        if weights is not None:
+            weights = check_tensor(weights, dev)
+            flat = weights.dim() == 1
+            if not weights.dtype.is_floating_point:
+                raise ValueError(f"weights should be a floating-point tensor, but got {weights.dtype}")
+            if weights.dim() not in (1, 2) or weights.shape[-1] != n or (weights.dim() == 2 and not 1 <= weights.shape[0] <= WLOSS_MAX_WEIGHTS):
+                raise ValueError(f"weights shape should be ({n},) or (K, {n}) with 1 <= K <= {WLOSS_MAX_WEIGHTS}, but got {tuple(weights.shape)}")
+            weights = weights.reshape(-1, n).contiguous().to(torch.float32)
+        source, gather = self._once_per_class(dedup)
+        out = gather(torch.ops.evogp_hip.tree_SR_weighted_loss(*self._shape(inputs), *source._tensors(), inputs, labels, weights,
+                                                               LOSS_KINDS[loss], 0.0 if param is None else param))
+        return out[:, 0] if flat else out
 
     # ---- multi-gene fitness ----------------------------------------------------------------------
     def _gene_data(self, what: str, inputs: Tensor, labels: Tensor):

@@ -658,6 +658,47 @@ int evogp_hip_sr_gene_fitness(unsigned pop_size, unsigned data_points, unsigned 
                               const float *value, const int16_t *type, const int16_t *size, const float *variables,
                               const float *labels, float *loss, float *coef, double *moments /* nullable */, evogp_stream_t stream);
 
+/* Weighted, robust and held-out losses (no counterpart in the reference, whose loss is the unweighted mean of squared or absolute errors
+ * over every row): for every single-output tree t and each of K = n_weights weight rows, in one pass over the dataset
+ * (csrc/sr_wloss.hip; no (pop, D) matrix exists),
+ *     loss[t][k] = ( sum_d W[k][d] * rho(p_td - y_d) ) / sum_d W[k][d]
+ * with p_td the float32 prediction on row d (the bits evogp_hip_batch_evaluate stores), r = (double)p_td - (double)y_d, and rho
+ * evaluated in float64:
+ *   EVOGP_LOSS_MSE      r^2
+ *   EVOGP_LOSS_MAE      |r|
+ *   EVOGP_LOSS_HUBER    r^2 / 2 for |r| <= delta, else delta (|r| - delta / 2);   loss_param = delta, finite and > 0
+ *   EVOGP_LOSS_PINBALL  tau r_y for r_y >= 0, else (tau - 1) r_y, r_y = y - p;     loss_param = tau in (0, 1): the fit sits at the tau-quantile
+ *   EVOGP_LOSS_LOGCOSH  |r| + log1p(exp(-2 |r|)) - log 2  (log cosh r in a form that cannot overflow)
+ * weights is f32[K][D], 1 <= K <= EVOGP_WLOSS_MAX_WEIGHTS, or NULL with n_weights == 1: every weight is 1 and no weight is loaded.  One
+ * sample-weight row, two 0/1-masked rows (training and validation), K folds or bootstrap replicates are all this call.
+ * Rules that decide a value exactly:
+ *   - a row with W[k][d] == 0 is NOT LOOKED AT in column k: it adds exactly 0 whatever p_td is, NaN and inf included (which
+ *     case_errors @ W cannot give: 0 * NaN is NaN);
+ *   - loss[t][k] is NaN when some row with W[k][d] != 0 has a prediction that is not finite, or when the tree is malformed (the rule
+ *     of evogp_hip_sr_linear_scaling: length clamped to [0, gp_len], not empty, no stack underflow, one value left);
+ *   - a weight row that holds a negative or non-finite weight, or whose sum is 0, gives NaN for every tree.  A one-workgroup kernel in
+ *     front decides that on the device and leaves sum_d W[k][d] (float64, fixed order: thread i of 256 adds rows i, i + 256, ..., the
+ *     lanes by the fixed butterfly, the waves in ascending order) and the flag there: nothing synchronises with the host;
+ *   - the result is (float)(S / Wsum) from float64, and may be +inf;
+ *   - column k depends on the tree, the dataset, W[k], the kind and the parameter only: not on K, the other weight rows, the other
+ *     trees or the run.  It is bit-identical from run to run, and weights == NULL gives the bits of a row of ones.
+ * No float atomics.  Sums have the fixed order of evogp_hip_sr_linear_scaling: lane partials over the wave's row tiles in ascending
+ * order, the 64 lanes by a fixed butterfly, the waves in ascending order.  loss is f32[pop][K].  The call can be captured into a HIP
+ * graph once one eager call on the stream has been made.
+ * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, n_weights outside 1 .. 8 or != 1 with weights == NULL, an unknown
+ * kind, a NaN loss_param, a delta that is not finite and positive, a tau outside (0, 1).  Then out_len != 1: EVOGP_E_UNSUPPORTED; then a
+ * NULL pointer other than weights: EVOGP_E_NULLPTR.  Any gp_len <= 1024, var_len and data_points. */
+#define EVOGP_WLOSS_MAX_WEIGHTS 8
+#define EVOGP_LOSS_MSE 0
+#define EVOGP_LOSS_MAE 1
+#define EVOGP_LOSS_HUBER 2
+#define EVOGP_LOSS_PINBALL 3
+#define EVOGP_LOSS_LOGCOSH 4
+int evogp_hip_sr_weighted_loss(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                               const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                               const float *labels, const float *weights /* nullable */, unsigned n_weights, int loss_kind,
+                               double loss_param, float *loss, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -740,7 +781,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
