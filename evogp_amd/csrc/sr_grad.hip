@@ -22,7 +22,15 @@
 // workspace of the tape kernels for longer rows, one slice of 2 x gp_len x 256 B per resident wave.  Every access is a [node][lane]
 // column: 64 consecutive floats, one per lane, conflict-free in LDS and one coalesced 256-byte line in memory.  Waves, workgroups, LDS
 // bytes and the workspace come from the plan the three tape passes share (sr_forward.hpp plan_tape_launch).
+//
+// The WEIGHTED build (WL, evogp_hip_sr_weighted_gradient: single-output trees) is the same walk with another epilogue: the row's
+// weight is read next to y and `valid` also asks for w != 0 (a tile without a weighted row is skipped whole), the loss is
+// sum w rho(r) in float64 per lane (wave_sum_d, then the waves in wave order) over Wsum, the reverse walk is seeded with
+// w rho'(r) / Wsum, and a non-finite prediction on a weighted row makes the tree NaN (sr_wloss.hip's rule).
+#include <type_traits>
+
 #include "sr_adjoint.hpp"
+#include "sr_moments.hpp"
 
 namespace evogp {
 
@@ -38,12 +46,24 @@ struct GradParams {
     int pop, D, gp_len, var_len, out_len, use_mse;
 };
 
+struct WGradParams : GradParams {   // the weighted build's
+    const float *w;           // [D], or nullptr: every weight is 1
+    const WeightStat *stat;   // the weight row's sum and whether it may be used (weight_stats_kernel); nullptr without w
+    double prm;               // delta (huber) or tau (pinball)
+    int kind;
+};
+
 // Dynamic LDS of one workgroup (16-byte aligned carve): op[L] kids[L] pay[L] stack[L] (u32), part[W][L], lpart[W], cls/len (2 words,
 // padded to 4), then, for LDS tapes, W x 2 x L x 64 floats.
 __host__ __device__ inline size_t grad_lds_head_words(int L, int W) { return (((size_t)4 * L + (size_t)W * L + W + 4) + 3) & ~(size_t)3; }
 
-template <bool MO>
-__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams p) {
+// the weighted build's head: lpart is W doubles on an 8-byte boundary, followed by the waves' "met a non-finite prediction" words
+__host__ __device__ inline size_t wgrad_lpart_word(int L, int W) { return (((size_t)4 * L + (size_t)W * L) + 1) & ~(size_t)1; }
+__host__ __device__ inline size_t wgrad_lds_head_words(int L, int W) { return ((wgrad_lpart_word(L, W) + (size_t)3 * W + 4) + 3) & ~(size_t)3; }
+
+template <bool MO, bool WL = false>
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(std::conditional_t<WL, WGradParams, GradParams> p) {
+    static_assert(!(MO && WL), "the weighted build takes single-output trees");
     extern __shared__ __attribute__((aligned(16))) uint32_t grad_lds[];
     const int L = p.gp_len;
     const int lane = threadIdx.x & 63;
@@ -53,15 +73,27 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams 
     int *s_stk = (int *)(s_pay + L);
     float *s_part = (float *)(s_stk + L);
     float *s_lpart = s_part + (size_t)W * L;
-    int *s_meta = (int *)(s_lpart + W);
+    double *s_dpart = (double *)(grad_lds + wgrad_lpart_word(L, W));   // (weighted build)
+    int *s_bad = (int *)(s_dpart + W);
+    int *s_meta = WL ? s_bad + W : (int *)(s_lpart + W);
     float *tape = p.tape ? p.tape + ((size_t)blockIdx.x * W + w) * 2 * L * kWave
-                         : (float *)(grad_lds + grad_lds_head_words(L, W)) + (size_t)w * 2 * L * kWave;
+                         : (float *)(grad_lds + (WL ? wgrad_lds_head_words(L, W) : grad_lds_head_words(L, W))) + (size_t)w * 2 * L * kWave;
     float *val = tape, *adj = tape + (size_t)L * kWave;
     const int ntiles = (p.D + kWave - 1) / kWave;
     const float inv_d = 1.0f / (float)p.D;
+    double wsum = (double)p.D;
+    bool usable = true;
+    if constexpr (WL) {
+        if (p.w) { wsum = p.stat->sum; usable = p.stat->usable != 0; }
+    }
 
     for (int t = blockIdx.x; t < p.pop; t += gridDim.x) {
         const size_t row = (size_t)t * L;
+        if (WL && !usable) {  // a weight row that may not be used: NaN loss, zero row, for every tree
+            for (int i = threadIdx.x; i < L; i += blockDim.x) p.grad[row + i] = 0.0f;
+            if (threadIdx.x == 0) p.loss[t] = __builtin_nanf("");
+            continue;
+        }
         // ---- wave 0: classify, decode, operand table ----
         if (w == 0) {
             int len = uni((int)p.size[row]);
@@ -91,10 +123,18 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams 
         };
 
         float acc = 0.0f;
+        double dacc = 0.0;   // (weighted build)
+        int bad = 0;
         for (int tile = w; tile < ntiles; tile += W) {
             const int d = tile * kWave + lane;
-            const bool valid = d < p.D;
+            bool valid = d < p.D;
             const int dc = valid ? d : p.D - 1;
+            float wv = 1.0f;
+            if constexpr (WL) {
+                if (p.w) wv = p.w[dc];
+                valid = valid && wv != 0.0f;   // a row without weight is not looked at
+                if (!__any(valid)) continue;   // (wave-uniform) nor is a tile of them
+            }
             const float *xr = p.X + (size_t)dc * p.var_len;
             v16f outs, gout;
             if (MO) {
@@ -136,7 +176,16 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams 
             }
             // ---- loss and the adjoints of the outputs ----
             float e = 0.0f, g0 = 0.0f;
-            if (!MO) {
+            if constexpr (WL) {
+                const float pred = val[lane];
+                const double r = (double)pred - (double)p.y[dc];
+                const bool lc = p.kind == EVOGP_LOSS_LOGCOSH;   // (wave-uniform)
+                const double term = valid ? (double)wv * (lc ? wloss_rho<true>(p.kind, p.prm, r) : wloss_rho<false>(p.kind, p.prm, r)) : 0.0;
+                dacc += term;
+                bad |= valid && !finite_f(pred);
+                const double dr = lc ? wloss_drho<true>(p.kind, p.prm, r) : wloss_drho<false>(p.kind, p.prm, r);
+                g0 = valid ? (float)((double)wv * dr / wsum) : 0.0f;
+            } else if (!MO) {
                 const float pred = val[lane], yv = p.y[dc];
                 e = grad_err(yv - pred, p.use_mse);
                 const float diff = pred - yv;
@@ -208,21 +257,34 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_grad_kernel(GradParams 
             const float s = wave_sum(adj[i * kWave + lane]);
             if (lane == 0) s_part[(size_t)w * L + i] = s;
         }
-        {
+        if (WL) {
+            const double s = wave_sum_d(dacc);
+            const int wbad = __any(bad) ? 1 : 0;
+            if (lane == 0) { s_dpart[w] = s; s_bad[w] = wbad; }
+        } else {
             const float s = wave_sum(acc);
             if (lane == 0) s_lpart[w] = s;
         }
         __syncthreads();
+        bool ok = true;   // (weighted build) no weighted row with a non-finite prediction
+        if (WL)
+            for (int k = 0; k < W; ++k) ok = ok && s_bad[k] == 0;
         for (int i = threadIdx.x; i < L; i += blockDim.x) {
             float s = 0.0f;
             if (i < len && (s_op[i] & kOpMask) == H_CONST)
                 for (int k = 0; k < W; ++k) s += s_part[(size_t)k * L + i];
-            p.grad[row + i] = s;
+            p.grad[row + i] = ok ? s : 0.0f;
         }
         if (threadIdx.x == 0) {
-            float s = 0.0f;
-            for (int k = 0; k < W; ++k) s += s_lpart[k];
-            p.loss[t] = s / (float)p.D;
+            if (WL) {
+                double s = 0.0;
+                for (int k = 0; k < W; ++k) s += s_dpart[k];
+                p.loss[t] = ok ? (float)(s / wsum) : __builtin_nanf("");
+            } else {
+                float s = 0.0f;
+                for (int k = 0; k < W; ++k) s += s_lpart[k];
+                p.loss[t] = s / (float)p.D;
+            }
         }
         __syncthreads();  // the tables are rebuilt for the next tree
     }
@@ -304,6 +366,41 @@ extern "C" int evogp_hip_sr_gradient(unsigned pop_size, unsigned data_points, un
     if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_grad_kernel<true>, (const void *)sr_grad_kernel<false>})) return (int)e;
     if (p.out_len > 1) hipLaunchKernelGGL(sr_grad_kernel<true>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     else hipLaunchKernelGGL(sr_grad_kernel<false>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int evogp_hip_sr_weighted_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                              const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                              const float *labels, const float *weights, int loss_kind, double loss_param, float *loss,
+                                              float *grad, evogp_stream_t stream_) {
+    if (pop_size == 0 || data_points == 0 || gp_len == 0 || gp_len > (unsigned)kMaxStack || var_len == 0 || out_len == 0 ||
+        pop_size > 0x7FFFFFFFu || data_points > 0x7FFFFFFFu)
+        return EVOGP_E_BADARG;
+    if (loss_kind < EVOGP_LOSS_MSE || loss_kind > EVOGP_LOSS_LOGCOSH || loss_param != loss_param) return EVOGP_E_BADARG;
+    if (loss_kind == EVOGP_LOSS_HUBER && !(loss_param > 0.0 && loss_param < HUGE_VAL)) return EVOGP_E_BADARG;
+    if (loss_kind == EVOGP_LOSS_PINBALL && !(loss_param > 0.0 && loss_param < 1.0)) return EVOGP_E_BADARG;
+    if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    if (!value || !type || !size || !variables || !labels || !loss || !grad) return EVOGP_E_NULLPTR;
+    const hipStream_t stream = (hipStream_t)stream_;
+    WGradParams p{};
+    p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.loss = loss; p.grad = grad;
+    p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len; p.out_len = 1;
+    p.w = weights; p.kind = loss_kind; p.prm = loss_param;
+    hipError_t e;
+    if (weights) {   // the row's sum and whether it may be used stay on the device (sr_wloss.hip's rule and kernel)
+        WeightStatOut out{};
+        out.slot[0] = (WeightStat *)acquire_counter(stream, &e);
+        if (!out.slot[0]) return (int)e;
+        p.stat = out.slot[0];
+        hipLaunchKernelGGL(weight_stats_kernel, dim3(1), dim3(kStatsThreads), 0, stream, weights, p.D, 1, out);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    TapePlan plan;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, wgrad_lds_head_words, &plan)) return rc;
+    p.tape = plan.tape;
+    static LdsGrant grant;
+    if ((e = grant_tape_lds(grant, {(const void *)sr_grad_kernel<false, true>})) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((sr_grad_kernel<false, true>), dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 

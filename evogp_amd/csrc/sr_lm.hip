@@ -14,13 +14,22 @@
 // Lanes are reduced by the fixed DPP butterfly (wave_sum), waves in wave order through LDS: no float atomics, bit-identical from run
 // to run.  Tapes live in LDS for rows of at most kTapeLdsLen nodes and in the tape kernels' per-stream global workspace for longer rows;
 // the launch is the plan the three tape passes share (sr_forward.hpp plan_tape_launch), which is why the loss is sr_grad.hip's bit for bit.
+//
+// The WEIGHTED build (WL, evogp_hip_sr_weighted_normal_eq) differs as sr_grad.hip's does: the row's weight is read next to y, `valid`
+// also asks for w != 0 (a tile without a weighted row is skipped whole), A and b are sums of w J_i J_j and w J_i r over Wsum, the loss
+// is sum w r^2 in float64 (sr_grad.hip's weighted loss for mse, bit for bit), and a non-finite prediction on a weighted row makes the
+// tree NaN.
+#include <type_traits>
+
 #include "sr_adjoint.hpp"
+#include "sr_moments.hpp"
 
 namespace evogp {
 
 constexpr int kLmTri = kLmMaxConsts * (kLmMaxConsts + 1) / 2;   // 36: upper triangle of A
 constexpr int kLmWords = kLmTri + kLmMaxConsts;                 // 44: a row of `normal`
 constexpr int kLmPart = 48;         // words of one wave's partial sums in LDS: 44 of `normal`, the sum of r^2, padding
+constexpr int kLmPartBad = 45, kLmPartLoss = 46;   // weighted build: "met a non-finite prediction", and the float64 sum of w r^2 (2 words)
 static_assert(kLmWords == EVOGP_LM_NORMAL_WORDS && kLmWords + 1 <= kLmPart, "layout of a normal-equation row");
 
 struct NormalEqParams {
@@ -33,6 +42,11 @@ struct NormalEqParams {
     float *normal;   // [pop][kLmWords]
     float *tape;     // global tapes (rows longer than kTapeLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len;
+};
+
+struct WNormalEqParams : NormalEqParams {   // the weighted build's
+    const float *w;           // [D], or nullptr: every weight is 1
+    const WeightStat *stat;   // the weight row's sum and whether it may be used (weight_stats_kernel); nullptr without w
 };
 
 // The optimised constants of a single-output row: the node indices of its first kLmMaxConsts CONST nodes inside [0, len), in prefix
@@ -64,7 +78,8 @@ __host__ __device__ inline size_t lm_lds_head_words(int L, int W) {
     return (((size_t)4 * L + (size_t)W * kLmPart + kLmMaxConsts + 4) + 3) & ~(size_t)3;
 }
 
-__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(NormalEqParams p) {
+template <bool WL = false>
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(std::conditional_t<WL, WNormalEqParams, NormalEqParams> p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lm_lds[];
     const int L = p.gp_len;
     const int lane = threadIdx.x & 63;
@@ -79,9 +94,19 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(Normal
                          : (float *)(lm_lds + lm_lds_head_words(L, W)) + (size_t)w * 2 * L * kWave;
     float *val = tape, *adj = tape + (size_t)L * kWave;
     const int ntiles = (p.D + kWave - 1) / kWave;
+    double wsum = (double)p.D;
+    bool usable = true;
+    if constexpr (WL) {
+        if (p.w) { wsum = p.stat->sum; usable = p.stat->usable != 0; }
+    }
 
     for (int t = blockIdx.x; t < p.pop; t += gridDim.x) {
         const size_t row = (size_t)t * L;
+        if (WL && !usable) {  // a weight row that may not be used: NaN loss, zero row, for every tree
+            for (int i = threadIdx.x; i < kLmWords; i += blockDim.x) p.normal[(size_t)t * kLmWords + i] = 0.0f;
+            if (threadIdx.x == 0) p.loss[t] = __builtin_nanf("");
+            continue;
+        }
         // ---- wave 0: classify, decode, operand table, the optimised constants ----
         if (w == 0) {
             int len = uni((int)p.size[row]);
@@ -114,10 +139,18 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(Normal
 #pragma unroll
         for (int k = 0; k < kLmMaxConsts; ++k) b[k] = 0.0f;
 
+        double dacc = 0.0;   // (weighted build)
+        int bad = 0;
         for (int tile = w; tile < ntiles; tile += W) {
             const int d = tile * kWave + lane;
-            const bool valid = d < p.D;
+            bool valid = d < p.D;
             const int dc = valid ? d : p.D - 1;
+            float wv = 1.0f;
+            if constexpr (WL) {
+                if (p.w) wv = p.w[dc];
+                valid = valid && wv != 0.0f;   // a row without weight is not looked at
+                if (!__any(valid)) continue;   // (wave-uniform) nor is a tile of them
+            }
             const float *xr = p.X + (size_t)dc * p.var_len;
             // ---- forward: execution order, every node's value on the tape ----
             for (int i = len - 1; i >= 0; --i) {
@@ -175,14 +208,23 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(Normal
                 }
             }
             const float rv = valid ? r : 0.0f;
-            r2 += rv * rv;
+            if (WL) {
+                const float pred = val[lane];
+                const double rd = (double)pred - (double)p.y[dc];
+                const double term = valid ? (double)wv * wloss_rho<false>(EVOGP_LOSS_MSE, 0.0, rd) : 0.0;
+                dacc += term;
+                bad |= valid && !finite_f(pred);
+            } else {
+                r2 += rv * rv;
+            }
             int k = 0;
 #pragma unroll
             for (int i = 0; i < kLmMaxConsts; ++i) {
+                const float wJ = WL ? wv * J[i] : J[i];
 #pragma unroll
                 for (int j = i; j < kLmMaxConsts; ++j, ++k)
-                    if (j < nc) A[k] += J[i] * J[j];
-                if (i < nc) b[i] += J[i] * rv;
+                    if (j < nc) A[k] += wJ * J[j];
+                if (i < nc) b[i] += wJ * rv;
             }
         }
 
@@ -198,12 +240,30 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_normal_eq_kernel(Normal
             const float s = wave_sum(b[k]);
             if (lane == 0) part[kLmTri + k] = s;
         }
-        {
+        if (WL) {
+            const double s = wave_sum_d(dacc);
+            const int wbad = __any(bad) ? 1 : 0;
+            if (lane == 0) { *(double *)(part + kLmPartLoss) = s; ((int *)part)[kLmPartBad] = wbad; }
+        } else {
             const float s = wave_sum(r2);
             if (lane == 0) part[kLmWords] = s;
         }
         __syncthreads();
-        if (threadIdx.x <= kLmWords) {
+        if (WL) {
+            if (threadIdx.x <= kLmWords) {
+                bool ok = true;   // no weighted row with a non-finite prediction
+                for (int k = 0; k < W; ++k) ok = ok && ((const int *)s_part)[(size_t)k * kLmPart + kLmPartBad] == 0;
+                if (threadIdx.x < kLmWords) {
+                    float s = 0.0f;
+                    for (int k = 0; k < W; ++k) s += s_part[(size_t)k * kLmPart + threadIdx.x];
+                    p.normal[(size_t)t * kLmWords + threadIdx.x] = ok ? (float)((double)s / wsum) : 0.0f;
+                } else {
+                    double s = 0.0;
+                    for (int k = 0; k < W; ++k) s += *(const double *)(s_part + (size_t)k * kLmPart + kLmPartLoss);
+                    p.loss[t] = ok ? (float)(s / wsum) : __builtin_nanf("");
+                }
+            }
+        } else if (threadIdx.x <= kLmWords) {
             float s = 0.0f;
             for (int k = 0; k < W; ++k) s += s_part[(size_t)k * kLmPart + threadIdx.x];
             s = s / (float)p.D;
@@ -368,8 +428,40 @@ extern "C" int evogp_hip_sr_normal_eq(unsigned pop_size, unsigned data_points, u
     if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, lm_lds_head_words, &plan)) return rc;
     p.tape = plan.tape;
     static LdsGrant grant;
-    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_normal_eq_kernel})) return (int)e;
-    hipLaunchKernelGGL(sr_normal_eq_kernel, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
+    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_normal_eq_kernel<>})) return (int)e;
+    hipLaunchKernelGGL(sr_normal_eq_kernel<>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int evogp_hip_sr_weighted_normal_eq(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                               const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                               const float *labels, const float *weights, float *loss, float *normal,
+                                               evogp_stream_t stream_) {
+    if (pop_size == 0 || data_points == 0 || gp_len == 0 || gp_len > (unsigned)kMaxStack || var_len == 0 || out_len == 0 ||
+        pop_size > 0x7FFFFFFFu || data_points > 0x7FFFFFFFu)
+        return EVOGP_E_BADARG;
+    if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    if (!value || !type || !size || !variables || !labels || !loss || !normal) return EVOGP_E_NULLPTR;
+    const hipStream_t stream = (hipStream_t)stream_;
+    WNormalEqParams p{};
+    p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.loss = loss; p.normal = normal;
+    p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len;
+    p.w = weights;
+    hipError_t e;
+    if (weights) {   // the row's sum and whether it may be used stay on the device (sr_wloss.hip's rule and kernel)
+        WeightStatOut out{};
+        out.slot[0] = (WeightStat *)acquire_counter(stream, &e);
+        if (!out.slot[0]) return (int)e;
+        p.stat = out.slot[0];
+        hipLaunchKernelGGL(weight_stats_kernel, dim3(1), dim3(kStatsThreads), 0, stream, weights, p.D, 1, out);
+        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    }
+    TapePlan plan;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, lm_lds_head_words, &plan)) return rc;
+    p.tape = plan.tape;
+    static LdsGrant grant;
+    if ((e = grant_tape_lds(grant, {(const void *)sr_normal_eq_kernel<true>})) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(sr_normal_eq_kernel<true>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 

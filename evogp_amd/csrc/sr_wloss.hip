@@ -7,7 +7,7 @@
 // and "some such row has a prediction that is not finite"; the result is (float)(S_k / sum_d W[k, d]).  The (pop, D) predictions are never
 // stored, and a row a column gives no weight to is not looked at in that column.  The launches, all on the caller's stream, nothing
 // synchronises with the host:
-//   1. weight_stats_kernel  ONE workgroup (label_stats_kernel's shape, sr_moments.hpp): per weight row the float64 sum in a fixed order
+//   1. weight_stats_kernel  ONE workgroup (sr_moments.hpp, next to label_stats_kernel and rho): per weight row the float64 sum in a fixed order
 //                           and whether the row may be used (no negative or non-finite weight, a sum that is not 0); both stay on the
 //                           device.  Not launched without weights.
 //   2. sr_wloss_kernel      sr_scale_kernel's decomposition (sr_scale.hip: the register interpreter, LEAN then FULL over the
@@ -37,12 +37,6 @@ static_assert(EVOGP_WLOSS_MAX_WEIGHTS == 8, "the accumulator widths end at 8");
 // trees per batch: the LDS partial-sum slots.  At 8 columns 32 trees keep partials and weights under a third of a CU's LDS
 constexpr int wloss_batch(int KW) { return KW == 8 ? kMaxBatch / 2 : kMaxBatch; }
 
-struct WeightStat {   // one 16-byte slot of acquire_counter per weight row
-    double sum;
-    unsigned usable;  // != 0: no negative or non-finite weight and sum != 0
-    unsigned pad;
-};
-
 struct WlossParams {
     const float *value;
     const int16_t *type;
@@ -58,57 +52,12 @@ struct WlossParams {
     int pop, D, gp_len, var_len, nw, batch, ntiles;
 };
 
-// rho in float64; r = (double)p - (double)y.  `kind` is wave-uniform.  LC: the log-cosh build.  The float64 exp and log1p take registers
-// the LEAN interpreter does not have (164 B of scratch per lane against 8 at KW = 2), so the other four kinds do not carry them
-template <bool LC>
-__device__ inline double wloss_rho(int kind, double prm, double r) {
-    const double a = fabs(r);
-    if (LC) return a + log1p(exp(-2.0 * a)) - M_LN2;   // log cosh r, no overflow
-    switch (kind) {
-    case EVOGP_LOSS_MSE: return r * r;
-    case EVOGP_LOSS_MAE: return a;
-    case EVOGP_LOSS_HUBER: return a <= prm ? r * r * 0.5 : prm * (a - prm * 0.5);
-    default: {
-        const double ry = -r;   // y - p
-        return ry >= 0.0 ? prm * ry : (prm - 1.0) * ry;
-    }
-    }
-}
-
 // (float)(S / Wsum), NaN for a column that may not be used or that met a non-finite prediction
 __device__ inline float wloss_value(const WlossParams &p, int k, double s, bool bad) {
     double wsum = (double)p.D;
     bool usable = true;
     if (p.W) { wsum = p.stat[k]->sum; usable = p.stat[k]->usable != 0; }
     return usable && !bad ? (float)(s / wsum) : __builtin_nanf("");
-}
-
-// ---- 1. weight statistics: one workgroup, thread i takes rows i, i + 256, ...; lanes by the butterfly, waves in order ------------------
-struct WeightStatOut { WeightStat *slot[EVOGP_WLOSS_MAX_WEIGHTS]; };
-
-static __global__ __launch_bounds__(kStatsThreads) void weight_stats_kernel(const float *W, int D, int nw, WeightStatOut out) {
-    __shared__ double s_w[kStatsThreads / kWave];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = 0; k < nw; ++k) {
-        const float *row = W + (size_t)k * D;
-        double s = 0.0;
-        int bad = 0;
-        for (int i = threadIdx.x; i < D; i += kStatsThreads) {
-            const float x = row[i];
-            bad |= !finite_f(x) || x < 0.0f;
-            s += (double)x;
-        }
-        const double ws = wave_sum_d(s);
-        const int any_bad = __syncthreads_or(bad);   // (also: the previous round's reads of s_w are over)
-        if (lane == 0) s_w[w] = ws;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double total = 0.0;
-            for (int i = 0; i < kStatsThreads / kWave; ++i) total += s_w[i];
-            out.slot[k]->sum = total;
-            out.slot[k]->usable = !any_bad && total != 0.0 ? 1u : 0u;
-        }
-    }
 }
 
 // ---- 2. the register interpreter ---------------------------------------------------------------------------------------------------------

@@ -376,6 +376,50 @@ Tensor tree_SR_weighted_loss(int64_t pop_size, int64_t data_points, int64_t gp_l
     return loss;
 }
 
+// the one weight row of the weighted tuning passes: (data_points,) float32 on the dataset's device, or nullptr without one
+static const float *weight_row(const c10::optional<Tensor> &weights, int64_t data_points, const Dataset &d) {
+    if (!weights.has_value()) return nullptr;
+    check_tensor(*weights, {data_points}, "weights", d.dev, at::kFloat);
+    return weights->data_ptr<float>();
+}
+
+// loss and gradient under a weight row and one of the five losses (evogp_hip_sr_weighted_gradient): what tree_SR_weighted_loss scores by
+std::tuple<Tensor, Tensor> tree_SR_weighted_gradient(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                     const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                     const Tensor &labels, const c10::optional<Tensor> &weights, int64_t loss_kind,
+                                                     double loss_param) {
+    const Dataset d = check_dataset("tree_SR_weighted_gradient", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    TORCH_CHECK(loss_kind >= EVOGP_LOSS_MSE && loss_kind <= EVOGP_LOSS_LOGCOSH, "loss_kind must be in range [", EVOGP_LOSS_MSE, ", ",
+                EVOGP_LOSS_LOGCOSH, "], but got ", loss_kind);
+    TORCH_CHECK(loss_param == loss_param, "loss_param must not be NaN");
+    TORCH_CHECK(loss_kind != EVOGP_LOSS_HUBER || (loss_param > 0.0 && loss_param < HUGE_VAL),
+                "loss_param (the delta of the Huber loss) must be finite and larger than 0, but got ", loss_param);
+    TORCH_CHECK(loss_kind != EVOGP_LOSS_PINBALL || (loss_param > 0.0 && loss_param < 1.0),
+                "loss_param (the tau of the pinball loss) must lie in (0, 1), but got ", loss_param);
+    const float *w = weight_row(weights, data_points, d);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), grad = empty({pop_size, gp_len}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_weighted_gradient((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
+                                            d.type, d.size, d.X, d.y, w, (int)loss_kind, loss_param, loss.data_ptr<float>(), grad.data_ptr<float>(),
+                                            current_stream(d.dev)),
+             "tree_SR_weighted_gradient");
+    return {loss, grad};
+}
+
+// loss and normal equations of the weighted MSE (evogp_hip_sr_weighted_normal_eq)
+std::tuple<Tensor, Tensor> tree_SR_weighted_normal_eq(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                      const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                      const Tensor &labels, const c10::optional<Tensor> &weights) {
+    const Dataset d = check_dataset("tree_SR_weighted_normal_eq", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    const float *w = weight_row(weights, data_points, d);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size}, at::kFloat, d.dev), normal = empty({pop_size, (int64_t)EVOGP_LM_NORMAL_WORDS}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_weighted_normal_eq((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
+                                             d.type, d.size, d.X, d.y, w, loss.data_ptr<float>(), normal.data_ptr<float>(), current_stream(d.dev)),
+             "tree_SR_weighted_normal_eq");
+    return {loss, normal};
+}
+
 // multi-gene fitness (evogp_hip_sr_gene_fitness): loss (pop,), coef (pop, 1 + out_len) = intercept, weights; with_moments: also the
 // (pop, out_len (out_len + 5) / 2) float64 moments the solve read
 Tensor3 gene_fitness_impl(const char *op, bool with_moments, int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
@@ -1144,6 +1188,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_weighted_loss(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights, int loss_kind, float loss_param) -> Tensor");
+    m.def("tree_SR_weighted_gradient(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights, int loss_kind, float loss_param) -> (Tensor loss, Tensor grad)");
+    m.def("tree_SR_weighted_normal_eq(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights) -> (Tensor loss, Tensor normal)");
     m.def("tree_SR_gene_fitness(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_gene_moments(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
@@ -1194,6 +1242,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
+    m.impl("tree_SR_weighted_gradient", &tree_SR_weighted_gradient);
+    m.impl("tree_SR_weighted_normal_eq", &tree_SR_weighted_normal_eq);
     m.impl("tree_SR_gene_fitness", &tree_SR_gene_fitness);
     m.impl("tree_SR_gene_moments", &tree_SR_gene_moments);
     m.impl("tree_wrap_linear", &tree_wrap_linear);

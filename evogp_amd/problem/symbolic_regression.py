@@ -29,7 +29,7 @@ class SymbolicRegression(BaseProblem):
                  max_depth: Optional[int] = None, max_complexity: Optional[int] = None, complexity_of=None, nested_constraints=None,
                  operand_constraints=None, structure_penalty: Optional[float] = None, loss: Optional[str] = None,
                  loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
-                 validation_mask: Optional[Tensor] = None):
+                 validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -89,9 +89,14 @@ class SymbolicRegression(BaseProblem):
         holds rows out: the same pass scores every tree twice, on the rows where the mask is False -- the loss that is evolved, masked
         and penalised as before -- and on the rows where it is True, kept on the device as ``last_validation_loss``;
         ``validation_scores(forest)`` returns the latter as scores, and StandardPipeline tracks ``best_validation_tree`` with it.  A
-        tree need not be defined on a row it is not scored on.  ``ValueError`` together with ``linear_scaling``, ``multigene``,
-        ``const_opt_steps`` > 0 or ``simplify_every`` > 0 (those passes minimise the unweighted MSE / MAE), and from ``evaluate`` /
-        ``scores`` with ``use_MSE=False`` while ``loss`` is set."""
+        tree need not be defined on a row it is not scored on.  ``ValueError`` together with ``linear_scaling``, ``multigene`` or
+        ``simplify_every`` > 0 (those passes minimise the unweighted MSE / MAE), together with ``const_opt_steps`` > 0 unless
+        ``const_opt_loss="problem"``, and from ``evaluate`` / ``scores`` with ``use_MSE=False`` while ``loss`` is set.
+        ``const_opt_loss``: None (constant tuning minimises the unweighted MSE / MAE, as ever) or ``"problem"``: ``optimize`` tunes
+        under the problem's own loss -- ``loss`` and ``loss_param`` (MSE when only weights or a mask are given), on the training weight
+        row: ``sample_weights`` with the held-out rows at 0, which the tuner therefore never reads (``Forest.optimize_constants(weights=,
+        loss=, param=)``).  ``const_opt_method="lm"`` takes no ``loss`` but ``"mse"`` there (``ValueError``); a problem with none of
+        the four loss options tunes as under None."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -183,9 +188,15 @@ class SymbolicRegression(BaseProblem):
         self.last_validation_loss = None   # (pop,): the loss on the held-out rows, of the forest scored last
         self._loss_weights = None          # (K, D) float32 on the data's device: what SR_weighted_loss is called with
         self._own_loss = any(o is not None for o in (loss, loss_param, sample_weights, validation_mask))
+        if const_opt_loss not in (None, "problem"):
+            raise ValueError(f"const_opt_loss should be None or 'problem', but got {const_opt_loss!r}")
+        self.const_opt_loss = const_opt_loss
         if self._own_loss:
+            if const_opt_loss == "problem" and self.const_opt_method == "lm" and loss not in (None, "mse"):
+                raise ValueError(f"const_opt_method='lm' minimises the (weighted) mean squared error, but the problem's loss is {loss!r}")
             for name, on in (("linear_scaling", self.linear_scaling), ("multigene", self.multigene),
-                             ("const_opt_steps > 0", self.const_opt_steps > 0), ("simplify_every > 0", self.simplify_every > 0)):
+                             ("const_opt_steps > 0", self.const_opt_steps > 0 and const_opt_loss != "problem"),
+                             ("simplify_every > 0", self.simplify_every > 0)):
                 if on:
                     raise ValueError(f"loss, loss_param, sample_weights and validation_mask cannot be combined with {name}: "
                                      "that pass minimises the unweighted mean squared / absolute error")
@@ -498,8 +509,12 @@ class SymbolicRegression(BaseProblem):
                 forest = forest.simplify(self.datapoints, self.labels, use_MSE, dedup=self.dedup)[0]
         if self.const_opt_steps <= 0:
             return forest
+        own = {}
+        if self.const_opt_loss == "problem" and self._own_loss:   # the loss the trees are scored by, on the rows they are scored on
+            W = self._loss_weights
+            own = dict(weights=None if W is None else W[0], loss=self.loss, param=self.loss_param)   # (no loss: what use_MSE says)
         return forest.optimize_constants(self.datapoints, self.labels, self.const_opt_steps, self.const_step_size, use_MSE,
-                                         method=self.const_opt_method, dedup=self.dedup)[0]
+                                         method=self.const_opt_method, dedup=self.dedup, **own)[0]
 
     @property
     def problem_dim(self):

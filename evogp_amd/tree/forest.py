@@ -246,23 +246,61 @@ class Forest:
         inputs, labels = self._sr_data(inputs, labels)
         return torch.ops.evogp_hip.tree_SR_case_errors(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels).t()
 
-    def SR_gradient(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
-        """``(loss, grad)``: ``loss`` (pop,) is what ``SR_fitness`` returns, ``grad`` (pop, max_tree_len) is d loss / d value at every
-        constant node and exactly 0 elsewhere (one reverse-mode HIP pass, csrc/sr_grad.hip).  Malformed trees: NaN loss, zero row."""
-        inputs, labels = self._sr_data(inputs, labels)
-        return torch.ops.evogp_hip.tree_SR_gradient(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels)
+    def _tuning_loss(self, what: str, inputs: Tensor, use_MSE: bool, weights, loss, param):
+        """the loss the constants are tuned under: None when ``weights``, ``loss`` and ``param`` are all None (the unweighted ops run,
+        as ever), else ``(weights, kind, param)`` as the weighted ops take them -- ``weights`` a contiguous float32 ``(D,)`` tensor on
+        the forest's device or None, ``kind`` the integer of ``LOSS_KINDS``.  ``ValueError`` for what the rules of ``SR_gradient`` exclude"""
+        if weights is None and loss is None and param is None:
+            return None
+        self._single_output(f"{what} with weights, loss or param", ValueError)
+        if loss is None:
+            loss = "mse" if use_MSE else "mae"
+        elif not use_MSE:
+            raise ValueError(f"{what}: loss={loss!r} says which error is minimised, so use_MSE must be left True")
+        param = check_loss(loss, param)
+        if weights is not None:
+            n = inputs.shape[0]
+            if not isinstance(weights, Tensor) or not weights.dtype.is_floating_point or weights.shape != (n,):
+                raise ValueError(f"weights should be a ({n},) floating-point tensor, but got "
+                                 f"{(tuple(weights.shape), weights.dtype) if isinstance(weights, Tensor) else weights!r}")
+            weights = weights.detach().to(self.batch_node_value.device).contiguous().to(torch.float32)
+        return weights, LOSS_KINDS[loss], 0.0 if param is None else param
 
-    def SR_normal_equations(self, inputs: Tensor, labels: Tensor):
+    def SR_gradient(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, weights: Optional[Tensor] = None,
+                    loss: Optional[str] = None, param: Optional[float] = None):
+        """``(loss, grad)``: ``loss`` (pop,) is what ``SR_fitness`` returns, ``grad`` (pop, max_tree_len) is d loss / d value at every
+        constant node and exactly 0 elsewhere (one reverse-mode HIP pass, csrc/sr_grad.hip).  Malformed trees: NaN loss, zero row.
+
+        ``weights`` (a ``(D,)`` floating tensor), ``loss`` and ``param`` (those of ``SR_weighted_loss``; single-output forests): loss
+        and gradient of ``sum_d w_d rho(tree(x_d) - y_d) / sum_d w_d`` instead -- the loss ``SR_weighted_loss`` scores by, on the rows
+        it scores.  ``weights`` alone means ``"mse"``, or ``"mae"`` with ``use_MSE=False``; ``loss`` with ``use_MSE=False`` is a
+        ``ValueError``.  A row of weight 0 is not looked at; the loss is NaN and the row zero also where a row WITH weight has a
+        non-finite prediction, and for every tree when ``weights`` holds a negative or non-finite entry or sums to 0 (decided on the
+        device).  With all three left at None the call is the unweighted one, unchanged."""
+        inputs, labels = self._sr_data(inputs, labels)
+        own = self._tuning_loss("SR_gradient", inputs, use_MSE, weights, loss, param)
+        if own is None:
+            return torch.ops.evogp_hip.tree_SR_gradient(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels)
+        return torch.ops.evogp_hip.tree_SR_weighted_gradient(*self._shape(inputs), *self._tensors(), inputs, labels, *own)
+
+    def SR_normal_equations(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor] = None):
         """``(loss, A, b, const_index)`` of the Gauss-Newton model of the MSE loss in each tree's OPTIMISED constants: its first
         ``min(nc, K)`` CONST nodes in prefix order, ``K = LM_MAX_CONSTS = 8`` (further constants are held fixed).  With ``J`` the per-row
         Jacobian of the prediction in those constants and ``r = pred - y``: ``A = J^T J / D`` (pop, K, K), symmetric; ``b = J^T r / D``
         (pop, K), half the gradient of the loss; ``loss`` (pop,) is ``SR_gradient``'s; ``const_index`` (pop, K) int64 is the node position
         of each optimised constant, -1 where the tree has fewer.  Rows and columns of absent constants are exactly 0.  Malformed
-        trees: NaN loss, zero ``A`` and ``b``.  One HIP pass (csrc/sr_lm.hip); single-output forests only."""
-        self._single_output("SR_normal_equations")
+        trees: NaN loss, zero ``A`` and ``b``.  One HIP pass (csrc/sr_lm.hip); single-output forests only.
+
+        ``weights`` (a ``(D,)`` floating tensor): the model of the WEIGHTED MSE, ``A = sum w J^T J / sum w``, ``b = sum w J^T r / sum w``,
+        ``loss`` that of ``SR_gradient(weights=weights)`` bit for bit, under its rules for rows of weight 0 and unusable weights."""
+        self._single_output("SR_normal_equations", ValueError if weights is not None else AssertionError)
         inputs, labels = self._sr_data(inputs, labels)
         value, ntype, size = self._tensors()
-        loss, normal = torch.ops.evogp_hip.tree_SR_normal_eq(*self._shape(inputs), value, ntype, size, inputs, labels)
+        if weights is None:
+            loss, normal = torch.ops.evogp_hip.tree_SR_normal_eq(*self._shape(inputs), value, ntype, size, inputs, labels)
+        else:
+            w = self._tuning_loss("SR_normal_equations", inputs, True, weights, None, None)[0]
+            loss, normal = torch.ops.evogp_hip.tree_SR_weighted_normal_eq(*self._shape(inputs), value, ntype, size, inputs, labels, w)
         K = LM_MAX_CONSTS
         T = K * (K + 1) // 2
         A, b = _symmetric(normal[:, :T], K), normal[:, T:].clone()
@@ -320,7 +358,8 @@ class Forest:
         return firsts, lambda t: t[class_id]
 
     def optimize_constants(self, inputs: Tensor, labels: Tensor, steps: int = 10, step_size: float = 0.1, use_MSE: bool = True,
-                           method: str = "descent", damping: float = 1e-3, dedup: bool = False):
+                           method: str = "descent", damping: float = 1e-3, dedup: bool = False, weights: Optional[Tensor] = None,
+                           loss: Optional[str] = None, param: Optional[float] = None):
         """``(forest, loss)``: ``steps`` iterations of a per-tree optimisation of the constants, all on the device with no host
         synchronisation (2 launches per step).  Returns a new Forest (this one is untouched) whose trees differ from these only in
         constant values, and the loss of each returned tree.  No tree's loss rises.
@@ -334,22 +373,37 @@ class Forest:
 
         ``dedup=True``: the same result, bit for bit, with the dataset passes run once per DISTINCT tree (``duplicate_classes``): the
         launches see the other rows as empty trees, and every row then takes the tuned constants and the loss of its class's first
-        row.  No host synchronisation is added."""
+        row.  No host synchronisation is added.
+
+        ``weights``, ``loss``, ``param`` (those of ``SR_gradient``; single-output forests): the loss that is minimised, and returned,
+        is ``sum_d w_d rho(tree(x_d) - y_d) / sum_d w_d`` -- sample weights, a robust loss, or a 0/1 row that keeps held-out rows away
+        from the tuner (a row of weight 0 is not looked at).  ``method="lm"`` takes weights and no loss but ``"mse"``.  A tree whose loss
+        is NaN (``SR_gradient`` says when) keeps its constants.  With all three left at None the call is the unweighted one."""
         assert steps >= 0, f"steps should be >= 0, but got {steps}"
         if method not in ("descent", "lm"):
             raise ValueError(f"method should be 'descent' or 'lm', but got {method!r}")
-        source, gather = self._once_per_class(dedup)
+        if method == "lm" and loss not in (None, "mse"):
+            raise ValueError(f"method='lm' minimises the (weighted) mean squared error, but got loss={loss!r}")
         if method == "lm":
             if not use_MSE:
                 raise ValueError("method='lm' minimises the mean squared error: use_MSE must be True")
             self._single_output("method='lm'", ValueError)
         inputs, labels = self._sr_data(inputs, labels)
+        own = self._tuning_loss("optimize_constants", inputs, use_MSE, weights, loss, param)
+        source, gather = self._once_per_class(dedup)
         shape, hip = self._shape(inputs), torch.ops.evogp_hip
         if method == "lm":   # the model is the packed normal equations, the per-tree scalar is lambda
-            value, loss = source._tune(steps, damping, lambda *tree: hip.tree_SR_normal_eq(*shape, *tree, inputs, labels), hip.tree_SR_lm_step)
+            if own is None:
+                evaluate = lambda *tree: hip.tree_SR_normal_eq(*shape, *tree, inputs, labels)
+            else:
+                evaluate = lambda *tree: hip.tree_SR_weighted_normal_eq(*shape, *tree, inputs, labels, own[0])
+            value, loss = source._tune(steps, damping, evaluate, hip.tree_SR_lm_step)
         else:                # the model is the gradient, the per-tree scalar is the step length
-            value, loss = source._tune(steps, step_size, lambda *tree: hip.tree_SR_gradient(*shape, use_MSE, *tree, inputs, labels),
-                                       lambda phase, *rest: hip.tree_SR_const_step(phase, self.output_len, *rest))
+            if own is None:
+                evaluate = lambda *tree: hip.tree_SR_gradient(*shape, use_MSE, *tree, inputs, labels)
+            else:
+                evaluate = lambda *tree: hip.tree_SR_weighted_gradient(*shape, *tree, inputs, labels, *own)
+            value, loss = source._tune(steps, step_size, evaluate, lambda phase, *rest: hip.tree_SR_const_step(phase, self.output_len, *rest))
         if dedup:   # constants live in the prefix, which the rows of a class share; every row keeps its own tail words
             live = torch.arange(self.max_tree_len, device=value.device)[None, :] < self.batch_subtree_size[:, :1]
             value = torch.where(live, gather(value), value)

@@ -699,6 +699,42 @@ int evogp_hip_sr_weighted_loss(unsigned pop_size, unsigned data_points, unsigned
                                const float *labels, const float *weights /* nullable */, unsigned n_weights, int loss_kind,
                                double loss_param, float *loss, evogp_stream_t stream);
 
+/* Constant tuning under sample weights, robust losses and held-out rows (no counterpart in the reference):
+ * evogp_hip_sr_gradient and evogp_hip_sr_normal_eq for the loss evogp_hip_sr_weighted_loss scores by, on the rows it scores.  Single-
+ * output trees, one label column, ONE weight row w = f32[D], or NULL: every weight is 1.  p_d is the float32 prediction of the tape's
+ * forward walk, r_d = (double)p_d - (double)y_d, Wsum = sum_d w_d in float64 in the fixed order of evogp_hip_sr_weighted_loss (D without w).
+ *   loss[t]     = (float)( sum over the rows with w_d != 0 of w_d * rho(r_d) / Wsum ), rho in float64 as in evogp_hip_sr_weighted_loss;
+ *   grad[t][i]  = d loss[t] / d value[t][i] at every CONST node i, exactly 0.0f elsewhere and on the tail: the reverse walk of
+ *                 evogp_hip_sr_gradient seeded per row with (float)(w_d * rho'(r_d) / Wsum),
+ *                     mse 2 r;  mae sign(r), 0 at r == 0;  huber r for |r| <= delta, else delta * sign(r);
+ *                     pinball -tau for r < 0, 1 - tau for r > 0, 0 at r == 0;  logcosh tanh(r).
+ *                 Adjoints and their accumulators are float32, as in evogp_hip_sr_gradient;
+ *   normal[t]   (evogp_hip_sr_weighted_normal_eq, MSE) the 44 words of evogp_hip_sr_normal_eq over the same optimised constants:
+ *                 A_ij = sum_d w_d J_i J_j / Wsum, b_i = sum_d w_d J_i r_d / Wsum, with loss[t] = sum_d w_d r_d^2 / Wsum.
+ * Rules that decide a value exactly:
+ *   - a row with w_d == 0 is NOT LOOKED AT: the tree may be NaN, infinite or divide by zero there, and nothing of that row reaches the
+ *     loss, the gradient, A or b (a 64-row tile without a weighted row is not walked at all);
+ *   - the loss is NaN and the grad / normal row all zero when the tree is malformed, when a row WITH weight has a prediction that is
+ *     not finite (the rule of evogp_hip_sr_weighted_loss; evogp_hip_sr_gradient lets inf through), or when the weight row holds a
+ *     negative or non-finite weight or sums to 0 -- then for every tree.  The last is decided on the device by the one-workgroup kernel
+ *     of evogp_hip_sr_weighted_loss; nothing synchronises with the host.  evogp_hip_sr_const_step and evogp_hip_sr_lm_step never
+ *     accept a NaN loss and propose no move from one: such trees keep their constants;
+ *   - no float atomics: the same inputs give the same bits.  Rows are split among the waves as in evogp_hip_sr_gradient (the same plan),
+ *     a lane's loss terms are added in float64 in ascending tile order, the 64 lanes by the fixed butterfly, the waves in wave order;
+ *     the two calls see the same rows in the same order, so for EVOGP_LOSS_MSE their losses are equal bit for bit;
+ *   - multiplying every weight by a power of two changes no bit of any result (barring overflow and underflow).
+ * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, an unknown kind, a NaN loss_param, a delta that is not finite and
+ * positive, a tau outside (0, 1).  Then out_len != 1: EVOGP_E_UNSUPPORTED; then a NULL pointer other than weights: EVOGP_E_NULLPTR.
+ * Rows of more than 64 nodes use the per-stream tape buffer of evogp_hip_sr_gradient, under the same rules. */
+int evogp_hip_sr_weighted_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                   const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                   const float *labels, const float *weights /* nullable */, int loss_kind, double loss_param,
+                                   float *loss, float *grad, evogp_stream_t stream);
+int evogp_hip_sr_weighted_normal_eq(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                    const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                    const float *labels, const float *weights /* nullable */, float *loss, float *normal,
+                                    evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -781,7 +817,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
