@@ -346,6 +346,18 @@ std::tuple<Tensor, Tensor> tree_SR_linear_scaling(int64_t pop_size, int64_t data
     return {loss, coef};
 }
 
+// the weight rows of the weighted scoring passes: (K, data_points) float32 on the dataset's device with 1 <= K <= 8, or nullptr and
+// K = 1 without them
+static const float *weight_rows(const c10::optional<Tensor> &weights, int64_t data_points, const Dataset &d, int64_t *K) {
+    *K = 1;
+    if (!weights.has_value()) return nullptr;
+    TORCH_CHECK(weights->dim() == 2 && weights->size(0) >= 1 && weights->size(0) <= EVOGP_WLOSS_MAX_WEIGHTS,
+                "weights must be a (K, data_points) tensor with K in range [1, ", EVOGP_WLOSS_MAX_WEIGHTS, "], but got shape ", weights->sizes());
+    *K = weights->size(0);
+    check_tensor(*weights, {*K, data_points}, "weights", d.dev, at::kFloat);
+    return weights->data_ptr<float>();
+}
+
 // weighted / robust / held-out losses (evogp_hip_sr_weighted_loss): loss (pop, K) for weights (K, D), (pop, 1) without weights
 Tensor tree_SR_weighted_loss(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
                              const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
@@ -359,14 +371,7 @@ Tensor tree_SR_weighted_loss(int64_t pop_size, int64_t data_points, int64_t gp_l
     TORCH_CHECK(loss_kind != EVOGP_LOSS_PINBALL || (loss_param > 0.0 && loss_param < 1.0),
                 "loss_param (the tau of the pinball loss) must lie in (0, 1), but got ", loss_param);
     int64_t K = 1;
-    const float *w = nullptr;
-    if (weights.has_value()) {
-        TORCH_CHECK(weights->dim() == 2 && weights->size(0) >= 1 && weights->size(0) <= EVOGP_WLOSS_MAX_WEIGHTS,
-                    "weights must be a (K, data_points) tensor with K in range [1, ", EVOGP_WLOSS_MAX_WEIGHTS, "], but got shape ", weights->sizes());
-        K = weights->size(0);
-        check_tensor(*weights, {K, data_points}, "weights", d.dev, at::kFloat);
-        w = weights->data_ptr<float>();
-    }
+    const float *w = weight_rows(weights, data_points, d, &K);
     c10::DeviceGuard guard(d.dev);
     Tensor loss = empty({pop_size, K}, at::kFloat, d.dev);
     check_rc(evogp_hip_sr_weighted_loss((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, d.value,
@@ -374,6 +379,23 @@ Tensor tree_SR_weighted_loss(int64_t pop_size, int64_t data_points, int64_t gp_l
                                         current_stream(d.dev)),
              "tree_SR_weighted_loss");
     return loss;
+}
+
+// linear scaling fitted on weight row 0 and scored on every row (evogp_hip_sr_weighted_scaling): loss (pop, K) for weights (K, D),
+// (pop, 1) without weights; coef (pop, 2) = intercept, slope
+std::tuple<Tensor, Tensor> tree_SR_weighted_scaling(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len,
+                                                    const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                    const Tensor &labels, const c10::optional<Tensor> &weights) {
+    const Dataset d = check_dataset("tree_SR_weighted_scaling", OutLen::One, pop_size, data_points, gp_len, var_len, out_len, value, type, size, variables, labels);
+    int64_t K = 1;
+    const float *w = weight_rows(weights, data_points, d, &K);
+    c10::DeviceGuard guard(d.dev);
+    Tensor loss = empty({pop_size, K}, at::kFloat, d.dev), coef = empty({pop_size, 2}, at::kFloat, d.dev);
+    check_rc(evogp_hip_sr_weighted_scaling((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                           d.value, d.type, d.size, d.X, d.y, w, (unsigned)K, loss.data_ptr<float>(), coef.data_ptr<float>(),
+                                           current_stream(d.dev)),
+             "tree_SR_weighted_scaling");
+    return {loss, coef};
 }
 
 // the one weight row of the weighted tuning passes: (data_points,) float32 on the dataset's device, or nullptr without one
@@ -1188,6 +1210,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_weighted_loss(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights, int loss_kind, float loss_param) -> Tensor");
+    m.def("tree_SR_weighted_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_weighted_gradient(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y, Tensor? weights, int loss_kind, float loss_param) -> (Tensor loss, Tensor grad)");
     m.def("tree_SR_weighted_normal_eq(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
@@ -1242,6 +1266,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
+    m.impl("tree_SR_weighted_scaling", &tree_SR_weighted_scaling);
     m.impl("tree_SR_weighted_gradient", &tree_SR_weighted_gradient);
     m.impl("tree_SR_weighted_normal_eq", &tree_SR_weighted_normal_eq);
     m.impl("tree_SR_gene_fitness", &tree_SR_gene_fitness);

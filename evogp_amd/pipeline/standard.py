@@ -70,7 +70,12 @@ class StandardPipeline(BasePipeline):
             self.validation_stale += 1
             if top > self.best_validation_fitness:
                 self.best_validation_fitness = top
-                self.best_validation_tree = forest[int(torch.nonzero(held == top)[0])]
+                first = int(torch.nonzero(held == top)[0])
+                if getattr(self.problem, "linear_scaling", False):
+                    # as best_tree below: the model whose held-out error is stated, the tree with its TRAIN-fitted coefficients written in
+                    self.best_validation_tree = self.problem.scaled(forest[first:first + 1], dedup=False)[0]
+                else:
+                    self.best_validation_tree = forest[first]
                 self.validation_stale = 0
         host = fitness.cpu()
         best = int(torch.argmax(host))

@@ -29,7 +29,8 @@ class SymbolicRegression(BaseProblem):
                  max_depth: Optional[int] = None, max_complexity: Optional[int] = None, complexity_of=None, nested_constraints=None,
                  operand_constraints=None, structure_penalty: Optional[float] = None, loss: Optional[str] = None,
                  loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
-                 validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None):
+                 validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None,
+                 scaling_loss: Optional[str] = None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -89,14 +90,23 @@ class SymbolicRegression(BaseProblem):
         holds rows out: the same pass scores every tree twice, on the rows where the mask is False -- the loss that is evolved, masked
         and penalised as before -- and on the rows where it is True, kept on the device as ``last_validation_loss``;
         ``validation_scores(forest)`` returns the latter as scores, and StandardPipeline tracks ``best_validation_tree`` with it.  A
-        tree need not be defined on a row it is not scored on.  ``ValueError`` together with ``linear_scaling``, ``multigene`` or
+        tree need not be defined on a row it is not scored on.  ``ValueError`` together with ``linear_scaling`` (unless
+        ``scaling_loss="problem"``, below), ``multigene`` or
         ``simplify_every`` > 0 (those passes minimise the unweighted MSE / MAE), together with ``const_opt_steps`` > 0 unless
         ``const_opt_loss="problem"``, and from ``evaluate`` / ``scores`` with ``use_MSE=False`` while ``loss`` is set.
         ``const_opt_loss``: None (constant tuning minimises the unweighted MSE / MAE, as ever) or ``"problem"``: ``optimize`` tunes
         under the problem's own loss -- ``loss`` and ``loss_param`` (MSE when only weights or a mask are given), on the training weight
         row: ``sample_weights`` with the held-out rows at 0, which the tuner therefore never reads (``Forest.optimize_constants(weights=,
         loss=, param=)``).  ``const_opt_method="lm"`` takes no ``loss`` but ``"mse"`` there (``ValueError``); a problem with none of
-        the four loss options tunes as under None."""
+        the four loss options tunes as under None.
+        ``scaling_loss`` (needs ``linear_scaling``; mirrors ``const_opt_loss``): None (every ``ValueError`` above stays) or
+        ``"problem"``: linear scaling works under the problem's ``sample_weights`` and ``validation_mask``
+        (``Forest.SR_weighted_scaled_fitness``, one pass).  Slope and intercept are fitted on the training weight row --
+        ``sample_weights`` with the held-out rows at 0 -- and ``scaled_fitness``, ``scaled``, ``evaluate`` and ``scores`` state the
+        error of that model on that row; ``last_validation_loss`` and ``validation_scores`` state the error of THE SAME model on the
+        held-out rows, which the fit never read.  A closed form exists for the squared error only: ``loss`` other than None or
+        ``"mse"`` raises ``ValueError``.  The sign check of ``monotonic``, the masks and penalties, ``dedup`` and
+        ``const_opt_loss="problem"`` work on top of it; a problem with none of the four loss options scales as under None."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -191,10 +201,18 @@ class SymbolicRegression(BaseProblem):
         if const_opt_loss not in (None, "problem"):
             raise ValueError(f"const_opt_loss should be None or 'problem', but got {const_opt_loss!r}")
         self.const_opt_loss = const_opt_loss
+        if scaling_loss not in (None, "problem"):
+            raise ValueError(f"scaling_loss should be None or 'problem', but got {scaling_loss!r}")
+        if scaling_loss == "problem" and not self.linear_scaling:
+            raise ValueError("scaling_loss='problem' needs linear_scaling=True")
+        self.scaling_loss = scaling_loss
+        self._scaling_own = scaling_loss == "problem" and self._own_loss   # linear scaling under the problem's weight rows
+        if self._scaling_own and loss not in (None, "mse"):
+            raise ValueError(f"linear scaling has a closed form for the squared error only, but the problem's loss is {loss!r}")
         if self._own_loss:
             if const_opt_loss == "problem" and self.const_opt_method == "lm" and loss not in (None, "mse"):
                 raise ValueError(f"const_opt_method='lm' minimises the (weighted) mean squared error, but the problem's loss is {loss!r}")
-            for name, on in (("linear_scaling", self.linear_scaling), ("multigene", self.multigene),
+            for name, on in (("linear_scaling", self.linear_scaling and not self._scaling_own), ("multigene", self.multigene),
                              ("const_opt_steps > 0", self.const_opt_steps > 0 and const_opt_loss != "problem"),
                              ("simplify_every > 0", self.simplify_every > 0)):
                 if on:
@@ -332,7 +350,11 @@ class SymbolicRegression(BaseProblem):
     def scaled_fitness(self, forest: Forest, dedup: Optional[bool] = None):
         """``(loss, slope, intercept)`` of every tree under linear scaling on this problem's data: ``Forest.SR_scaled_fitness``, or
         under ``execute_mode="torch"`` the same definition from ``batch_forward``'s predictions in float64 torch.  ``dedup``: None takes
-        the problem's setting"""
+        the problem's setting.  Under ``scaling_loss="problem"``: ``Forest.SR_weighted_scaled_fitness`` (or its torch twin) on this
+        problem's weight rows -- the loss and the coefficients of the training row; the validation column of the same pass goes to
+        ``last_validation_loss``"""
+        if self._scaling_own:
+            return self._weighted_scaled_fitness(forest, dedup)
         if self.execute_mode != "torch":
             return self._slope_checked(*forest.SR_scaled_fitness(self.datapoints, self.labels,
                                                                  dedup=self.dedup if dedup is None else bool(dedup)))
@@ -355,6 +377,58 @@ class SymbolicRegression(BaseProblem):
         nan = torch.full_like(loss, float("nan"))
         return self._slope_checked(torch.where(bad, nan, loss), torch.where(bad, nan, b), torch.where(bad, nan, a))
 
+    def _weighted_scaled_fitness(self, forest: Forest, dedup: Optional[bool], keep_validation: bool = True):
+        W = self._loss_weights
+        if self.execute_mode != "torch":
+            loss, slope, intercept = forest.SR_weighted_scaled_fitness(self.datapoints, self.labels, W,
+                                                                       dedup=self.dedup if dedup is None else bool(dedup))
+        else:
+            loss, slope, intercept = self._weighted_scaling_torch(forest.batch_forward(self.datapoints)[:, :, 0], W)
+        if W is None:
+            return self._slope_checked(loss, slope, intercept)
+        if self.validation_mask is not None and keep_validation:
+            self.last_validation_loss = loss[:, 1]
+        return self._slope_checked(loss[:, 0].contiguous(), slope, intercept)
+
+    def _weighted_scaling_torch(self, p: Tensor, W: Optional[Tensor]):
+        """the definition of ``Forest.SR_weighted_scaled_fitness`` (include/evogp_hip.h evogp_hip_sr_weighted_scaling) on the
+        ``(pop, D)`` float32 predictions in two-pass float64 torch: ``(loss (pop, K) or (pop,) without W, slope, intercept)``"""
+        dev, f64 = p.device, torch.float64
+        y = self.labels.to(dev)[:, 0].to(f64)
+        Wd = torch.ones(1, p.shape[1], dtype=f64, device=dev) if W is None else W.to(dev).to(f64)
+        zero = torch.zeros((), dtype=f64, device=dev)
+        on = Wd != 0                                                    # (K, D): a row without weight is not looked at
+        wsum = Wd.sum(1)
+        usable = (torch.isfinite(Wd) & (Wd >= 0)).all(1) & (wsum != 0)
+        ybar0 = (Wd[0] * y).sum() / wsum[0]
+        v = y - ybar0
+        vbar = (Wd * v[None, :]).sum(1) / wsum                          # (K,)
+        dv = v[None, :] - vbar[:, None]                                 # (K, D)
+        V = (Wd * dv * dv).sum(1)
+        pd = p.to(f64)
+        pz = torch.where(on[None, :, :], pd[:, None, :], zero)          # (pop, K, D)
+        m = (Wd[None] * pz).sum(2) / wsum[None, :]                      # (pop, K)
+        dp = torch.where(on[None, :, :], pd[:, None, :] - m[:, :, None], zero)
+        M = (Wd[None] * dp * dp).sum(2)
+        c = (Wd[None] * dp * dv[None]).sum(2)
+        inf = torch.full((), float("inf"), dtype=p.dtype, device=dev)
+        mn = torch.where(on[0][None, :], p, inf).min(1).values
+        mx = torch.where(on[0][None, :], p, -inf).max(1).values
+        flat = (mn == mx) | (M[:, 0] <= 0) | (on[0].sum() == 1)
+        b = torch.where(flat, zero, c[:, 0] / M[:, 0])
+        a = torch.where(flat, ybar0 + vbar[0], ybar0 + vbar[0] - b * m[:, 0])
+        delta = b[:, None] * (m - m[:, :1]) - (vbar - vbar[0])[None, :]
+        num = b[:, None] ** 2 * M - 2.0 * b[:, None] * c + V[None, :] + wsum[None, :] * delta * delta
+        num[:, 0] = V[0] - b * c[:, 0]
+        loss = (torch.where(num < 0, zero, num) / wsum[None, :]).to(torch.float32)
+        af, bf = a.to(torch.float32), b.to(torch.float32)
+        bad = (on[None, :, :] & ~torch.isfinite(p)[:, None, :]).any(2)  # (pop, K)
+        dead = bad[:, 0] | ~usable[0] | ~torch.isfinite(af) | ~torch.isfinite(bf)
+        nan = float("nan")
+        loss = torch.where(dead[:, None] | bad | ~usable[None, :], torch.full_like(loss, nan), loss)
+        af, bf = torch.where(dead, torch.full_like(af, nan), af), torch.where(dead, torch.full_like(bf, nan), bf)
+        return (loss[:, 0] if W is None else loss), bf, af
+
     def _slope_checked(self, loss: Tensor, slope: Tensor, intercept: Tensor):
         """under a +-1 ``monotonic`` constraint a negative slope turns the proven direction round: such a tree fails (NaN loss)"""
         if self._sign_constrained:
@@ -363,8 +437,12 @@ class SymbolicRegression(BaseProblem):
 
     def scaled(self, forest: Forest, dedup: Optional[bool] = None) -> Forest:
         """``forest`` with every tree T rewritten as ``intercept + slope * T`` for its own least-squares coefficients on this problem's
-        data (``Forest.apply_scaling`` with ``grow=True``: rows four words longer, at most 1024)"""
-        _, slope, intercept = self.scaled_fitness(forest, dedup)
+        data (``Forest.apply_scaling`` with ``grow=True``: rows four words longer, at most 1024); under ``scaling_loss="problem"`` the
+        coefficients fitted on the training weight row (``last_validation_loss`` is left as it is)"""
+        if self._scaling_own:
+            _, slope, intercept = self._weighted_scaled_fitness(forest, dedup, keep_validation=False)
+        else:
+            _, slope, intercept = self.scaled_fitness(forest, dedup)
         return forest.apply_scaling(slope, intercept, grow=True)[0]
 
     def _check_scaling(self, use_MSE: bool):
@@ -468,6 +546,9 @@ class SymbolicRegression(BaseProblem):
         """``(loss, on_device)``: the positive loss of every tree under this problem's model, and whether a HIP pass over a device
         forest computed it (``scores`` then finishes it in one launch)"""
         on_device = self.execute_mode != "torch" and forest.batch_node_value.is_cuda
+        if self._scaling_own:
+            self._check_scaling(use_MSE)
+            return self.scaled_fitness(forest)[0], on_device
         if self._own_loss:
             if self.loss is not None and not use_MSE:
                 raise ValueError(f"this problem's loss is {self.loss!r}: use_MSE must be left True")

@@ -16,6 +16,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     subtrees              SR_subtree_errors, simplify: the loss of every subtree; the smaller tree that is no worse
     linear scaling        SR_scaled_fitness, apply_scaling: the loss under the least-squares slope and intercept; the tree with them
     weighted losses       SR_weighted_loss: sample weights, Huber / pinball / log-cosh, training and validation columns in one pass
+    weighted scaling      SR_weighted_scaled_fitness: linear scaling fitted on one weight row, scored on up to 8, in one pass
     multi-gene            SR_gene_fitness, SR_gene_moments, gene_predict: a tree's outputs as features of a least-squares model
     intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
@@ -541,23 +542,10 @@ class Forest:
                 applied.to(torch.bool))
 
     # ---- weighted, robust and held-out losses -----------------------------------------------------
-    def SR_weighted_loss(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor] = None, loss: str = "mse",
-                         param: Optional[float] = None, dedup: bool = False) -> Tensor:
-        """``(sum_d W[k, d] * rho(tree(x_d) - y_d)) / sum_d W[k, d]`` of every tree, float32, taken inside the evaluation kernel in one
-        pass (csrc/sr_wloss.hip): the ``(pop, D)`` predictions are never stored.  ``weights``: None (every weight 1) or ``(D,)`` gives
-        ``(pop,)``; ``(K, D)`` with ``1 <= K <= 8`` gives ``(pop, K)``, one column per weight row -- sample weights, a training and a
-        validation row of 0/1 masks, K folds -- for one interpretation of the trees.  ``loss``: ``"mse"``, ``"mae"``, ``"huber"``
-        (``param`` = delta > 0), ``"pinball"`` (``param`` = tau in (0, 1): the fit sits at the tau-quantile) or ``"logcosh"``; rho is
-        evaluated in float64 on the float32 predictions of ``batch_forward``.
-
-        A row with weight exactly 0 is not looked at in that column: the tree may be NaN or infinite there.  A column is NaN where a
-        row WITH weight has a non-finite prediction or the tree is malformed, and for every tree when its weight row holds a negative
-        or non-finite weight or sums to 0 (decided on the device: include/evogp_hip.h has the rules).  A column depends on its own
-        weight row only.  Deterministic from run to run, no host synchronisation; single-output forests.
-
-        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
-        self._single_output("SR_weighted_loss", ValueError)
-        param = check_loss(loss, param)
+    def _weight_rows(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor]):
+        """``(inputs, labels, weights, flat)`` as the weighted passes take them: float32 ``(D, input_len)``, ``(D, 1)`` and ``(K, D)`` or
+        None on the forest's device; ``flat``: no weights or one ``(D,)`` row, the result has no column axis.  ``ValueError`` for a shape
+        or a dtype"""
         dev = self.batch_node_value.device
         inputs, labels = check_tensor(inputs, dev), check_tensor(labels, dev)
         n = inputs.shape[0]
@@ -575,10 +563,56 @@ class Forest:
             if weights.dim() not in (1, 2) or weights.shape[-1] != n or (weights.dim() == 2 and not 1 <= weights.shape[0] <= WLOSS_MAX_WEIGHTS):
                 raise ValueError(f"weights shape should be ({n},) or (K, {n}) with 1 <= K <= {WLOSS_MAX_WEIGHTS}, but got {tuple(weights.shape)}")
             weights = weights.reshape(-1, n).contiguous().to(torch.float32)
+        return inputs, labels, weights, flat
+
+    def SR_weighted_loss(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor] = None, loss: str = "mse",
+                         param: Optional[float] = None, dedup: bool = False) -> Tensor:
+        """``(sum_d W[k, d] * rho(tree(x_d) - y_d)) / sum_d W[k, d]`` of every tree, float32, taken inside the evaluation kernel in one
+        pass (csrc/sr_wloss.hip): the ``(pop, D)`` predictions are never stored.  ``weights``: None (every weight 1) or ``(D,)`` gives
+        ``(pop,)``; ``(K, D)`` with ``1 <= K <= 8`` gives ``(pop, K)``, one column per weight row -- sample weights, a training and a
+        validation row of 0/1 masks, K folds -- for one interpretation of the trees.  ``loss``: ``"mse"``, ``"mae"``, ``"huber"``
+        (``param`` = delta > 0), ``"pinball"`` (``param`` = tau in (0, 1): the fit sits at the tau-quantile) or ``"logcosh"``; rho is
+        evaluated in float64 on the float32 predictions of ``batch_forward``.
+
+        A row with weight exactly 0 is not looked at in that column: the tree may be NaN or infinite there.  A column is NaN where a
+        row WITH weight has a non-finite prediction or the tree is malformed, and for every tree when its weight row holds a negative
+        or non-finite weight or sums to 0 (decided on the device: include/evogp_hip.h has the rules).  A column depends on its own
+        weight row only.  Deterministic from run to run, no host synchronisation; single-output forests.
+
+        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
+        self._single_output("SR_weighted_loss", ValueError)
+        param = check_loss(loss, param)
+        inputs, labels, weights, flat = self._weight_rows(inputs, labels, weights)
         source, gather = self._once_per_class(dedup)
         out = gather(torch.ops.evogp_hip.tree_SR_weighted_loss(*self._shape(inputs), *source._tensors(), inputs, labels, weights,
                                                                LOSS_KINDS[loss], 0.0 if param is None else param))
         return out[:, 0] if flat else out
+
+    # ---- linear scaling under sample weights, scored on held-out rows ------------------------------
+    def SR_weighted_scaled_fitness(self, inputs: Tensor, labels: Tensor, weights: Optional[Tensor] = None, dedup: bool = False):
+        """``(loss, slope, intercept)``: linear scaling (``SR_scaled_fitness``) fitted under sample weights and scored on up to 8
+        weight rows in ONE interpretation of the trees (csrc/sr_wscale.hip); the ``(pop, D)`` predictions are never stored.
+        ``weights``: None (every weight 1) or ``(D,)`` gives a ``(pop,)`` loss; ``(K, D)`` with ``1 <= K <= 8`` gives ``(pop, K)``.
+        **Row 0 is the fit row**: ``intercept + slope * tree(x)`` is the weighted least-squares fit on it, in closed form, float64.
+        Every row k, row 0 included, is then scored with those coefficients:
+        ``loss[:, k] = sum_d W[k, d] (intercept + slope * tree(x_d) - y_d)^2 / sum_d W[k, d]`` -- a training row and a validation row
+        of 0/1 masks give the held-out error of the model fitted WITHOUT the held-out rows.  ``slope`` and ``intercept`` are ``(pop,)``.
+
+        A tree that is constant over the rows row 0 weights (decided exactly, on the minimum and maximum prediction), or that has one
+        such row only, gets slope 0 and the weighted mean of the labels.  A data row with weight exactly 0 in a weight row is not looked
+        at there: the tree may be NaN or infinite on it.  Column k is NaN where a data row WITH weight in row k has a non-finite
+        prediction; if that is row 0, so are the coefficients and every column.  A malformed tree is NaN everywhere.  A weight row with
+        a negative or non-finite weight or a sum of 0 gives NaN: everywhere when it is row 0, in its own column otherwise (decided on
+        the device: include/evogp_hip.h has the rules).  Multiplying a weight row by a power of two changes no bit.  A column depends on
+        row 0 and its own row only.  Deterministic from run to run, no host synchronisation; single-output forests, squared error.
+
+        ``dedup=True``: the same bits with the pass run once per DISTINCT tree (``duplicate_classes``)."""
+        self._single_output("SR_weighted_scaled_fitness", ValueError)
+        inputs, labels, weights, flat = self._weight_rows(inputs, labels, weights)
+        source, gather = self._once_per_class(dedup)
+        loss, coef = torch.ops.evogp_hip.tree_SR_weighted_scaling(*self._shape(inputs), *source._tensors(), inputs, labels, weights)
+        loss, coef = gather(loss), gather(coef)
+        return (loss[:, 0] if flat else loss), coef[:, 1], coef[:, 0]
 
     # ---- multi-gene fitness ----------------------------------------------------------------------
     def _gene_data(self, what: str, inputs: Tensor, labels: Tensor):

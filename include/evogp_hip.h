@@ -735,6 +735,50 @@ int evogp_hip_sr_weighted_normal_eq(unsigned pop_size, unsigned data_points, uns
                                     const float *labels, const float *weights /* nullable */, float *loss, float *normal,
                                     evogp_stream_t stream);
 
+/* Linear scaling under sample weights with held-out scoring, in ONE pass over the dataset (no counterpart in the reference; DESIGN.md
+ * section 3.22).  Single-output trees, one label column, squared error.  weights is f32[K][D], 1 <= K <= EVOGP_WLOSS_MAX_WEIGHTS, or
+ * NULL with n_weights == 1: every weight is 1 and no weight is loaded.  Row 0 is the FIT row, rows 1 .. K-1 are SCORE rows: the
+ * least-squares a + b * T(x) is fitted on row 0 and every row, row 0 included, is scored with those coefficients -- a training row and a
+ * validation row of 0/1 masks give the held-out error of the model fitted without the held-out rows.
+ * p_d is the float32 prediction on row d (the bits evogp_hip_batch_evaluate stores).  All arithmetic is float64, the outputs are
+ * rounded once to float32.  With W_k = sum_d W[k][d],
+ *     ybar0 = sum_d W[0][d] y_d / W_0,        v_d = (double)y_d - ybar0,
+ * and per row k, over the data rows with W[k][d] != 0:  m_k the weighted mean of p,  M_k = sum w (p - m_k)^2,
+ * vbar_k = sum w v / W_k,  c_k = sum w (p - m_k)(v - vbar_k),  V_k = sum w (v - vbar_k)^2:
+ *   fit     b = c_0 / M_0,   a = ybar0 + vbar_0 - b m_0                                                  coef[t] = { a, b }
+ *   score   delta_k = b (m_k - m_0) - (vbar_k - vbar_0),
+ *           loss[t][k] = max(0, b^2 M_k - 2 b c_k + V_k + W_k delta_k^2) / W_k,   which is sum_d W[k][d] (a + b p_d - y_d)^2 / W_k with
+ *           the unrounded a, b; for k = 0 it is max(0, V_0 - b c_0) / W_0.
+ * Rules that decide a value exactly:
+ *   - flat: a tree is flat when min p == max p over the rows with W[0][d] != 0 (decided on the float32 values), or M_0 <= 0, or
+ *     exactly one row has weight in row 0.  Then b = 0, a = ybar0 + vbar_0, and every column uses the formula above with b = 0;
+ *   - a data row with W[k][d] == 0 is NOT LOOKED AT in column k: its prediction may be NaN or infinite, in the sums and in the
+ *     minimum and maximum of the flat rule alike;
+ *   - loss[t][k] is NaN when some row with W[k][d] != 0 has a prediction that is not finite.  If k == 0, the coefficients and every
+ *     column of that tree are NaN.  A malformed tree (the rule of evogp_hip_sr_linear_scaling) is NaN everywhere, and so is a tree whose
+ *     a or b is not finite as float32;
+ *   - a weight row that holds a negative or non-finite weight, or whose sum is 0, may not be used: if it is row 0, everything is NaN for
+ *     every tree; if it is row k > 0, column k is NaN for every tree and the rest is untouched.  A one-workgroup kernel in front decides
+ *     that on the device and leaves W_k (the order and the bits of evogp_hip_sr_weighted_loss), ybar0, vbar_k and V_k there:
+ *     nothing synchronises with the host;
+ *   - the sums are uncentred (sum w p, sum w p^2, sum w p v per column), every term carries the weight as a factor and enters its sum
+ *     by one fused multiply-add (a prediction that is not finite enters as 0: its columns are NaN by the rule above), so multiplying a
+ *     weight row by a power of two changes no bit of any output, barring overflow and underflow; any other positive factor changes
+ *     the outputs by rounding only;
+ *   - column k depends on the tree, the dataset, W[0] and W[k] only: not on K, the other weight rows, the other trees or the run.  It is
+ *     bit-identical from run to run, and weights == NULL gives the bits of a row of ones.
+ * No float atomics, no (pop, D) buffer.  Sums have the fixed order of evogp_hip_sr_linear_scaling: lane partials over the wave's row
+ * tiles in ascending order, the 64 lanes by a fixed butterfly, the waves in ascending order.  loss is f32[pop][K], coef f32[pop][2]
+ * (intercept, slope: what evogp_hip_wrap_linear takes).  The call can be captured into a HIP graph once one eager call on the stream
+ * has been made.
+ * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, n_weights outside 1 .. 8 or != 1 with weights == NULL.  Then
+ * out_len != 1: EVOGP_E_UNSUPPORTED; then a NULL pointer other than weights: EVOGP_E_NULLPTR.  Any gp_len <= 1024, var_len and
+ * data_points. */
+int evogp_hip_sr_weighted_scaling(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                  const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                  const float *labels, const float *weights /* nullable */, unsigned n_weights, float *loss /* [pop][K] */,
+                                  float *coef /* [pop][2]: intercept, slope */, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -817,7 +861,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
