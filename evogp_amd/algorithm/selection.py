@@ -36,9 +36,14 @@ class DefaultSelection(BaseSelection):
 
     def __call__(self, forest: Forest, fitness: torch.Tensor):
         """-> (elite_indices int32, survivor_indices int32), both prefixes of the descending order.
-        A stable sort is used so that replicated ranks of a sharded run agree on ties."""
+        A stable sort is used so that replicated ranks of a sharded run agree on ties.  NaN ranks worst, behind -inf, and -0 ties
+        with +0 -- the ranking of csrc/select.hip and parallel.select_order, so the fused step and this one choose the same two
+        sets.  (The reference's plain torch.sort(descending=True) puts NaN FIRST, selection/default.py:65: a tree without a
+        fitness would be its first elite.)"""
         n_elite, n_survive = self.counts(forest.pop_size)
-        order = torch.sort(fitness, descending=True, stable=True).indices
+        nan = fitness != fitness
+        by_value = torch.sort(torch.where(nan, float("-inf"), fitness), descending=True, stable=True).indices
+        order = by_value[torch.sort(nan[by_value].to(torch.int8), stable=True).indices]   # NaN behind -inf, both groups in order
         return order[:n_elite].to(torch.int32), order[:n_survive].to(torch.int32)
 
 

@@ -4,6 +4,7 @@ GeneticProgramming.step composes them (genetic_programming.py:105-124), on expli
 import numpy as np
 import pytest
 
+from default_step_replay import _expected  # (pinned to the reference's recorded runs by tests/test_default_step_parity.py)
 from helpers import ARITH, ALLF, assert_forest_equal, depth2leaf, roulette_uniform
 
 pytestmark = pytest.mark.gpu
@@ -21,36 +22,6 @@ def oracle():
     from oracle.pyoracle import Oracle
 
     return Oracle("port")
-
-
-def _expected(oracle, forest, order, rnd, below, n_elite, n_surv, donors, parents=None, pop=None):
-    """What the reference's operators produce for these draws (genetic_programming.py:110-122: elites = forest[elite indices],
-    parents drawn from forest[survivor indices] — a list that may repeat trees)."""
-    v, t, s = forest
-    pop = v.shape[0] if pop is None else pop
-    L = v.shape[1]
-    n_new = pop - n_elite
-    sizes = s[:, 0].astype(np.int64)
-    r = rnd.astype(np.int64)
-    parents = order if parents is None else parents
-    li = parents[r[0] % n_surv]
-    ri = parents[r[1] % n_surv]
-    p = (r[2] % sizes[li]).astype(np.int32)
-    q = (r[3] % sizes[ri]).astype(np.int32)
-    child = [a.copy() for a in oracle.crossover(v, t, s, li.astype(np.int32), ri.astype(np.int32), p, q)]
-    mut = r[4] < below
-    pm = np.full(n_new, -1, np.int32)
-    if mut.any():
-        cs = child[2][mut, 0].astype(np.int64)
-        pm_m = ((r[5][mut] % 1024) % cs).astype(np.int32)
-        pm[mut] = pm_m
-        res = oracle.mutate(child[0][mut], child[1][mut], child[2][mut], pm_m, donors[0][mut], donors[1][mut], donors[2][mut])
-        for a, b in zip(child, res):
-            a[mut] = b
-    elite = order[:n_elite]
-    out = tuple(np.concatenate([src[elite], ch]) for src, ch in zip((v, t, s), child))
-    dec = np.stack([li, ri, p, q, mut.astype(np.int64), pm], axis=1).astype(np.int32)
-    return out, dec
 
 
 @pytest.mark.parametrize("pop,L,mlc,dmlc,funcs,rate,elite_rate,surv_rate", [
