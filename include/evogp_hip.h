@@ -23,7 +23,9 @@
  *     type   int16   [pop][gp_len]   NodeType, bit 7 = OUT_NODE
  *     size   int16   [pop][gp_len]   subtree size, size[t][0] = live length of tree t
  * Output rows are written on [0, len) and zero-filled on [len, gp_len) (the reference leaves
- * the tail uninitialised: torch_wrapper.cu:64-66, generate.cu:167-172).
+ * the tail uninitialised: torch_wrapper.cu:64-66, generate.cu:167-172).  Words of an INPUT row behind
+ * size[t][0] may hold anything, and no result depends on them; where a function copies a row "as it is"
+ * or "unchanged", those words travel with it (tests/forest_invariance.py).
  *
  * No torch types, no C++ types: this header is plain C and is what a cgo / JNI / ctypes /
  * libtorch binding includes (INTEGRATION.md shows the libtorch and ctypes stubs).
