@@ -94,6 +94,9 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_twins": [_i],
     "evogp_hip_debug_tc_fold": [_i],
     "evogp_hip_debug_tc_end": [_i],
+    "evogp_hip_debug_tc_nanpeek": [_i],
+    "evogp_hip_debug_tc_nanpeek_raised": [],
+    "evogp_hip_debug_tc_batches": [_i, _i],
     "evogp_hip_debug_tc_table": [_i],
     "evogp_hip_debug_tc_table_entry": [_i, _i, C.POINTER(C.c_uint)],
     "evogp_hip_debug_profile": [_i],

@@ -59,9 +59,10 @@ The block is ONE `asm volatile` statement that never returns (it ends the wave).
   SGPR  s[8:9] records  s[10:11] fitness  s12 pop, then end of this XCD's dynamic region  s13 D  s14 LDS distance X->y  s15 tiles  s16 batch  s17 flags (bits 5-7, 17-30: trusted variables)
         s18 static phase  s19 record stride  s[20:21] jump target  s22 J = dword offset of the current instruction
         s23 H = K * stack height  s24 scatter M0 of the division / scratch  s25 tile  s26 b (tree in batch)
-        s27 trees in batch  s28 t0  s29 next dynamic t0 / program block  s[30:31] mask of evaluated trees
+        s27 trees in batch (peek builds: then trees visited)  s28 t0  s29 next dynamic t0 / program block  s[30:31] mask of evaluated trees
         s[32:33] record address  s[34:35] operands a, b  s[36:99] program window  s[100:101] scratch
         in/out operands of the statement: static cursor, static end, static stride, first dynamic tree, prefetch offset
+        the kernarg pointer's pair (an input, dead behind the prologue): peek builds keep the mask of the batch's trees still to visit there
   VGPR  v0 lane  v1 X base of the lane  v2 X base of the tile  v3 y address of the tile  v4,v5 addresses
         v6 error accumulator  v7 batch results (lane b = tree b)  v8 NaN  v9 scratch  v[10:11] counter address
         v12 grabbed t0  v13 warm-up offset  v[14:17] warm-up sink  v18..v23 division temporaries
@@ -117,6 +118,14 @@ LIBPK = True     # pow / sinh / cosh: the library's sequences over row PAIRS (ge
 RECGLC = False   # fused build: the record loads carry glc (EVOGP_TC_GEN_RECGLC=1) instead of one s_dcache_inv per batch
 CODEWARM = False  # EVOGP_TC_GEN_CODEWARM=1: every wave pulls the handler table and the bodies behind it into its XCD's L2 before it starts (experiment: 4-5 us SLOWER at 250 k - 1 M trees, no change at 125 k: profiles/r05Z_codewarm_ab.log)
 CNDE64 = False  # EVOGP_TC_GEN_CNDE64=1: every VOP2 v_cndmask_b32 ..., vcc in its 64-bit encoding (scripts/ubench/valu_rates.hip: the VOP2 form costs a SIMD ~4 issue slots of the VOP3 form)
+# NANPEEK (gen(peek=True), the K8 / K4 / K1 builds of the ordinary launches; flags bit 15 raises it per launch): at a batch's start lane b
+# loads word 0's first dword of record t0 + b; the lanes that find NAN_TREE there form the mask N.  They get their quiet NaN and their bit in
+# the mask of evaluated trees at once, and the tree loop walks the set bits of live = batch & ~N (s_ff1_i32_b64, s_bitset0_b64) instead of
+# counting b up to the batch's size: a NaN-proven tree costs no record fetch, no pass set-up and no dispatch.  `live` sits in the kernarg
+# pointer's register pair (dead behind the prologue), the batch's size register counts the visited trees from then on (the second-tree hook).
+# Without the flag N = 0, the walk visits the batch's trees in the parent's order, and the second-tree hook runs where the parent's ran (at
+# the second tree, never at the batch's end): the same loads, grabs and states as the parent's loop, a few scalar instructions apart.
+NANPEEK_BIT = 15
 KWARM = False  # scalar-cache warm-up of the next record (EVOGP_TC_GEN_KWARM=1 at generation time enables it): +1.5 % in round 2, -0.5 % since the division was rebuilt (profiles/r03E_div_range_ab.log)
 
 
@@ -168,8 +177,10 @@ def count_path(L, start, taken, idx_on=True, stop=()):
     return c
 
 
-def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
+def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False, peek=False):
     assert K % 4 == 0 or K == 1
+    # peek: the batch loop that settles NaN-proven trees without visiting them (NANPEEK above) -- the ordinary launches' builds
+    assert not peek or not (KWARM or stats or fused or wide)   # (KWARM sinks its loads into the register pair that holds `live`)
     assert 24 + 4 * K + K * DEPTH <= 256
     G = max(K // 4, 1)   # 1-KiB groups of a variable's tile: 64 lanes x 16 bytes (K = 1 uses the first row of every lane's four)
     RPL = min(K, 4)      # rows per lane and group
@@ -301,6 +312,49 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"global_load_dwordx4 v[14:17], v13, s[{T1}:{T2}]")
         a(f"global_load_dwordx4 v[14:17], v13, s[{T1}:{T2}] offset:1024")
 
+    LIVE = "%[karg]"   # (peek) mask of the batch's trees still to visit: the kernarg pointer's pair, dead behind the prologue
+
+    def batch_size(end):
+        """trees of the batch that starts at t0 and ends at `end` at the latest; (peek) their mask"""
+        a(f"s_sub_u32 s{sNB}, {end}, s{sT0}")
+        dyn_batch(T1)
+        a(f"s_min_u32 s{sNB}, s{sNB}, s{T1}")
+        if peek:
+            a(f"s_bfm_b64 {LIVE}, s{sNB}, 0")
+            a(f"s_cmp_lt_u32 s{sNB}, 64")              # (a field of 64 bits is a width of 0 to s_bfm)
+            a(f"s_cselect_b64 {LIVE}, {LIVE}, -1")
+
+    def peek_issue():
+        """(peek) lane b < trees in batch sends for word 0's first dword of record t0 + b -- lines that the warm-up loads of the previous
+        batch pulled towards L2.  Issued BEFORE the batch's grab and warm-up loads: see the wait at have_batch"""
+        skip = lab(f"no_peek_{len(sect[0])}")
+        a(f"s_bitcmp1_b32 s17, {NANPEEK_BIT}")
+        a(f"s_cbranch_scc0 {skip}")
+        rec_addr(T1, T2, f"s{sT0}", T1)
+        a("v_mul_lo_u32 v5, v0, s19")
+        a(f"s_mov_b64 exec, {LIVE}")
+        a(f"global_load_dword v18, v5, s[{T1}:{T2}]")
+        a("s_mov_b64 exec, -1")
+        a(f"{skip}:")
+
+    def next_live(none):
+        """(peek) b = the lowest tree still to visit, taken off the mask; to `none` when there is none"""
+        a(f"s_cmp_eq_u64 {LIVE}, 0")
+        a(f"s_cbranch_scc1 {none}")
+        a(f"s_ff1_i32_b64 s{sB}, {LIVE}")
+        a(f"s_bitset0_b64 {LIVE}, s{sB}")
+
+    def next_in_batch(none):
+        """T2 = number in the batch of the tree the loop takes after the current one (the early record fetch); to `none` when there is none"""
+        if peek:
+            a(f"s_cmp_eq_u64 {LIVE}, 0")
+            a(f"s_cbranch_scc1 {none}")
+            a(f"s_ff1_i32_b64 s{T2}, {LIVE}")
+        else:
+            a(f"s_add_u32 s{T2}, s{sB}, 1")
+            a(f"s_cmp_lt_u32 s{T2}, s{sNB}")
+            a(f"s_cbranch_scc0 {none}")
+
     def dyn_batch(dst):
         """trees per DYNAMIC batch = batch >> flags[9:8] (at least 1): the tail is handed out in smaller pieces"""
         a(f"s_bfe_u32 s{T2}, s17, 0x20008")
@@ -324,6 +378,21 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"v_mov_b32 v4, {STRIDE}")
         a("ds_add_rtn_u32 v12, v4, v9")
         a("s_mov_b64 exec, -1")
+
+    def second_tree_hook(tag, done):
+        """a pool batch (s18 == 1) whose grab has landed: the NEXT batch is known -- warm its records, or send the region's grab"""
+        a(f"v_readfirstlane_b32 s{sT0N}, v12")
+        a(f"s_add_u32 s{sT0N}, s{sT0N}, {CUR}")
+        a(f"s_cmp_lt_u32 s{sT0N}, {END_}")
+        a(f"s_cbranch_scc0 {lab('pool_dry' + tag)}")
+        warm(f"s{sT0N}")
+        a(f"s_branch {done}")
+        # ... or the pool has run dry: this wave's next batch comes from its XCD's region, and the grab goes out now -- a tree ahead of
+        # its use, and at a moment of this wave's own (left to the batch's end, all waves of a workgroup -- of most workgroups -- would
+        # queue at the counters together, with nothing to do meanwhile)
+        a(f"{lab('pool_dry' + tag)}:")
+        grab()
+        a("s_mov_b32 s18, 2")
 
     # ------------------------------------------------------------------ prologue
     if fused:
@@ -405,7 +474,7 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"s_mov_b32 {DYN}, s{P2_}")                 # first tree of the dynamic region
         # one dynamic region and one counter line per XCD: region = XCC_ID & flags[15:12], s18 still holds trees per region
         a(f"s_getreg_b32 s{P1_}, hwreg(HW_REG_XCC_ID, 0, 4)")
-        a(f"s_bfe_u32 s{P2_}, s17, 0x4000c")
+        a(f"s_bfe_u32 s{P2_}, s17, 0x3000c")
         a(f"s_and_b32 s{P1_}, s{P1_}, s{P2_}")
         a(f"s_mul_i32 s{P2_}, s{P1_}, s18")
         a(f"s_add_u32 {DYN}, {DYN}, s{P2_}")          # first tree of this XCD's region
@@ -452,11 +521,13 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"s_mov_b32 s{sT0}, s{sT0N}")
         a(f"s_cmp_lt_u32 s{sT0}, {END_}")
         a(f"s_cbranch_scc0 {lab('to_dyn')}")
+        if peek:
+            batch_size(END_)
+            peek_issue()
         pool_grab()                                    # the next batch, one batch ahead: consumed behind this batch's second tree
         warm(f"s{sT0}")
-        a(f"s_sub_u32 s{sNB}, {END_}, s{sT0}")
-        dyn_batch(T1)
-        a(f"s_min_u32 s{sNB}, s{sNB}, s{T1}")
+        if not peek:
+            batch_size(END_)
         a(f"s_branch {lab('have_batch')}")
         # the pool is used up (every wave of the workgroup finds that out by itself, a batch after its last one): the rest of the launch
         # comes from this XCD's region.  The one grab whose latency nothing hides.
@@ -472,15 +543,45 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a(f"s_mov_b32 s{sT0}, s{sT0N}")
         a(f"s_cmp_ge_u32 s{sT0}, s12")
         a(f"s_cbranch_scc1 {lab('exit')}")
+        if peek:
+            batch_size("s12")
+            peek_issue()
         grab()                                         # the next batch, consumed at the end of this one
         warm(f"s{sT0}")
-        a(f"s_sub_u32 s{sNB}, s12, s{sT0}")
-        dyn_batch(T1)
-        a(f"s_min_u32 s{sNB}, s{sNB}, s{T1}")
+        if not peek:
+            batch_size("s12")
     a(f"{lab('have_batch')}:")
-    a(f"s_mov_b32 s{sB}, 0")
     a(f"s_mov_b64 s[{sOK}:{sOK + 1}], 0")
     a("v_mov_b32 v7, 0")
+    if peek:
+        # SETTLE.  The peek is the OLDEST of this batch's vector-memory operations: behind it went the two warm-up loads, and in front of
+        # those, from an XCD's region (s18 == 0), the grab of the next batch -- loads and atomics with a result return in order, so a wait
+        # for "as many as were issued behind it" is a wait for the peek and for nothing younger (the warm-up loads and the grab stay in
+        # flight, as the batch's end wants them).  The previous batch's fitness store and whatever else is older can only make the wait
+        # longer, never shorter.  v18 is a division temporary: no program runs between the load and this read.
+        nw = 2 if L2WARM else 0
+        a(f"s_mov_b32 s{sNB}, 0")                      # from here on: trees of this batch the loop has visited
+        a(f"s_bitcmp1_b32 s17, {NANPEEK_BIT}")
+        a(f"s_cbranch_scc0 {lab('first_tree')}")       # (no peek in this launch: N = 0)
+        a("s_cmp_eq_u32 s18, 1")
+        a(f"s_cbranch_scc1 {lab('peek_pool')}")
+        a(f"s_waitcnt vmcnt({nw + 1})")
+        a(f"s_branch {lab('peek_here')}")
+        a(f"{lab('peek_pool')}:")
+        a(f"s_waitcnt vmcnt({nw})")
+        a(f"{lab('peek_here')}:")
+        a("v_and_b32 v18, 0xffff, v18")                # the handler's offset in the table: what tc_word0 puts into bits 0-15 (word 0: flavour 0)
+        a(f"v_cmp_eq_u32 vcc, {hex(SLOT * hid['nan_tree'])}, v18")
+        a("v_mov_b32 v9, 0x7fc00000")
+        a(f"s_and_b64 vcc, vcc, {LIVE}")               # N (the lanes behind the batch hold nothing)
+        a(f"s_andn2_b64 {LIVE}, {LIVE}, vcc")
+        a(f"s_mov_b64 s[{sOK}:{sOK + 1}], vcc")        # what NAN_TREE does, for all of N at once: evaluated, THE quiet NaN in lane b
+        a("s_nop 1")
+        a("v_cndmask_b32 v7, v7, v9, vcc")
+        a(f"{lab('first_tree')}:")
+        next_live(lab('batch_end'))
+    else:
+        a(f"s_mov_b32 s{sB}, 0")
     # ------------------------------------------------------------------ tree loop
     a(f"{lab('tree')}:")
     if fused:
@@ -498,22 +599,16 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     if not fused:
         # the second tree of a pool batch: the grab made at the batch's start has landed (nothing is in flight behind the wait above),
         # so the NEXT batch is known -- its records are pulled into L2 while the rest of this one runs
-        a(f"s_cmp_eq_u32 s{sB}, 1")
+        if peek:
+            # (the second tree the loop VISITS: a batch with fewer than two such trees comes to the same lines at its end, see batch_end)
+            a(f"s_add_u32 s{sNB}, s{sNB}, 1")
+            a(f"s_cmp_eq_u32 s{sNB}, 2")
+        else:
+            a(f"s_cmp_eq_u32 s{sB}, 1")
         a(f"s_cbranch_scc0 {lab('no_prewarm')}")
         a("s_cmp_eq_u32 s18, 1")
         a(f"s_cbranch_scc0 {lab('no_prewarm')}")
-        a(f"v_readfirstlane_b32 s{sT0N}, v12")
-        a(f"s_add_u32 s{sT0N}, s{sT0N}, {CUR}")
-        a(f"s_cmp_lt_u32 s{sT0N}, {END_}")
-        a(f"s_cbranch_scc0 {lab('pool_dry')}")
-        warm(f"s{sT0N}")
-        a(f"s_branch {lab('no_prewarm')}")
-        # ... or the pool has run dry: this wave's next batch comes from its XCD's region, and the grab goes out now -- a tree ahead of
-        # its use, and at a moment of this wave's own (left to the batch's end, all waves of a workgroup -- of most workgroups -- would
-        # queue at the counters together, with nothing to do meanwhile)
-        a(f"{lab('pool_dry')}:")
-        grab()
-        a("s_mov_b32 s18, 2")
+        second_tree_hook("", lab('no_prewarm'))
         a(f"{lab('no_prewarm')}:")
     if stats:
         a(f"v_add_u32 v{A_TREES}, 1, v{A_TREES}")
@@ -2162,7 +2257,7 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         a("global_store_dword v[10:11], v9, off")         # (v[10:11]: word 0 of the scratch block itself)
     else:
         a(f"s_getreg_b32 s{T1}, hwreg(HW_REG_XCC_ID, 0, 4)")
-        a(f"s_bfe_u32 s{T2}, s17, 0x4000c")
+        a(f"s_bfe_u32 s{T2}, s17, 0x3000c")
         a(f"s_and_b32 s{T1}, s{T1}, s{T2}")
         a(f"s_lshl_b32 s{T1}, s{T1}, 7")
         a(f"s_add_u32 s{T1}, s{T1}, 128")                 # this XCD's counter line -> word 0 of the scratch block
@@ -2330,9 +2425,7 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
         """the tree's last tile, nothing in flight: send for the record of the batch's next tree (END below; flags bit 10 tells tree_done)"""
         if not EARLYREC or stats:
             return
-        a(f"s_add_u32 s{T2}, s{sB}, 1")
-        a(f"s_cmp_lt_u32 s{T2}, s{sNB}")
-        a(f"s_cbranch_scc0 {lab('no_early_' + tag)}")
+        next_in_batch(lab('no_early_' + tag))
         if not fused:
             a(f"s_add_u32 s{T2}, s{T2}, s{sT0}")
         rec_addr(sREC, sREC + 1, f"s{T2}", T2)
@@ -2422,9 +2515,7 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
             # set by the host for single-output launches, tells tree_done that it did)
             a(f"s_cmp_lt_u32 s{T1}, s15")
             a(f"s_cbranch_scc1 {lab(f'no_early{fl}')}")
-            a(f"s_add_u32 s{T2}, s{sB}, 1")
-            a(f"s_cmp_lt_u32 s{T2}, s{sNB}")
-            a(f"s_cbranch_scc0 {lab(f'no_early{fl}')}")
+            next_in_batch(lab(f'no_early{fl}'))
             if not fused:
                 a(f"s_add_u32 s{T2}, s{T2}, s{sT0}")
             rec_addr(sREC, sREC + 1, f"s{T2}", T2)
@@ -2517,17 +2608,38 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     a(f"s_bitset1_b64 s[{sOK}:{sOK + 1}], s{sB}")
     a(f"v_writelane_b32 v7, s{T1}, m0")
     if EARLYREC and not stats:
-        a(f"s_add_u32 s{sB}, s{sB}, 1")
-        a(f"s_cmp_lt_u32 s{sB}, s{sNB}")
-        a(f"s_cbranch_scc0 {lab('batch_end')}")
+        if peek:
+            next_live(lab('batch_end'))            # (the tree END has sent for: the same lowest bit of the mask)
+        else:
+            a(f"s_add_u32 s{sB}, s{sB}, 1")
+            a(f"s_cmp_lt_u32 s{sB}, s{sNB}")
+            a(f"s_cbranch_scc0 {lab('batch_end')}")
         a("s_bitcmp1_b32 s17, 10")                 # single-output launch: END has sent for this tree's record
         a(f"s_cbranch_scc1 {lab('tree_loaded')}")
         a(f"s_branch {lab('tree')}")
     a(f"{lab('next_tree')}:")
-    a(f"s_add_u32 s{sB}, s{sB}, 1")
-    a(f"s_cmp_lt_u32 s{sB}, s{sNB}")
-    a(f"s_cbranch_scc1 {lab('tree')}")
+    if peek:
+        next_live(lab('batch_end'))
+        a(f"s_branch {lab('tree')}")
+    else:
+        a(f"s_add_u32 s{sB}, s{sB}, 1")
+        a(f"s_cmp_lt_u32 s{sB}, s{sNB}")
+        a(f"s_cbranch_scc1 {lab('tree')}")
     a(f"{lab('batch_end')}:")
+    if peek:
+        # a pool batch in which the loop visited fewer than two trees has not looked at its grab yet: the second-tree hook runs here, so
+        # that the next batch's records are warmed -- or, the pool dry, the region's grab is on its way -- before the lines below take it.
+        # Only in a launch that peeks: without the flag a batch of one tree goes on as the parent's did, hook never run (the pool's grab is
+        # read below; a dry pool is found at the next batch's start, to_dyn)
+        a(f"s_bitcmp1_b32 s17, {NANPEEK_BIT}")
+        a(f"s_cbranch_scc0 {lab('hooked')}")
+        a(f"s_cmp_ge_u32 s{sNB}, 2")
+        a(f"s_cbranch_scc1 {lab('hooked')}")
+        a("s_cmp_eq_u32 s18, 1")
+        a(f"s_cbranch_scc0 {lab('hooked')}")
+        a("s_waitcnt lgkmcnt(0)")                  # (the pool's grab: an LDS operation)
+        second_tree_hook("_end", lab('hooked'))
+        a(f"{lab('hooked')}:")
     # batch finished: everything outstanding has long landed (warm-up load, the next dynamic grab); take the grab
     # first, then mean = sum / D and one coalesced store for the evaluated trees
     tick_begin()
@@ -2674,6 +2786,11 @@ def gen(K, DEPTH, stats=False, fast=0, info=None, fused=False, wide=False):
     : [karg] "s"(karg_) \\
     : {clob_txt})
 '''
+    # ([karg] is an input the statement overwrites in its peek builds -- `live`, see LIVE -- and, with KWARM, sinks loads into: legal only
+    # because the statement ends the wave.  Nothing behind the prologue may read the kernarg pointer there; the stats build, which does at
+    # its exit, is never a peek build: the assert at the top of gen())
+    if peek:
+        out = out.replace("  asm volatile( \\\n", "  /* [karg] does not survive the prologue: the batch loop keeps its mask of trees to visit in that register pair */ \\\n  asm volatile( \\\n", 1)
     return out
 
 
@@ -2708,7 +2825,7 @@ if __name__ == "__main__":
         with open(f"{outdir}/tc_interp_k{K}.inc", "w") as f:
             for fast, tag in ((0, "ieee"), (1, "fast"), (2, "short")):  # division: IEEE / no range scaling / one correction
                 info = {}
-                f.write(gen(K, depth, fast=fast, info=info))
+                f.write(gen(K, depth, fast=fast, info=info, peek=True))
                 table[f"K{K}_{tag}"] = info
             if K == 8:
                 for fast in (0, 1, 2):   # the fused build (one batch per entry, sr_fused_kernel)

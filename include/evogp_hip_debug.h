@@ -54,6 +54,19 @@ int evogp_hip_debug_tc_fold(int mode);
  * other launch; -1 = back to the default / the environment (EVOGP_TC_END = 0 or 1 before the first call; unset: 1).  The fitness words do
  * not depend on the choice (tests/test_gpu_tc_end.py compares them bit for bit). */
 int evogp_hip_debug_tc_end(int mode);
+/* Whether a launch whose records the packed compiler wrote with NAN_TREE words allowed (evogp_hip_debug_tc_fold >= 1) tells the interpreter
+ * to peek at every record's first dword at a batch's start and to settle the NaN-proven trees there, without fetching their records or
+ * visiting them: -1 = by the launch's trees per CU (DEFAULT: from 900 on; the environment variable EVOGP_TC_NANPEEK =
+ * 0 / 2 sets never / always before the first call); 0 = never: every tree is visited and NAN_TREE runs as a handler; 1 = always.  The
+ * records and the fitness words do not depend on the choice (tests/test_gpu_tc_nanpeek.py compares them bit for bit).  _raised: 1 when the
+ * most recent interpreter launch carried the flag. */
+int evogp_hip_debug_tc_nanpeek(int mode);
+int evogp_hip_debug_tc_nanpeek_raised(void);
+/* Trees per batch of the interpreter's waves (1 .. 64; 0 = the default: 8, 2 with one row per lane, or EVOGP_TC_BATCH) and the shift that
+ * makes the batches a wave draws that much smaller (0 .. 3; -1 = the default: by the launch's size, or EVOGP_TC_DYNSHIFT).  Small
+ * populations draw single trees by default; tests set the headline launch's geometry (8, 0) to run its batch loop on a small forest.  The
+ * fitness words do not depend on the choice. */
+int evogp_hip_debug_tc_batches(int batch, int dyn_shift);
 /* Whether the packed compiler's arithmetic line takes a word's handler, its twin, its in-place form, "kept", "uses a variable" and the stack
  * delta from its word table -- one class code per lane, one LDS read (csrc/sr_tc.hip tc_table_entry) -- or from the
  * selects of before: 1 = the table; 0 = the selects; -1 = back to the default / the environment (EVOGP_TC_TABLE = 0 or 1 before the first
