@@ -646,6 +646,65 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_derivative_inter
     return {vlo, vhi, vflags, dlo, dhi, dflags};
 }
 
+// the prologue of the two input-gradient ops: the forest, X (D, var_len) and the requested variables (checked here: the C entry reads
+// wrt on the host); returns D and var_len
+struct XgradCall {
+    Forest f;
+    int64_t D, var_len, V;
+    int wrt[EVOGP_XGRAD_MAX_VARS];
+};
+
+XgradCall check_xgrad(const char *op, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, at::IntArrayRef wrt) {
+    XgradCall c{Forest::infer(value, type, size), 0, 0, 0, {}};
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, "too many data points: ", variables.size(0));
+    c.D = variables.size(0), c.var_len = variables.size(1), c.V = (int64_t)wrt.size();
+    check_tensor(variables, {c.D, c.var_len}, "variables", c.f.dev, at::kFloat);
+    TORCH_CHECK(c.V >= 1 && c.V <= EVOGP_XGRAD_MAX_VARS, op, ": wrt must hold 1 to ", EVOGP_XGRAD_MAX_VARS, " variables, but got ", c.V);
+    for (int64_t k = 0; k < c.V; ++k) {
+        TORCH_CHECK(wrt[k] >= 0 && wrt[k] < c.var_len, op, ": wrt[", k, "] must be in range [0, ", c.var_len, "), but got ", wrt[k]);
+        for (int64_t j = 0; j < k; ++j) TORCH_CHECK(wrt[j] != wrt[k], op, ": wrt holds variable ", wrt[k], " twice");
+        c.wrt[k] = (int)wrt[k];
+    }
+    return c;
+}
+
+// (pred (pop, D), dpred (V, pop, D)) float32: the prediction and its partial derivatives in the variables wrt on every data row
+// (evogp_hip_sr_input_gradient)
+std::tuple<Tensor, Tensor> tree_SR_input_gradient(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                  at::IntArrayRef wrt) {
+    const XgradCall c = check_xgrad("tree_SR_input_gradient", value, type, size, variables, wrt);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor pred = empty({c.f.pop, c.D}, at::kFloat, c.f.dev), dpred = empty({c.V, c.f.pop, c.D}, at::kFloat, c.f.dev);
+    check_rc(evogp_hip_sr_input_gradient((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type,
+                                         c.f.size, variables.data_ptr<float>(), (unsigned)c.V, c.wrt, pred.data_ptr<float>(),
+                                         dpred.data_ptr<float>(), current_stream(c.f.dev)),
+             "tree_SR_input_gradient");
+    return {pred, dpred};
+}
+
+// (loss (pop, 1 + V) float32, violations (pop, V) int32): the squared error of the prediction and of every requested derivative against
+// dlabels (D, V) (None: zeros), and the rows whose derivative leaves [dmin, dmax] ((V,) each; None: unbounded) (evogp_hip_sr_derivative_loss)
+std::tuple<Tensor, Tensor> tree_SR_derivative_loss(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                   const Tensor &labels, const c10::optional<Tensor> &dlabels, at::IntArrayRef wrt,
+                                                   const c10::optional<Tensor> &dmin, const c10::optional<Tensor> &dmax) {
+    const XgradCall c = check_xgrad("tree_SR_derivative_loss", value, type, size, variables, wrt);
+    check_tensor(labels, {c.D, 1}, "labels", c.f.dev, at::kFloat);
+    if (dlabels.has_value()) check_tensor(*dlabels, {c.D, c.V}, "dlabels", c.f.dev, at::kFloat);
+    if (dmin.has_value()) check_tensor(*dmin, {c.V}, "dmin", c.f.dev, at::kFloat);
+    if (dmax.has_value()) check_tensor(*dmax, {c.V}, "dmax", c.f.dev, at::kFloat);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor loss = empty({c.f.pop, 1 + c.V}, at::kFloat, c.f.dev), viol = empty({c.f.pop, c.V}, at::kInt, c.f.dev);
+    check_rc(evogp_hip_sr_derivative_loss((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type,
+                                          c.f.size, variables.data_ptr<float>(), labels.data_ptr<float>(),
+                                          dlabels.has_value() ? dlabels->data_ptr<float>() : nullptr, (unsigned)c.V, c.wrt,
+                                          dmin.has_value() ? dmin->data_ptr<float>() : nullptr, dmax.has_value() ? dmax->data_ptr<float>() : nullptr,
+                                          loss.data_ptr<float>(), viol.data_ptr<int>(), current_stream(c.f.dev)),
+             "tree_SR_derivative_loss");
+    return {loss, viol};
+}
+
 // (units int32 (pop, gp_len, n_dims), flags uint8 (pop, gp_len), violations int32 (pop,)): the unit of every subtree, the variables carrying
 // var_units (var_len, n_dims) and, with check_root, the root held to label_units (n_dims,) (evogp_hip_tree_dimensions)
 std::tuple<Tensor, Tensor, Tensor> tree_dimensions(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &var_units,
@@ -1224,6 +1283,9 @@ TORCH_LIBRARY(evogp_hip, m) {
           " -> (Tensor value, Tensor node_type, Tensor subtree_size, Tensor applied)");
     m.def("tree_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper) -> (Tensor lo, Tensor hi, Tensor flags)");
     m.def("tree_derivative_intervals(Tensor value, Tensor node_type, Tensor subtree_size, Tensor lower, Tensor upper, Tensor wrt) -> (Tensor vlo, Tensor vhi, Tensor vflags, Tensor dlo, Tensor dhi, Tensor dflags)");
+    m.def("tree_SR_input_gradient(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, int[] wrt) -> (Tensor pred, Tensor dpred)");
+    m.def("tree_SR_derivative_loss(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor? dlabels, int[] wrt,"
+          " Tensor? dmin, Tensor? dmax) -> (Tensor loss, Tensor violations)");
     m.def("tree_dimensions(Tensor value, Tensor node_type, Tensor subtree_size, Tensor var_units, Tensor label_units, bool check_root) -> (Tensor units, Tensor flags, Tensor violations)");
     m.def("tree_structure(Tensor value, Tensor node_type, Tensor subtree_size, Tensor cost, Tensor operand_limit, Tensor rule_outer, Tensor rule_inner, Tensor rule_limit, int max_depth, int max_complexity)"
           " -> (Tensor complexity, Tensor height, Tensor depth, Tensor nest, Tensor flags, Tensor violations)");
@@ -1274,6 +1336,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_wrap_linear", &tree_wrap_linear);
     m.impl("tree_intervals", &tree_intervals);
     m.impl("tree_derivative_intervals", &tree_derivative_intervals);
+    m.impl("tree_SR_input_gradient", &tree_SR_input_gradient);
+    m.impl("tree_SR_derivative_loss", &tree_SR_derivative_loss);
     m.impl("tree_dimensions", &tree_dimensions);
     m.impl("tree_structure", &tree_structure);
 }

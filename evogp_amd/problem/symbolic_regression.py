@@ -30,7 +30,8 @@ class SymbolicRegression(BaseProblem):
                  operand_constraints=None, structure_penalty: Optional[float] = None, loss: Optional[str] = None,
                  loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
                  validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None,
-                 scaling_loss: Optional[str] = None):
+                 scaling_loss: Optional[str] = None, derivative_labels: Optional[Tensor] = None, derivative_wrt=None,
+                 derivative_weight=1.0, sampled_monotonic=None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -106,7 +107,21 @@ class SymbolicRegression(BaseProblem):
         error of that model on that row; ``last_validation_loss`` and ``validation_scores`` state the error of THE SAME model on the
         held-out rows, which the fit never read.  A closed form exists for the squared error only: ``loss`` other than None or
         ``"mse"`` raises ``ValueError``.  The sign check of ``monotonic``, the masks and penalties, ``dedup`` and
-        ``const_opt_loss="problem"`` work on top of it; a problem with none of the four loss options scales as under None."""
+        ``const_opt_loss="problem"`` work on top of it; a problem with none of the four loss options scales as under None.
+        ``derivative_labels``, ``derivative_wrt``, ``derivative_weight`` (derivative-informed fitness; labels of shape ``(D, 1)``):
+        ``derivative_labels`` ``(D, V)`` holds measured or known values of d y / d x_v on the datapoints for the variables
+        ``derivative_wrt`` (an int or a list of V distinct variables, at most 8; None: every variable, in order).  ``evaluate`` /
+        ``scores`` then return ``-(loss_0 + sum_k weight_k * loss_k)`` with the columns of ``Forest.SR_derivative_loss``: the mean
+        squared error of the prediction and of each partial derivative, in one pass (``execute_mode`` plays no part in it);
+        ``derivative_weight`` is a float or a ``(V,)`` sequence, finite and >= 0.  ``derivative_loss(forest)`` returns the raw columns.
+        ``ValueError`` together with ``linear_scaling``, ``multigene``, ``loss`` / ``loss_param`` / ``sample_weights`` /
+        ``validation_mask``, ``const_opt_steps`` > 0 or ``simplify_every`` > 0 (those closed forms and tuners do not know the
+        derivative columns), and from ``evaluate`` / ``scores`` with ``use_MSE=False``.
+        ``sampled_monotonic`` (sampled shape constraints; single-output problems): ``{variable: +1 | -1 | (dmin, dmax)}`` as for
+        ``monotonic``, but held on the ROWS of the dataset instead of proven on a box: a tree whose partial derivative in the variable
+        leaves its range, or is NaN, on any datapoint gets NaN from ``evaluate`` and -inf from ``scores`` (the optimistic companion
+        of ``monotonic``; the two may be combined).  Alone it only masks: the fitness of the other trees is the plain one, bit for
+        bit.  Its variables are appended to ``derivative_wrt`` where that lacks them (they carry no label and no weight)."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -247,6 +262,70 @@ class SymbolicRegression(BaseProblem):
             elif w is not None:
                 self._loss_weights = w[None, :].contiguous()
 
+        self._init_derivatives(derivative_labels, derivative_wrt, derivative_weight, sampled_monotonic)
+
+    def _init_derivatives(self, derivative_labels, derivative_wrt, derivative_weight, sampled_monotonic):
+        """the derivative options, checked on the host: ``_deriv_wrt`` (the variables of one ``SR_derivative_loss`` call),
+        ``derivative_labels`` (D, V) padded with a zero column per appended variable, ``derivative_weight`` (n labelled,) float64"""
+        self.derivative_labels, self.derivative_weight, self.sampled_monotonic = None, None, None
+        self._deriv_wrt, self._deriv_labelled, self._deriv_pending = [], 0, None
+        if derivative_labels is None and sampled_monotonic is None:
+            if derivative_wrt is not None:
+                raise ValueError("derivative_wrt needs derivative_labels")
+            return
+        num_inputs, D = self.datapoints.shape[1], self.datapoints.shape[0]
+        wrt = []
+        if derivative_labels is not None:
+            for name, on in (("linear_scaling", self.linear_scaling), ("multigene", self.multigene),
+                             ("loss, loss_param, sample_weights or validation_mask", self._own_loss),
+                             ("const_opt_steps > 0", self.const_opt_steps > 0), ("simplify_every > 0", self.simplify_every > 0)):
+                if on:
+                    raise ValueError(f"derivative_labels cannot be combined with {name}: that pass does not know the derivative columns")
+            self._one_label_column("derivative_labels", "works on one label column, (D, 1)")
+            if derivative_wrt is None:
+                if num_inputs > 8:
+                    raise ValueError(f"derivative_wrt=None asks for all {num_inputs} variables, but at most 8 are supported: name them")
+                wrt = list(range(num_inputs))
+            else:
+                wrt = [derivative_wrt] if isinstance(derivative_wrt, int) else [int(v) for v in derivative_wrt]
+            if not wrt or len(set(wrt)) != len(wrt) or not all(0 <= v < num_inputs for v in wrt):
+                raise ValueError(f"derivative_wrt should name distinct variables in 0 .. {num_inputs - 1}, but got {wrt}")
+            if not isinstance(derivative_labels, Tensor) or derivative_labels.shape != (D, len(wrt)) or not derivative_labels.dtype.is_floating_point:
+                raise ValueError(f"derivative_labels should be a ({D}, {len(wrt)}) floating-point tensor: one column per variable of "
+                                 f"derivative_wrt, but got {tuple(derivative_labels.shape) if isinstance(derivative_labels, Tensor) else derivative_labels!r}")
+            lam = torch.as_tensor(derivative_weight, dtype=torch.float64).reshape(-1)
+            if lam.numel() == 1:
+                lam = lam.expand(len(wrt)).clone()
+            if lam.shape != (len(wrt),) or not bool((torch.isfinite(lam) & (lam >= 0)).all()):
+                raise ValueError(f"derivative_weight should be a float or ({len(wrt)},) floats, finite and >= 0, but got {derivative_weight!r}")
+            self.derivative_weight = lam
+        elif derivative_wrt is not None:
+            raise ValueError("derivative_wrt needs derivative_labels")
+        self._deriv_labelled = len(wrt)
+        if sampled_monotonic is not None:
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with sampled_monotonic: that pass works on single-output trees")
+            self._one_label_column("sampled_monotonic")
+            variables, bounds, signs = parse_monotonic(sampled_monotonic, num_inputs)
+            self.sampled_monotonic = {v: s if s else b for v, b, s in zip(variables, bounds, signs)}
+            wrt = wrt + [v for v in variables if v not in wrt]
+            self._constrained = True
+        if len(wrt) > 8:
+            raise ValueError(f"derivative_wrt and sampled_monotonic name {len(wrt)} variables together, but at most 8 are supported")
+        self._deriv_wrt = wrt
+        if derivative_labels is not None:
+            dl = derivative_labels.detach().to(self.datapoints.device).to(torch.float32)
+            pad = dl.new_zeros((D, len(wrt) - self._deriv_labelled))
+            self.derivative_labels = torch.cat([dl, pad], dim=1).contiguous()
+
+    def derivative_loss(self, forest: Forest):
+        """``(loss (pop, 1 + V), violations (pop, V))``: ``Forest.SR_derivative_loss`` on this problem's data, derivative labels and
+        ``sampled_monotonic`` bounds, over the variables ``derivative_wrt`` followed by those only ``sampled_monotonic`` names (their
+        label is 0).  The raw columns: no weight, no mask"""
+        if not self._deriv_wrt:
+            raise ValueError("this problem has neither derivative_labels nor sampled_monotonic")
+        return forest.SR_derivative_loss(self.datapoints, self.labels, self.derivative_labels, self._deriv_wrt, self.sampled_monotonic)
+
     def _one_label_column(self, feature: str, claim: str = "works on single-output problems only"):
         if self.labels.dim() != 2 or self.labels.shape[1] != 1:
             raise ValueError(f"{feature} {claim}, but the labels have shape {tuple(self.labels.shape)}")
@@ -316,6 +395,12 @@ class SymbolicRegression(BaseProblem):
             box = self.safe_mask(forest) if self.monotonic is None else self.monotone_mask(forest)   # (the latter holds the former)
             box = box.to(fitness.device)
             mask = box if mask is None else mask & box
+        if self.sampled_monotonic is not None:   # (the pass the fitness came from, when derivative_labels is on: one launch for both)
+            cols = [self._deriv_wrt.index(v) for v in self.sampled_monotonic]
+            pending, self._deriv_pending = self._deriv_pending, None   # what _loss has just computed for this very forest
+            viol = pending[1] if pending is not None and pending[0] is forest else self.derivative_loss(forest)[1]
+            obeys = (viol[:, cols] == 0).all(1).to(fitness.device)
+            mask = obeys if mask is None else mask & obeys
         counted = []   # (violations, penalty) of the passes that count violations
         if self.input_units is not None:
             counted.append((self.dimensions(forest)[2], self.dimension_penalty))
@@ -546,6 +631,13 @@ class SymbolicRegression(BaseProblem):
         """``(loss, on_device)``: the positive loss of every tree under this problem's model, and whether a HIP pass over a device
         forest computed it (``scores`` then finishes it in one launch)"""
         on_device = self.execute_mode != "torch" and forest.batch_node_value.is_cuda
+        if self.derivative_labels is not None:
+            if not use_MSE:
+                raise ValueError("derivative_labels minimises squared errors: use_MSE must be True")
+            cols, viol = self.derivative_loss(forest)
+            self._deriv_pending = (forest, viol) if self.sampled_monotonic is not None else None   # (_masked takes it: one pass for both)
+            lam = self.derivative_weight.to(cols.device).to(cols.dtype)
+            return cols[:, 0] + (cols[:, 1:1 + self._deriv_labelled] * lam[None, :]).sum(1), on_device
         if self._scaling_own:
             self._check_scaling(use_MSE)
             return self.scaled_fitness(forest)[0], on_device

@@ -20,6 +20,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     multi-gene            SR_gene_fitness, SR_gene_moments, gene_predict: a tree's outputs as features of a least-squares model
     intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
+    input gradients       SR_input_gradients, SR_derivative_loss: d tree / d x on the data rows; the derivative loss and violations
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
     genetic operators     mutate, crossover
@@ -47,6 +48,7 @@ _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") 
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
+XGRAD_MAX_VARS = 8  # variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
 LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
@@ -731,6 +733,65 @@ class Forest:
         for k, (dmin, dmax) in enumerate(want):
             ok = ok & ((dfl[k, :, 0] & 3) == 0) & (dlo[k, :, 0] >= dmin) & (dhi[k, :, 0] <= dmax)
         return ok
+
+    # ---- input gradients on the data ----------------------------------------------------------------
+    def _xgrad_wrt(self, what: str, wrt, extra=()):
+        """the requested variables of the input-gradient ops as a host list: ``_wrt``'s checks, then the variables of ``extra`` that
+        ``wrt`` lacks appended, distinct, at most ``XGRAD_MAX_VARS``"""
+        self._single_output(what, ValueError)
+        if wrt is None and self.input_len > XGRAD_MAX_VARS:
+            raise ValueError(f"{what}: wrt=None asks for all {self.input_len} variables, but one call takes at most {XGRAD_MAX_VARS}: "
+                             "name the variables in wrt")
+        idx = self._wrt(wrt)
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"{what}: wrt names a variable twice: {idx}")
+        if extra:
+            idx = idx + [v for v in self._wrt(list(extra)) if v not in idx]
+        if len(idx) > XGRAD_MAX_VARS:
+            raise ValueError(f"{what}: {len(idx)} variables are requested, but one call takes at most {XGRAD_MAX_VARS}")
+        return idx
+
+    def SR_input_gradients(self, inputs: Tensor, wrt=None):
+        """``(pred, grad)``: ``pred`` (pop, D) the prediction of every tree on every row of ``inputs`` (D, input_len), ``grad`` (pop, D, V)
+        its partial derivative in variable ``wrt[k]`` at that row -- reverse-mode differentiation on the value tape (csrc/sr_xgrad.hip,
+        one HIP pass), by the rules of the constant gradient.  ``grad`` is a permuted view of the kernel's (V, pop, D) array.  A
+        variable the tree does not hold has exactly 0; a malformed tree NaN everywhere.  A derivative may be NaN where the prediction
+        is finite (``0 * NaN`` under a branch that was not taken).  ``wrt``: an int or a list of distinct variables, at most
+        ``XGRAD_MAX_VARS`` = 8; None means every variable and needs ``input_len <= 8`` (``ValueError`` otherwise, as for an index out
+        of range, a repeated index or a multi-output forest)."""
+        idx = self._xgrad_wrt("SR_input_gradients", wrt)
+        inputs = check_tensor(inputs, self.batch_node_value.device)
+        assert inputs.dim() == 2 and inputs.shape[1] == self.input_len, (
+            f"inputs shape[1] should be {self.input_len}, but got {tuple(inputs.shape)}")
+        pred, dpred = torch.ops.evogp_hip.tree_SR_input_gradient(*self._tensors(), inputs.contiguous().to(torch.float32), idx)
+        return pred, dpred.permute(1, 2, 0)
+
+    def SR_derivative_loss(self, inputs: Tensor, labels: Tensor, dlabels: Optional[Tensor] = None, wrt=None, bounds=None):
+        """``(loss, violations)`` without a (pop, D) array (csrc/sr_xgrad.hip, one HIP pass, no host synchronisation): ``loss`` (pop, 1 + V)
+        float32 -- column 0 the mean squared error of the prediction against ``labels`` (D, 1), column 1 + k the mean squared error of
+        d tree / d x_wrt[k] against ``dlabels[:, k]`` (``dlabels`` (D, V); None: zeros, the column is then the mean squared sensitivity
+        to the variable); ``violations`` (pop, V) int32 -- the rows on which that derivative is outside its range in ``bounds`` =
+        ``{variable: +1 | -1 | (dmin, dmax)}`` (``parse_monotonic``) or is NaN; a variable without a bound counts its NaN rows only.
+        Variables of ``bounds`` that ``wrt`` lacks are appended to it; the columns follow that order (``dlabels`` then needs a column
+        for each).  A column is NaN when a row term is not finite; a malformed tree has NaN columns and ``D`` violations.  Sums are
+        float64 in a fixed order: bit-identical from run to run.  ``ValueError`` as for ``SR_input_gradients``."""
+        variables, ranges, _ = parse_monotonic(bounds or {})
+        idx = self._xgrad_wrt("SR_derivative_loss", wrt, variables)
+        inputs, labels = self._sr_data(inputs, labels)
+        dev, V = self.batch_node_value.device, len(idx)
+        if dlabels is not None:
+            dlabels = check_tensor(dlabels, dev)
+            if dlabels.shape != (inputs.shape[0], V):
+                raise ValueError(f"dlabels should have shape ({inputs.shape[0]}, {V}): one column per requested variable {idx}, "
+                                 f"but got {tuple(dlabels.shape)}")
+            dlabels = dlabels.contiguous().to(torch.float32)
+        dmin = dmax = None
+        if variables:
+            lo, hi = [float("-inf")] * V, [float("inf")] * V
+            for v, (a, b) in zip(variables, ranges):
+                lo[idx.index(v)], hi[idx.index(v)] = a, b
+            dmin, dmax = torch.tensor(lo, dtype=torch.float32).to(dev), torch.tensor(hi, dtype=torch.float32).to(dev)
+        return torch.ops.evogp_hip.tree_SR_derivative_loss(*self._tensors(), inputs, labels, dlabels, idx, dmin, dmax)
 
     # ---- dimensional analysis --------------------------------------------------------------------
     def SR_dimensions(self, input_units, label_units=None):

@@ -781,6 +781,45 @@ int evogp_hip_sr_weighted_scaling(unsigned pop_size, unsigned data_points, unsig
                                   const float *labels, const float *weights /* nullable */, unsigned n_weights, float *loss /* [pop][K] */,
                                   float *coef /* [pop][2]: intercept, slope */, evogp_stream_t stream);
 
+/* Input gradients of single-output trees on the rows of the dataset, and the derivative loss computed from them (no counterpart in the
+ * reference; csrc/sr_xgrad.hip).  p_d is the float32 prediction of the tape's forward walk on row d (the walk of
+ * evogp_hip_sr_gradient), g_{k,d} = d tree / d x_{wrt[k]} at X[d]: the reverse walk of evogp_hip_sr_gradient seeded with 1.0f at the root,
+ * adjoints in float32 by the same rules (DESIGN.md "Constant gradients"; an IF gives 0 to its condition, its adjoint to the branch it
+ * took and 0 to the other).  g_{k,d} is the float32 sum, starting from +0.0f, of the adjoints of the VAR nodes that hold variable wrt[k],
+ * in prefix order: +0.0f exactly for a variable the tree does not hold, 1.0f for a root that is that variable.
+ * NaN: the rules are the constant gradient's and are not repaired.  0 * NaN is NaN, so a NaN or infinite value in a branch that was NOT
+ * taken (IF, max, min) can make a derivative NaN on a row whose prediction is finite.
+ *   evogp_hip_sr_input_gradient   pred f32[pop][D] = p_d, dpred f32[n_wrt][pop][D] = g_{k,d}.  A malformed tree (the rule of
+ *                                 evogp_hip_sr_gradient) has NaN in every word of its rows of both.
+ *   evogp_hip_sr_derivative_loss  writes no (pop, D) array.  loss f32[pop][1 + n_wrt], violations i32[pop][n_wrt]:
+ *       loss[t][0]     = (float)( sum_d ((double)p_d - (double)labels[d])^2 / D ): equal bit for bit to the loss of
+ *                        evogp_hip_sr_weighted_gradient with weights == NULL and EVOGP_LOSS_MSE (same plan, same walk, same order);
+ *       loss[t][1 + k] = (float)( sum_d ((double)g_{k,d} - (double)dlabels[d][k])^2 / D ); dlabels f32[D][n_wrt], or NULL: every label
+ *                        is 0 and the column is the mean squared sensitivity of the tree to the variable;
+ *       a column is NaN exactly when one of its row terms is not finite (sqrt(x0) at x0 == 0: column 0 finite, the x0 column NaN);
+ *       violations[t][k] = the number of rows with !(dmin[k] <= g_{k,d} && g_{k,d} <= dmax[k]); a NaN derivative counts.  dmin / dmax:
+ *                        f32[n_wrt] on the device, or NULL: -inf / +inf, and then only NaN counts;
+ *       a malformed tree has NaN in every column and violations = D.
+ *     Sums are float64 per lane over the wave's row tiles in ascending order, the 64 lanes by the fixed butterfly, the waves in wave
+ *     order; violations are counted per tile by ballot and added as integers in the same order.
+ * wrt: int32[n_wrt] ON THE HOST, read before the call returns (unlike evogp_hip_tree_derivative_intervals, whose wrt lives on the device
+ * and is the caller's to check: here the entries are checked before any launch and nothing synchronises with the host); 1 <= n_wrt <=
+ * EVOGP_XGRAD_MAX_VARS, entries distinct and in [0, var_len).
+ * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, var_len >= 2^28, n_wrt outside 1 .. 8, an entry of wrt out of range or
+ * repeated.  Then a NULL pointer other than dlabels, dmin, dmax: EVOGP_E_NULLPTR; then out_len != 1: EVOGP_E_UNSUPPORTED.
+ * One launch each, no float atomics: bit-identical from run to run.  Rows of more than 64 nodes use the per-stream tape buffer of
+ * evogp_hip_sr_gradient, under the same rules.  Any data_points and var_len; the outputs must not alias the inputs or one another. */
+#define EVOGP_XGRAD_MAX_VARS 8
+int evogp_hip_sr_input_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                const float *value, const int16_t *type, const int16_t *size, const float *variables, unsigned n_wrt,
+                                const int *wrt /* host */, float *pred /* [pop][D] */, float *dpred /* [n_wrt][pop][D] */,
+                                evogp_stream_t stream);
+int evogp_hip_sr_derivative_loss(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                 const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                 const float *labels, const float *dlabels /* nullable */, unsigned n_wrt, const int *wrt /* host */,
+                                 const float *dmin /* nullable */, const float *dmax /* nullable */, float *loss /* [pop][1 + n_wrt] */,
+                                 int *violations /* [pop][n_wrt] */, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -863,7 +902,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
