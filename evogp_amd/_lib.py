@@ -101,6 +101,7 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_tc_batches": [_i, _i],
     "evogp_hip_debug_tc_table": [_i],
     "evogp_hip_debug_tc_dense": [_i],
+    "evogp_hip_debug_tc_dense_fallbacks": [],
     "evogp_hip_debug_tc_table_entry": [_i, _i, C.POINTER(C.c_uint)],
     "evogp_hip_debug_profile": [_i],
     "evogp_hip_debug_profile_read": [C.POINTER(C.c_float), C.POINTER(C.c_int)],

@@ -75,8 +75,14 @@ int evogp_hip_debug_tc_table(int mode);
 /* Whether a launch of the packed arithmetic line with its word table gives a lane to every function node only (tc_compile_dense_kernel:
  * leaves are read from the row by their parent's lane) or to every node (tc_compile_packed_kernel): 1 = function
  * nodes; 0 = every node; -1 = back to the default / the environment (EVOGP_TC_DENSE = 0 or 1 before the first call; unset: 1).  The program
- * words, the fitness words and the marks do not depend on the choice (tests/test_gpu_tc_dense.py compares them bit for bit). */
+ * words, the fitness words and the marks do not depend on the choice (tests/test_gpu_tc_dense.py compares them bit for bit).
+ * tc_compile_dense_kernel loads the rows of `type` and `size` eight bytes per lane; a launch whose rows do not start on 8 bytes (gp_len not a
+ * multiple of 4, or a `type` / `size` pointer not aligned to 8 bytes) is tc_compile_packed_kernel's whatever the switch says.
+ * _fallbacks: the number of batches of the most recent program-compiler launch that tc_compile_dense_kernel handed to the packed passes
+ * (a row it does not take: DESIGN.md section 3.1), or -1 when that launch was not tc_compile_dense_kernel's -- the switch, the alignment,
+ * another line of the compiler, a call without a scratch block (waits for the device). */
 int evogp_hip_debug_tc_dense(int mode);
+int evogp_hip_debug_tc_dense_fallbacks(void);
 /* Entry `code` (0 .. 127) of the word table, of its half for launches without (recip = 0) or with (1) reciprocal columns, as the engine was
  * built with it: entry[0] = the four handler ids, entry[1] = the other fields (host memory; tests/test_tc_word_table.py holds the table
  * to a Python restatement of the selects). */
