@@ -79,6 +79,137 @@ class DefaultMutation(BaseMutation):
         return forest
 
 
+# ---- semantic backpropagation (no counterpart in the reference) --------------------------------------------------------------------
+def _leaf_rows(values: torch.Tensor, ntype: int, max_tree_len: int):
+    """one-node trees holding ``values`` (n,) as (value, type, size) rows of ``max_tree_len`` words"""
+    n = values.shape[0]
+    value = torch.zeros((n, max_tree_len), dtype=torch.float32, device=values.device)
+    node_type = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
+    size = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
+    value[:, 0], node_type[:, 0], size[:, 0] = values.to(torch.float32), ntype, 1
+    return value, node_type, size
+
+
+class SemanticBackpropMutation(BaseMutation):
+    """The Random Desired Operator of Pawlak, Wieloch & Krawiec (IEEE TEVC 2015): a mutating tree is inverted from its root down to a
+    random node on the rows of the dataset (``Forest.SR_backprop_match``, csrc/sr_backprop.hip), which gives the values
+    the subtree at that node would have to return for the tree to hit the labels, and the subtree is replaced by the member of a LIBRARY
+    of small trees whose values on the rows are nearest to them -- or, with ``allow_constant``, by the constant that is nearer still.
+    The first variation operator here that looks at ``datapoints`` and ``labels``.
+
+    ``library``: a single-output Forest (at most 1024 trees).  Without one it is built from ``descriptor``: the one-node tree of every
+    variable and ``library_size`` random trees, reduced to one member per semantics (``semantic_unique(datapoints, keep="smallest")``)
+    and truncated to 1024; its semantics are computed once.  ``update_library(forest)`` replaces it by the semantically distinct members
+    of a forest, e.g. of the population.  A library narrower than the forest is padded to the forest's ``max_tree_len``; a wider one
+    is a ``ValueError`` at the call.
+
+    The mutating trees and their positions are drawn as ``DefaultMutation`` draws them.  A mutating tree without a match (``best ==
+    -1``: a function on the path has no inverse, no row is REQUIRED, or no library member is finite there) goes to ``fallback`` -- any
+    ``BaseMutation``; it is applied to the mutating trees with its ``mutation_rate`` raised to 1 for the call and its result is kept
+    for the trees without a match -- or stays as it is.  Host synchronisations: one (the number of mutating trees) against
+    ``DefaultMutation``'s three; a fallback adds its own."""
+
+    takes_skip_rows = True
+
+    def __init__(self, mutation_rate: float, datapoints: torch.Tensor, labels: torch.Tensor, library: Optional[Forest] = None,
+                 descriptor: Optional[GenerateDescriptor] = None, library_size: int = 256, allow_constant: bool = True,
+                 fallback: Optional[BaseMutation] = None):
+        if datapoints.dim() != 2 or labels.shape[0] != datapoints.shape[0] or labels.numel() != datapoints.shape[0]:
+            raise ValueError(f"datapoints should be (D, input_len) and labels (D,) or (D, 1), but got {tuple(datapoints.shape)} and {tuple(labels.shape)}")
+        if fallback is not None and not isinstance(fallback, BaseMutation):
+            raise ValueError(f"fallback should be a BaseMutation, but got {type(fallback).__name__}")
+        self.mutation_rate = mutation_rate
+        self.datapoints = datapoints.contiguous().to(torch.float32)
+        self.labels = labels.reshape(-1, 1).contiguous().to(torch.float32)
+        self.allow_constant = bool(allow_constant)
+        self.fallback = fallback
+        if library is None:
+            if descriptor is None:
+                raise ValueError("SemanticBackpropMutation needs a library or a descriptor to build one from")
+            if descriptor.output_len != 1 or descriptor.input_len != datapoints.shape[1]:
+                raise ValueError(f"the descriptor should generate single-output trees of {datapoints.shape[1]} inputs, but has "
+                                 f"{descriptor.input_len} inputs and {descriptor.output_len} outputs")
+            if not isinstance(library_size, int) or library_size < 0:
+                raise ValueError(f"library_size should be a non-negative integer, but got {library_size!r}")
+            dev = self.datapoints.device
+            variables = Forest(descriptor.input_len, 1, *_leaf_rows(torch.arange(descriptor.input_len, device=dev), NType.VAR, descriptor.max_tree_len),
+                               func_mask=descriptor.func_mask)
+            library = variables + Forest.random_generate(library_size, descriptor) if library_size else variables
+        self.update_library(library)
+
+    def update_library(self, forest: Forest) -> None:
+        """the library becomes the semantically distinct members of ``forest`` on the datapoints (the smallest tree of every class, in
+        index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation."""
+        from ..tree.forest import BACKPROP_MAX_LIBRARY
+
+        if not isinstance(forest, Forest) or forest.output_len != 1 or forest.input_len != self.datapoints.shape[1]:
+            raise ValueError(f"the library should be a single-output Forest of {self.datapoints.shape[1]} inputs")
+        unique, _, _ = forest.semantic_unique(self.datapoints, keep="smallest")
+        self.library = unique[:BACKPROP_MAX_LIBRARY] if unique.pop_size > BACKPROP_MAX_LIBRARY else unique
+        self.semantics = self.library.batch_forward(self.datapoints)[:, :, 0].contiguous()
+        self._padded = {}
+
+    def _library_rows(self, max_tree_len: int):
+        """the library's three tensors at the forest's row width"""
+        lib = self.library
+        if lib.max_tree_len == max_tree_len:
+            return lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size
+        if lib.max_tree_len > max_tree_len:
+            raise ValueError(f"the library's max_tree_len {lib.max_tree_len} exceeds the forest's {max_tree_len}")
+        if max_tree_len not in self._padded:
+            pad = (0, max_tree_len - lib.max_tree_len)
+            self._padded[max_tree_len] = tuple(torch.nn.functional.pad(a, pad) for a in (lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size))
+        return self._padded[max_tree_len]
+
+    def __call__(self, forest: Forest, skip_rows: int = 0) -> Forest:
+        dev = forest.batch_node_value.device
+        mask = _keep_rows(torch.rand(forest.pop_size, device=dev) < self.mutation_rate, skip_rows)
+        rows = torch.nonzero(mask).squeeze(1)   # (the one synchronisation)
+        n_mut = int(rows.shape[0])
+        if n_mut == 0:
+            return forest
+        raw = torch.randint(0, MAX_STACK, (n_mut,), dtype=torch.int32, device=dev)
+        return self.apply(forest, rows, (raw % forest.batch_subtree_size[rows, 0]).to(torch.int32))
+
+    def apply(self, forest: Forest, rows: torch.Tensor, positions: torch.Tensor) -> Forest:
+        """the operator on the trees ``rows`` (int64 indices) at the nodes ``positions`` (one per row of ``rows``): match, donors,
+        splice; writes the rows of ``forest`` and returns it.  No host synchronisation."""
+        if forest.output_len != 1 or forest.input_len != self.library.input_len:
+            raise ValueError(f"SemanticBackpropMutation: the forest should have {self.library.input_len} inputs and one output, but has "
+                             f"{forest.input_len} and {forest.output_len}")
+        lib_value, lib_type, lib_size = self._library_rows(forest.max_tree_len)
+        chosen = forest[rows]
+        positions = positions.to(torch.int32)
+        best, dist, const, const_dist, _, _ = chosen.SR_backprop_match(self.datapoints, self.labels, positions, self.semantics)
+        found = best >= 0
+        member = best.clamp(min=0).to(torch.int64)
+        value, node_type, size = lib_value[member], lib_type[member], lib_size[member]
+        if self.allow_constant:
+            nearer = found & (const_dist < dist.gather(1, member[:, None]).squeeze(1))
+            cv, ct, cs = _leaf_rows(const, NType.CONST, forest.max_tree_len)
+            value, node_type, size = (torch.where(nearer[:, None], c, a) for c, a in ((cv, value), (ct, node_type), (cs, size)))
+        donors = Forest(forest.input_len, 1, value, node_type, size, func_mask=self.library.func_mask)
+        new = chosen.mutate(torch.where(found, positions, torch.full_like(positions, -1)), donors)   # (position -1: the row is copied)
+        if self.fallback is not None:
+            other = self._fall_back(chosen)
+            new = Forest(forest.input_len, 1, *(torch.where(found[:, None], a, b) for a, b in zip(new._tensors(), other._tensors())),
+                         func_mask=Forest.join_masks(new.func_mask, other.func_mask))
+        forest[rows] = new
+        return forest
+
+    def _fall_back(self, chosen: Forest) -> Forest:
+        """``fallback`` on every mutating tree: its rate is 1 for the call"""
+        op = self.fallback
+        rate = getattr(op, "mutation_rate", None)
+        try:
+            if rate is not None:
+                op.mutation_rate = 1.0
+            return op(Forest(chosen.input_len, chosen.output_len, *(a.clone() for a in chosen._tensors()), func_mask=chosen.func_mask))
+        finally:
+            if rate is not None:
+                op.mutation_rate = rate
+
+
 # ---- structural and point mutations (SURVEY.md §8f N3) -----------------------------------------------------------
 # The reference builds these from boolean-mask gathers, a per-row "vmap_subtree" gather program and tree_mutate
 # (mutation/mutation_utils.py:6-48, hoist.py:43-75, insert.py:45-85, delete.py:44-105, single_point.py:43-126,

@@ -705,6 +705,65 @@ std::tuple<Tensor, Tensor> tree_SR_derivative_loss(const Tensor &value, const Te
     return {loss, viol};
 }
 
+// the prologue of the two semantic-backpropagation ops: the forest, X (D, var_len), y (D,) or (D, 1), pos (pop,) int32
+struct BackpropCall {
+    Forest f;
+    int64_t D, var_len;
+};
+
+BackpropCall check_backprop(const char *op, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                            const Tensor &labels, const Tensor &pos) {
+    BackpropCall c{Forest::infer(value, type, size), 0, 0};
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, "too many data points: ", variables.size(0));
+    c.D = variables.size(0), c.var_len = variables.size(1);
+    check_tensor(variables, {c.D, c.var_len}, "variables", c.f.dev, at::kFloat);
+    if (labels.dim() == 2) check_tensor(labels, {c.D, 1}, "labels", c.f.dev, at::kFloat);   // (D,) or (D, 1)
+    else check_tensor(labels, {c.D}, "labels", c.f.dev, at::kFloat);
+    check_tensor(pos, {c.f.pop}, "pos", c.f.dev, at::kInt);
+    return c;
+}
+
+// (desired float32 (pop, D), state uint8 (pop, D), status int32 (pop,)): the value the subtree at node pos[t] must return on every row for
+// the tree to hit the label (evogp_hip_sr_desired)
+std::tuple<Tensor, Tensor, Tensor> tree_SR_desired(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
+                                                   const Tensor &labels, const Tensor &pos) {
+    const BackpropCall c = check_backprop("tree_SR_desired", value, type, size, variables, labels, pos);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor desired = empty({c.f.pop, c.D}, at::kFloat, c.f.dev), state = empty({c.f.pop, c.D}, at::kByte, c.f.dev);
+    Tensor status = empty({c.f.pop}, at::kInt, c.f.dev);
+    check_rc(evogp_hip_sr_desired((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type, c.f.size,
+                                  variables.data_ptr<float>(), labels.data_ptr<float>(), pos.data_ptr<int>(), desired.data_ptr<float>(),
+                                  state.data_ptr<uint8_t>(), status.data_ptr<int>(), current_stream(c.f.dev)),
+             "tree_SR_desired");
+    return {desired, state, status};
+}
+
+// (best int32 (pop,), dist float64 (pop, K), const float32 (pop,), const_dist float64 (pop,), counts int32 (pop, 3), status int32 (pop,)): the
+// desired values of tree_SR_desired matched against the library semantics lib (K, D) without a (pop, D) array (evogp_hip_sr_backprop_match).
+// The kernel reads the library transposed: the (D, K) copy is made here, once per call
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_SR_backprop_match(const Tensor &value, const Tensor &type, const Tensor &size,
+                                                                                const Tensor &variables, const Tensor &labels, const Tensor &pos,
+                                                                                const Tensor &lib) {
+    const BackpropCall c = check_backprop("tree_SR_backprop_match", value, type, size, variables, labels, pos);
+    TORCH_CHECK(lib.dim() == 2 && lib.size(0) >= 1 && lib.size(0) <= EVOGP_BACKPROP_MAX_LIB,
+                "tree_SR_backprop_match: lib must be a (K, data_points) tensor with K in [1, ", EVOGP_BACKPROP_MAX_LIB, "], but got shape ", lib.sizes());
+    const int64_t K = lib.size(0);
+    check_tensor(lib, {K, c.D}, "lib", c.f.dev, at::kFloat);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor lib_t = lib.t().contiguous();
+    Tensor best = empty({c.f.pop}, at::kInt, c.f.dev), dist = empty({c.f.pop, K}, at::kDouble, c.f.dev);
+    Tensor cnst = empty({c.f.pop}, at::kFloat, c.f.dev), const_dist = empty({c.f.pop}, at::kDouble, c.f.dev);
+    Tensor counts = empty({c.f.pop, 3}, at::kInt, c.f.dev), status = empty({c.f.pop}, at::kInt, c.f.dev);
+    check_rc(evogp_hip_sr_backprop_match((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type,
+                                         c.f.size, variables.data_ptr<float>(), labels.data_ptr<float>(), pos.data_ptr<int>(), (unsigned)K,
+                                         lib_t.data_ptr<float>(), dist.data_ptr<double>(), best.data_ptr<int>(), cnst.data_ptr<float>(),
+                                         const_dist.data_ptr<double>(), counts.data_ptr<int>(), status.data_ptr<int>(), current_stream(c.f.dev)),
+             "tree_SR_backprop_match");
+    return {best, dist, cnst, const_dist, counts, status};
+}
+
 // (units int32 (pop, gp_len, n_dims), flags uint8 (pop, gp_len), violations int32 (pop,)): the unit of every subtree, the variables carrying
 // var_units (var_len, n_dims) and, with check_root, the root held to label_units (n_dims,) (evogp_hip_tree_dimensions)
 std::tuple<Tensor, Tensor, Tensor> tree_dimensions(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &var_units,
@@ -1286,6 +1345,9 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_SR_input_gradient(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, int[] wrt) -> (Tensor pred, Tensor dpred)");
     m.def("tree_SR_derivative_loss(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor? dlabels, int[] wrt,"
           " Tensor? dmin, Tensor? dmax) -> (Tensor loss, Tensor violations)");
+    m.def("tree_SR_desired(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor pos) -> (Tensor desired, Tensor state, Tensor status)");
+    m.def("tree_SR_backprop_match(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor pos, Tensor lib)"
+          " -> (Tensor best, Tensor dist, Tensor const, Tensor const_dist, Tensor counts, Tensor status)");
     m.def("tree_dimensions(Tensor value, Tensor node_type, Tensor subtree_size, Tensor var_units, Tensor label_units, bool check_root) -> (Tensor units, Tensor flags, Tensor violations)");
     m.def("tree_structure(Tensor value, Tensor node_type, Tensor subtree_size, Tensor cost, Tensor operand_limit, Tensor rule_outer, Tensor rule_inner, Tensor rule_limit, int max_depth, int max_complexity)"
           " -> (Tensor complexity, Tensor height, Tensor depth, Tensor nest, Tensor flags, Tensor violations)");
@@ -1338,6 +1400,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_derivative_intervals", &tree_derivative_intervals);
     m.impl("tree_SR_input_gradient", &tree_SR_input_gradient);
     m.impl("tree_SR_derivative_loss", &tree_SR_derivative_loss);
+    m.impl("tree_SR_desired", &tree_SR_desired);
+    m.impl("tree_SR_backprop_match", &tree_SR_backprop_match);
     m.impl("tree_dimensions", &tree_dimensions);
     m.impl("tree_structure", &tree_structure);
 }

@@ -21,6 +21,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     intervals             SR_intervals, safe_mask: bounds of every subtree over a box of inputs; the trees finite on all of it
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
     input gradients       SR_input_gradients, SR_derivative_loss: d tree / d x on the data rows; the derivative loss and violations
+    backpropagation       SR_desired_semantics, SR_backprop_match: the values a subtree would have to return; the nearest library member
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
     genetic operators     mutate, crossover
@@ -48,7 +49,8 @@ _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") 
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
-XGRAD_MAX_VARS = 8  # variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
+BACKPROP_MAX_LIBRARY = 1024  # library members per SR_backprop_match call (include/evogp_hip.h EVOGP_BACKPROP_MAX_LIB)
+XGRAD_MAX_VARS = 8  #variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
 LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
@@ -792,6 +794,52 @@ class Forest:
                 lo[idx.index(v)], hi[idx.index(v)] = a, b
             dmin, dmax = torch.tensor(lo, dtype=torch.float32).to(dev), torch.tensor(hi, dtype=torch.float32).to(dev)
         return torch.ops.evogp_hip.tree_SR_derivative_loss(*self._tensors(), inputs, labels, dlabels, idx, dmin, dmax)
+
+    # ---- semantic backpropagation --------------------------------------------------------------------
+    def _backprop_args(self, what: str, inputs: Tensor, labels: Tensor, positions: Tensor):
+        """the dataset and the positions as the two ops take them; ``ValueError`` for a multi-output forest or positions of another
+        shape or a non-integer dtype (their RANGE is the kernel's to report: status 2, no host synchronisation)"""
+        self._single_output(what, ValueError)
+        inputs, labels = self._sr_data(inputs, labels)
+        positions = check_tensor(positions, self.batch_node_value.device)
+        if tuple(positions.shape) != (self.pop_size,):
+            raise ValueError(f"{what}: positions should have shape ({self.pop_size},), but got {tuple(positions.shape)}")
+        if positions.dtype.is_floating_point or positions.dtype == torch.bool:
+            raise ValueError(f"{what}: positions should be integers, but got {positions.dtype}")
+        return inputs, labels, positions.contiguous().to(torch.int32)
+
+    def SR_desired_semantics(self, inputs: Tensor, labels: Tensor, positions: Tensor):
+        """``(desired, state, status)``: semantic backpropagation (Pawlak, Wieloch & Krawiec 2015; csrc/sr_backprop.hip, one HIP pass, no
+        host synchronisation).  ``desired`` (pop, D) float32 is the value the subtree at node ``positions[t]`` of tree t would have to
+        return on row d for the whole tree to return ``labels[d]``: the tree inverted from its root down to that node, one float32
+        operation per function on the way (DESIGN.md 3.24 has the table).  ``state`` (pop, D) uint8: 0 REQUIRED (``desired`` holds the
+        value), 1 FREE (any value reproduces the label: ``0 * x``, the branch an IF does not take), 2 IMPOSSIBLE (no value does);
+        ``desired`` is NaN where the state is not 0.  ``status`` (pop,) int32: 0 ok, 1 malformed row, 2 position outside the tree, 3
+        BLOCKED (a function on the path has no inverse here: sin, pow, a comparison, a loose variant, an IF's condition); with a status
+        other than 0 every row is IMPOSSIBLE.  ``ValueError`` for a multi-output forest or ``positions`` that is not (pop,) integers."""
+        inputs, labels, positions = self._backprop_args("SR_desired_semantics", inputs, labels, positions)
+        return torch.ops.evogp_hip.tree_SR_desired(*self._tensors(), inputs, labels, positions)
+
+    def SR_backprop_match(self, inputs: Tensor, labels: Tensor, positions: Tensor, library):
+        """``(best, dist, const, const_dist, counts, status)``: the desired values of ``SR_desired_semantics`` matched against a library
+        of subtrees in the same HIP pass, without a (pop, D) array and without a host synchronisation.  ``library``: a (K, D) float32
+        tensor of semantics, or a single-output Forest of K trees whose semantics are ``library.batch_forward(inputs)``; 1 <= K <=
+        ``BACKPROP_MAX_LIBRARY`` = 1024.  ``dist`` (pop, K) float64: the squared distance of member k to the desired values over the
+        REQUIRED rows (+inf where the member is not finite on one of them); ``best`` (pop,) int32 the nearest member, the smallest
+        index on ties, -1 when ``status`` is not 0, no row is REQUIRED or no member is finite; ``const`` (pop,) float32 and
+        ``const_dist`` (pop,) float64 the best constant (the mean of the desired values) and its distance; ``counts`` (pop, 3) int32
+        the REQUIRED, FREE and IMPOSSIBLE rows.  ``ValueError`` as for ``SR_desired_semantics``, and for a library of another shape."""
+        inputs, labels, positions = self._backprop_args("SR_backprop_match", inputs, labels, positions)
+        if isinstance(library, Forest):
+            if library.input_len != self.input_len or library.output_len != 1:
+                raise ValueError(f"SR_backprop_match: the library forest should have {self.input_len} inputs and one output, but has "
+                                 f"{library.input_len} and {library.output_len}")
+            library = library.batch_forward(inputs)[:, :, 0]
+        library = check_tensor(library, self.batch_node_value.device)
+        if library.dim() != 2 or library.shape[1] != inputs.shape[0] or not 1 <= library.shape[0] <= BACKPROP_MAX_LIBRARY:
+            raise ValueError(f"SR_backprop_match: library should have shape (K, {inputs.shape[0]}) with 1 <= K <= {BACKPROP_MAX_LIBRARY}, "
+                             f"but got {tuple(library.shape)}")
+        return torch.ops.evogp_hip.tree_SR_backprop_match(*self._tensors(), inputs, labels, positions, library.contiguous().to(torch.float32))
 
     # ---- dimensional analysis --------------------------------------------------------------------
     def SR_dimensions(self, input_units, label_units=None):

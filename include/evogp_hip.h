@@ -820,6 +820,41 @@ int evogp_hip_sr_derivative_loss(unsigned pop_size, unsigned data_points, unsign
                                  const float *dmin /* nullable */, const float *dmax /* nullable */, float *loss /* [pop][1 + n_wrt] */,
                                  int *violations /* [pop][n_wrt] */, evogp_stream_t stream);
 
+/* Semantic backpropagation over single-output trees on the rows of the dataset (Pawlak, Wieloch & Krawiec 2015; no counterpart in the
+ * reference; csrc/sr_backprop.hip, DESIGN.md section 3.24, which holds the rule table; tests/backprop_ref.py restates it).  pos i32[pop]
+ * names one node per tree.  The tree is inverted from the root down to that node: per row d a target t and a state, (labels[d], REQUIRED)
+ * at the root, one float32 operation per function node on the path, the other operands' values taken from the tape of the forward walk
+ * of evogp_hip_sr_gradient.  States: 0 REQUIRED (the subtree must return t), 1 FREE (any value reproduces the label), 2 IMPOSSIBLE (none
+ * does); FREE and IMPOSSIBLE are absorbing.  status i32[pop]: 0 ok; 1 the row is malformed (the rule of evogp_hip_sr_gradient); 2 pos is
+ * outside [0, length); 3 BLOCKED: a function on the path has no rule (the loose variants, pow, the comparisons, the trigonometric and
+ * hyperbolic functions, unknown ids, and an IF entered through its condition).  With status != 0 nothing is inverted and every row counts
+ * as IMPOSSIBLE.  The ancestors of pos are those the subtree sizes of a well-formed row give; they are taken from the node types, so no
+ * size word but the root's is read.
+ *   evogp_hip_sr_desired          desired f32[pop][D]: t where the state is REQUIRED, NaN elsewhere; state u8[pop][D]; status.
+ *   evogp_hip_sr_backprop_match   writes no (pop, D) array.  lib_t f32[D][n_lib]: the semantics of a library of n_lib subtrees, TRANSPOSED
+ *                                 (entry k on row d at lib_t[d][k]), 1 <= n_lib <= EVOGP_BACKPROP_MAX_LIB.
+ *       dist f64[pop][n_lib]   sum over the REQUIRED rows of ((double)t_d - (double)lib_t[d][k])^2; +inf when lib_t[d][k] is not finite on
+ *                              a REQUIRED row; 0 without a REQUIRED row;
+ *       best i32[pop]          the entry of least dist, the smallest on ties; -1 with status != 0, without a REQUIRED row, or when every
+ *                              dist is +inf;
+ *       cnst f32[pop], const_dist f64[pop]   the mean of t over the REQUIRED rows and their centred sum of squares (what a constant
+ *                              subtree would cost), from float64 sums shifted by a REQUIRED value of the tree; NaN without a REQUIRED row;
+ *       counts i32[pop][3]     the REQUIRED, FREE and IMPOSSIBLE rows; status as above.
+ *     Sums are float64: a lane owns the entries lane, lane + 64, ... and adds the REQUIRED rows of the wave's tiles in ascending order,
+ *     the waves are added in wave order.
+ * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, n_lib outside 1 .. 1024.  Then a NULL pointer: EVOGP_E_NULLPTR; then
+ * out_len != 1: EVOGP_E_UNSUPPORTED.  One launch each, no float atomics, nothing synchronises with the host: bit-identical from run to run.
+ * Rows of more than 64 nodes use the per-stream tape buffer of evogp_hip_sr_gradient, under the same rules.  The outputs must not alias
+ * the inputs or one another. */
+#define EVOGP_BACKPROP_MAX_LIB 1024
+int evogp_hip_sr_desired(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len, const float *value,
+                         const int16_t *type, const int16_t *size, const float *variables, const float *labels, const int *pos,
+                         float *desired /* [pop][D] */, unsigned char *state /* [pop][D] */, int *status /* [pop] */, evogp_stream_t stream);
+int evogp_hip_sr_backprop_match(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                const float *value, const int16_t *type, const int16_t *size, const float *variables, const float *labels,
+                                const int *pos, unsigned n_lib, const float *lib_t /* [D][n_lib] */, double *dist /* [pop][n_lib] */,
+                                int *best, float *cnst, double *const_dist, int *counts /* [pop][3] */, int *status, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -902,7 +937,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
