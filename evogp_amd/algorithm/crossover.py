@@ -6,6 +6,7 @@ from __future__ import annotations
 import torch
 
 from ..tree import Forest
+from .semantic_library import SemanticLibrary
 
 
 class BaseCrossover:
@@ -109,3 +110,75 @@ class CombinedDefaultCrossover(BaseCrossover):
             rpos = (raw[1] % sizes[right.long()]).to(torch.int32)
             children.append(sub.crossover(left, right, lpos, rpos))
         return CombinedForest(children, forest.data_info)
+
+
+# ---- approximately geometric semantic crossover (no counterpart in the reference) ------------------------------------------------------
+class ApproxGeometricCrossover(BaseCrossover):
+    """The approximately geometric semantic crossover (AGX) of Pawlak, Wieloch & Krawiec (IEEE TEVC 2015), next to their Random Desired
+    Operator (``SemanticBackpropMutation``): the recipient is inverted from its root down to a random node towards the MIDPOINT of its
+    own and its mate's predictions on ``datapoints`` (``Forest.SR_midpoint_match``, csrc/sr_backprop.hip), and the
+    subtree at that node is replaced by the member of a LIBRARY of small trees nearest to what the node would have to return -- or,
+    with ``allow_constant``, by the constant that is nearer still.  The offspring lies, approximately, on the segment between its
+    parents in semantic space.  It needs no labels.
+
+    ``library``, ``descriptor``, ``library_size``: as for ``SemanticBackpropMutation``; a ``SemanticLibrary`` may be shared with it,
+    and ``update_library`` on either then reaches both.  Pairs and the recipient's position are drawn as ``DefaultCrossover.draw`` draws
+    them (the donor position is unused); a pair of one tree with itself is not excluded: its midpoint is the tree's own predictions, so
+    the subtree is replaced by the library member nearest to what it already computes.  An offspring without a match (``best == -1``:
+    a function on the path has no inverse, no row is REQUIRED, or no library member is finite there) takes the offspring of the same
+    index from ``fallback`` -- any ``BaseCrossover``, called once with the same arguments -- or is a copy of its recipient.  No host
+    synchronisation of its own."""
+
+    def __init__(self, datapoints: torch.Tensor, library=None, descriptor=None, library_size: int = 256, allow_constant: bool = True,
+                 fallback: BaseCrossover = None):
+        if not isinstance(datapoints, torch.Tensor) or datapoints.dim() != 2 or datapoints.shape[0] == 0:
+            raise ValueError(f"datapoints should be a (D, input_len) tensor, but got {tuple(getattr(datapoints, 'shape', ()))}")
+        if fallback is not None and not isinstance(fallback, BaseCrossover):
+            raise ValueError(f"fallback should be a BaseCrossover, but got {type(fallback).__name__}")
+        self.datapoints = datapoints.contiguous().to(torch.float32)
+        self.allow_constant = bool(allow_constant)
+        self.fallback = fallback
+        self.semantic_library = SemanticLibrary.of(self.datapoints, library, descriptor, library_size, "ApproxGeometricCrossover")
+
+    @property
+    def library(self) -> Forest:
+        return self.semantic_library.library
+
+    @property
+    def semantics(self) -> torch.Tensor:
+        return self.semantic_library.semantics
+
+    def update_library(self, forest: Forest) -> None:
+        """the library becomes the semantically distinct members of ``forest`` on the datapoints (``SemanticLibrary.update_library``);
+        a shared library changes for every operator that holds it.  One host synchronisation."""
+        self.semantic_library.update_library(forest)
+
+    def draw(self, tree_sizes: torch.Tensor, n_parents: int, target_cnt: int, device):
+        """the draws of ``DefaultCrossover``: pairs and positions; the donor position is drawn and not used"""
+        return DefaultCrossover().draw(tree_sizes, n_parents, target_cnt, device)
+
+    def __call__(self, forest: Forest, survivor_indices: torch.Tensor, target_cnt: int, fitness: torch.Tensor):
+        parents = forest[survivor_indices]
+        sizes = parents.batch_subtree_size[:, 0]
+        left, right, left_pos, _ = self.draw(sizes, len(parents), target_cnt, sizes.device)
+        new, found = self.apply(parents, left, right, left_pos)
+        if self.fallback is not None:
+            other = self.fallback(forest, survivor_indices, target_cnt, fitness)
+            new = Forest(new.input_len, 1, *(torch.where(found[:, None], a, b) for a, b in zip(new._tensors(), other._tensors())),
+                         func_mask=Forest.join_masks(new.func_mask, other.func_mask))
+        return new
+
+    def apply(self, parents: Forest, left: torch.Tensor, right: torch.Tensor, left_pos: torch.Tensor):
+        """``(offspring, found)``: offspring n is ``parents[left[n]]`` with the subtree at ``left_pos[n]`` replaced by the donor that
+        brings it nearest to the midpoint between itself and ``parents[right[n]]``; a verbatim copy where ``found[n]`` is False.  No
+        host synchronisation."""
+        if parents.output_len != 1 or parents.input_len != self.library.input_len:
+            raise ValueError(f"ApproxGeometricCrossover: the forest should have {self.library.input_len} inputs and one output, but has "
+                             f"{parents.input_len} and {parents.output_len}")
+        self.semantic_library.rows(parents.max_tree_len)   # (a library wider than the forest: ValueError before anything runs)
+        chosen = parents[left.to(torch.int64)]
+        left_pos = left_pos.to(torch.int32)
+        best, dist, const, const_dist, _, _ = chosen.SR_midpoint_match(self.datapoints, left_pos, parents, self.semantics, mate_index=right)
+        found = best >= 0
+        donors = self.semantic_library.donors(best, dist, const, const_dist, self.allow_constant, parents.input_len, parents.max_tree_len)
+        return chosen.mutate(torch.where(found, left_pos, torch.full_like(left_pos, -1)), donors), found   # (position -1: a copy)

@@ -11,6 +11,7 @@ from typing import Optional
 import torch
 
 from ..tree import MAX_STACK, Forest, GenerateDescriptor, NType
+from .semantic_library import SemanticLibrary
 
 
 class BaseMutation:
@@ -80,16 +81,6 @@ class DefaultMutation(BaseMutation):
 
 
 # ---- semantic backpropagation (no counterpart in the reference) --------------------------------------------------------------------
-def _leaf_rows(values: torch.Tensor, ntype: int, max_tree_len: int):
-    """one-node trees holding ``values`` (n,) as (value, type, size) rows of ``max_tree_len`` words"""
-    n = values.shape[0]
-    value = torch.zeros((n, max_tree_len), dtype=torch.float32, device=values.device)
-    node_type = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
-    size = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
-    value[:, 0], node_type[:, 0], size[:, 0] = values.to(torch.float32), ntype, 1
-    return value, node_type, size
-
-
 class SemanticBackpropMutation(BaseMutation):
     """The Random Desired Operator of Pawlak, Wieloch & Krawiec (IEEE TEVC 2015): a mutating tree is inverted from its root down to a
     random node on the rows of the dataset (``Forest.SR_backprop_match``, csrc/sr_backprop.hip), which gives the values
@@ -97,8 +88,8 @@ class SemanticBackpropMutation(BaseMutation):
     of small trees whose values on the rows are nearest to them -- or, with ``allow_constant``, by the constant that is nearer still.
     The first variation operator here that looks at ``datapoints`` and ``labels``.
 
-    ``library``: a single-output Forest (at most 1024 trees).  Without one it is built from ``descriptor``: the one-node tree of every
-    variable and ``library_size`` random trees, reduced to one member per semantics (``semantic_unique(datapoints, keep="smallest")``)
+    ``library``: a single-output Forest (at most 1024 trees), or a ``SemanticLibrary`` (semantic_library.py) shared with other operators,
+    ``ApproxGeometricCrossover`` among them.  Without one it is built from ``descriptor``: the one-node tree of every variable and ``library_size`` random trees, reduced to one member per semantics (``semantic_unique(datapoints, keep="smallest")``)
     and truncated to 1024; its semantics are computed once.  ``update_library(forest)`` replaces it by the semantically distinct members
     of a forest, e.g. of the population.  A library narrower than the forest is padded to the forest's ``max_tree_len``; a wider one
     is a ``ValueError`` at the call.
@@ -111,7 +102,7 @@ class SemanticBackpropMutation(BaseMutation):
 
     takes_skip_rows = True
 
-    def __init__(self, mutation_rate: float, datapoints: torch.Tensor, labels: torch.Tensor, library: Optional[Forest] = None,
+    def __init__(self, mutation_rate: float, datapoints: torch.Tensor, labels: torch.Tensor, library=None,
                  descriptor: Optional[GenerateDescriptor] = None, library_size: int = 256, allow_constant: bool = True,
                  fallback: Optional[BaseMutation] = None):
         if datapoints.dim() != 2 or labels.shape[0] != datapoints.shape[0] or labels.numel() != datapoints.shape[0]:
@@ -123,43 +114,20 @@ class SemanticBackpropMutation(BaseMutation):
         self.labels = labels.reshape(-1, 1).contiguous().to(torch.float32)
         self.allow_constant = bool(allow_constant)
         self.fallback = fallback
-        if library is None:
-            if descriptor is None:
-                raise ValueError("SemanticBackpropMutation needs a library or a descriptor to build one from")
-            if descriptor.output_len != 1 or descriptor.input_len != datapoints.shape[1]:
-                raise ValueError(f"the descriptor should generate single-output trees of {datapoints.shape[1]} inputs, but has "
-                                 f"{descriptor.input_len} inputs and {descriptor.output_len} outputs")
-            if not isinstance(library_size, int) or library_size < 0:
-                raise ValueError(f"library_size should be a non-negative integer, but got {library_size!r}")
-            dev = self.datapoints.device
-            variables = Forest(descriptor.input_len, 1, *_leaf_rows(torch.arange(descriptor.input_len, device=dev), NType.VAR, descriptor.max_tree_len),
-                               func_mask=descriptor.func_mask)
-            library = variables + Forest.random_generate(library_size, descriptor) if library_size else variables
-        self.update_library(library)
+        self.semantic_library = SemanticLibrary.of(self.datapoints, library, descriptor, library_size, "SemanticBackpropMutation")
+
+    @property
+    def library(self) -> Forest:
+        return self.semantic_library.library
+
+    @property
+    def semantics(self) -> torch.Tensor:
+        return self.semantic_library.semantics
 
     def update_library(self, forest: Forest) -> None:
-        """the library becomes the semantically distinct members of ``forest`` on the datapoints (the smallest tree of every class, in
-        index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation."""
-        from ..tree.forest import BACKPROP_MAX_LIBRARY
-
-        if not isinstance(forest, Forest) or forest.output_len != 1 or forest.input_len != self.datapoints.shape[1]:
-            raise ValueError(f"the library should be a single-output Forest of {self.datapoints.shape[1]} inputs")
-        unique, _, _ = forest.semantic_unique(self.datapoints, keep="smallest")
-        self.library = unique[:BACKPROP_MAX_LIBRARY] if unique.pop_size > BACKPROP_MAX_LIBRARY else unique
-        self.semantics = self.library.batch_forward(self.datapoints)[:, :, 0].contiguous()
-        self._padded = {}
-
-    def _library_rows(self, max_tree_len: int):
-        """the library's three tensors at the forest's row width"""
-        lib = self.library
-        if lib.max_tree_len == max_tree_len:
-            return lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size
-        if lib.max_tree_len > max_tree_len:
-            raise ValueError(f"the library's max_tree_len {lib.max_tree_len} exceeds the forest's {max_tree_len}")
-        if max_tree_len not in self._padded:
-            pad = (0, max_tree_len - lib.max_tree_len)
-            self._padded[max_tree_len] = tuple(torch.nn.functional.pad(a, pad) for a in (lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size))
-        return self._padded[max_tree_len]
+        """the library becomes the semantically distinct members of ``forest`` on the datapoints (``SemanticLibrary.update_library``);
+        a shared library changes for every operator that holds it.  One host synchronisation."""
+        self.semantic_library.update_library(forest)
 
     def __call__(self, forest: Forest, skip_rows: int = 0) -> Forest:
         dev = forest.batch_node_value.device
@@ -177,18 +145,12 @@ class SemanticBackpropMutation(BaseMutation):
         if forest.output_len != 1 or forest.input_len != self.library.input_len:
             raise ValueError(f"SemanticBackpropMutation: the forest should have {self.library.input_len} inputs and one output, but has "
                              f"{forest.input_len} and {forest.output_len}")
-        lib_value, lib_type, lib_size = self._library_rows(forest.max_tree_len)
+        self.semantic_library.rows(forest.max_tree_len)   # (a library wider than the forest: ValueError before anything runs)
         chosen = forest[rows]
         positions = positions.to(torch.int32)
         best, dist, const, const_dist, _, _ = chosen.SR_backprop_match(self.datapoints, self.labels, positions, self.semantics)
         found = best >= 0
-        member = best.clamp(min=0).to(torch.int64)
-        value, node_type, size = lib_value[member], lib_type[member], lib_size[member]
-        if self.allow_constant:
-            nearer = found & (const_dist < dist.gather(1, member[:, None]).squeeze(1))
-            cv, ct, cs = _leaf_rows(const, NType.CONST, forest.max_tree_len)
-            value, node_type, size = (torch.where(nearer[:, None], c, a) for c, a in ((cv, value), (ct, node_type), (cs, size)))
-        donors = Forest(forest.input_len, 1, value, node_type, size, func_mask=self.library.func_mask)
+        donors = self.semantic_library.donors(best, dist, const, const_dist, self.allow_constant, forest.input_len, forest.max_tree_len)
         new = chosen.mutate(torch.where(found, positions, torch.full_like(positions, -1)), donors)   # (position -1: the row is copied)
         if self.fallback is not None:
             other = self._fall_back(chosen)

@@ -1,0 +1,92 @@
+"""The library of small trees the semantic operators draw their donors from (``SemanticBackpropMutation``,
+``ApproxGeometricCrossover``): its build from a descriptor, ``update_library``, its semantics on the datapoints
+and its rows padded to a forest's width.  One object may serve several operators: an ``update_library`` call on it reaches them all."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from ..tree import Forest, GenerateDescriptor, NType
+
+
+def leaf_rows(values: torch.Tensor, ntype: int, max_tree_len: int):
+    """one-node trees holding ``values`` (n,) as (value, type, size) rows of ``max_tree_len`` words"""
+    n = values.shape[0]
+    value = torch.zeros((n, max_tree_len), dtype=torch.float32, device=values.device)
+    node_type = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
+    size = torch.zeros((n, max_tree_len), dtype=torch.int16, device=values.device)
+    value[:, 0], node_type[:, 0], size[:, 0] = values.to(torch.float32), ntype, 1
+    return value, node_type, size
+
+
+class SemanticLibrary:
+    """``library``: a single-output Forest (at most 1024 trees are kept).  Without one it is built from ``descriptor``: the one-node
+    tree of every variable and ``library_size`` random trees.  Either way it is reduced to one member per semantics
+    (``semantic_unique(datapoints, keep="smallest")``) and truncated to 1024; ``semantics`` (K, D) float32 is computed once.
+    ``owner`` names the operator in the error texts."""
+
+    def __init__(self, datapoints: torch.Tensor, library: Optional[Forest] = None, descriptor: Optional[GenerateDescriptor] = None,
+                 library_size: int = 256, owner: str = "SemanticLibrary"):
+        self.datapoints = datapoints
+        if library is None:
+            if descriptor is None:
+                raise ValueError(f"{owner} needs a library or a descriptor to build one from")
+            if descriptor.output_len != 1 or descriptor.input_len != datapoints.shape[1]:
+                raise ValueError(f"the descriptor should generate single-output trees of {datapoints.shape[1]} inputs, but has "
+                                 f"{descriptor.input_len} inputs and {descriptor.output_len} outputs")
+            if not isinstance(library_size, int) or library_size < 0:
+                raise ValueError(f"library_size should be a non-negative integer, but got {library_size!r}")
+            dev = self.datapoints.device
+            variables = Forest(descriptor.input_len, 1, *leaf_rows(torch.arange(descriptor.input_len, device=dev), NType.VAR, descriptor.max_tree_len),
+                               func_mask=descriptor.func_mask)
+            library = variables + Forest.random_generate(library_size, descriptor) if library_size else variables
+        self.update_library(library)
+
+    @classmethod
+    def of(cls, datapoints: torch.Tensor, library, descriptor, library_size, owner: str) -> "SemanticLibrary":
+        """what an operator's ``library=`` argument stands for: a shared SemanticLibrary as it is, or a new one"""
+        if isinstance(library, SemanticLibrary):
+            if tuple(library.datapoints.shape) != tuple(datapoints.shape):
+                raise ValueError(f"the shared library was built on datapoints of shape {tuple(library.datapoints.shape)}, "
+                                 f"but {owner} has {tuple(datapoints.shape)}")
+            return library
+        return cls(datapoints, library, descriptor, library_size, owner)
+
+    def update_library(self, forest: Forest) -> None:
+        """the library becomes the semantically distinct members of ``forest`` on the datapoints (the smallest tree of every class, in
+        index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation."""
+        from ..tree.forest import BACKPROP_MAX_LIBRARY
+
+        if not isinstance(forest, Forest) or forest.output_len != 1 or forest.input_len != self.datapoints.shape[1]:
+            raise ValueError(f"the library should be a single-output Forest of {self.datapoints.shape[1]} inputs")
+        unique, _, _ = forest.semantic_unique(self.datapoints, keep="smallest")
+        self.library = unique[:BACKPROP_MAX_LIBRARY] if unique.pop_size > BACKPROP_MAX_LIBRARY else unique
+        self.semantics = self.library.batch_forward(self.datapoints)[:, :, 0].contiguous()
+        self._padded = {}
+
+    def rows(self, max_tree_len: int):
+        """the library's three tensors at the forest's row width"""
+        lib = self.library
+        if lib.max_tree_len == max_tree_len:
+            return lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size
+        if lib.max_tree_len > max_tree_len:
+            raise ValueError(f"the library's max_tree_len {lib.max_tree_len} exceeds the forest's {max_tree_len}")
+        if max_tree_len not in self._padded:
+            pad = (0, max_tree_len - lib.max_tree_len)
+            self._padded[max_tree_len] = tuple(torch.nn.functional.pad(a, pad) for a in (lib.batch_node_value, lib.batch_node_type, lib.batch_subtree_size))
+        return self._padded[max_tree_len]
+
+    def donors(self, best: torch.Tensor, dist: torch.Tensor, const: torch.Tensor, const_dist: torch.Tensor, allow_constant: bool,
+               input_len: int, max_tree_len: int) -> Forest:
+        """the donor of every matched tree: the member ``best`` (member 0 where best is -1: such a row is not spliced), or with
+        ``allow_constant`` the one-node CONST where it is nearer than that member"""
+        lib_value, lib_type, lib_size = self.rows(max_tree_len)
+        found = best >= 0
+        member = best.clamp(min=0).to(torch.int64)
+        value, node_type, size = lib_value[member], lib_type[member], lib_size[member]
+        if allow_constant:
+            nearer = found & (const_dist < dist.gather(1, member[:, None]).squeeze(1))
+            cv, ct, cs = leaf_rows(const, NType.CONST, max_tree_len)
+            value, node_type, size = (torch.where(nearer[:, None], c, a) for c, a in ((cv, value), (ct, node_type), (cs, size)))
+        return Forest(input_len, 1, value, node_type, size, func_mask=self.library.func_mask)

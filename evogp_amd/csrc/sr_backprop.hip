@@ -30,8 +30,17 @@
 //   The waves' sums meet in one LDS row in wave order; the constant's moments are float64 sums SHIFTED by the wave's first REQUIRED value
 //   (the pilot, as sr_genes.hip), merged in wave order by the pairwise update of Chan, Golub & LeVeque.
 // No float atomics, nothing synchronises with the host: the same inputs give the same bits.
+//
+// MID == true (approximately geometric semantic crossover; tests/agx_ref.py restates it) takes the root target
+// from a MATE instead of the labels: tree t is paired with row mate[t] of a second forest of the same row width, and on row d the target
+// is mid = 0.5f * T_t(x_d) + 0.5f * T_mate(x_d), REQUIRED where mid is finite and IMPOSSIBLE from the start where it is not.  Wave 0
+// classifies the mate as well and builds its operand table first (its build stack is the words that then hold the parent table); per
+// tile a wave walks the mate forward onto the value tape, keeps its root value in a register and walks the recipient over the same
+// tape.  Status 4: mate[t] is outside [0, n_mates) or the mate's row is malformed.  y is not read.
 #include "sr_forward.hpp"
 #include "sr_moments.hpp"
+
+#include <type_traits>
 
 namespace evogp {
 
@@ -40,7 +49,7 @@ constexpr int kBackpropAcc = kBackpropMaxLib / kWave;   // float64 sums per lane
 static_assert(kBackpropAcc * kWave == kBackpropMaxLib && kBackpropAcc == 16, "lane j owns the entries j, j + 64, ...: 16 of them at most");
 
 enum : int { BP_REQUIRED = 0, BP_FREE = 1, BP_IMPOSSIBLE = 2 };
-enum : int { BP_OK = 0, BP_MALFORMED = 1, BP_POSITION = 2, BP_BLOCKED = 3 };
+enum : int { BP_OK = 0, BP_MALFORMED = 1, BP_POSITION = 2, BP_BLOCKED = 3, BP_MATE = 4 };
 // the rules, the operand the path takes folded in; up to R_MIN the word's index is the SIBLING's (a NaN there: IMPOSSIBLE)
 enum : uint32_t { R_ADD = 0, R_SUB0, R_SUB1, R_MUL, R_DIV0, R_DIV1, R_MAX, R_MIN, R_NEG, R_INV, R_SQRT, R_ABS, R_EXP, R_LOG, R_IF1, R_IF2, R_NONE };
 
@@ -63,6 +72,14 @@ struct BackpropParams {
     float *tape;          // global tapes (rows longer than kTapeLdsLen): [blocks * W][2][gp_len][64]; nullptr: the tapes are in LDS
     int pop, D, gp_len, var_len, K, KB;   // KB: the bucket of K the LDS row of sums is sized for (0: materialising)
 };
+// the MID builds' arguments: the labelled builds keep their own struct, and with it their kernel-argument layout
+struct BackpropMidParams : BackpropParams {
+    const float *mvalue;  // the mates: a forest of n_mates rows of gp_len words
+    const int16_t *mtype;
+    const int16_t *msize;
+    const int *mate;      // [pop]          the mate's row of every tree
+    int n_mates;
+};
 
 // Dynamic LDS of one workgroup in front of the tapes: sums[KB] mom[W][2] (double), op[L] kid[L] pay[L] parent[L] path[L] (u32),
 // cnt[W][4] (REQUIRED, FREE, IMPOSSIBLE, the pilot's bits), meta[4] (class, length, status, steps)
@@ -72,6 +89,39 @@ __host__ __device__ inline size_t backprop_lds_head_words(int L, int W) {
 }
 __device__ inline size_t backprop_head_words(int KB, int L, int W) {
     return (((size_t)2 * KB + (size_t)4 * W + (size_t)5 * L + (size_t)4 * W + 4) + 3) & ~(size_t)3;
+}
+// The MID builds: behind meta the mate's operand table mop[L] mkid[L] mpay[L] and its length mmeta[4]
+template <int KB>
+__host__ __device__ inline size_t backprop_mid_lds_head_words(int L, int W) {
+    return (((size_t)2 * KB + (size_t)4 * W + (size_t)8 * L + (size_t)4 * W + 8) + 3) & ~(size_t)3;
+}
+__device__ inline size_t backprop_mid_head_words(int KB, int L, int W) {
+    return (((size_t)2 * KB + (size_t)4 * W + (size_t)8 * L + (size_t)4 * W + 8) + 3) & ~(size_t)3;
+}
+
+// one forward walk of a tree of `len` nodes in execution order: every node's value of this lane's row on the tape
+__device__ inline void backprop_forward(const uint32_t *s_op, const uint32_t *s_kid, const uint32_t *s_pay, int len, const float *xr,
+                                        float *val, int lane) {
+    for (int i = len - 1; i >= 0; --i) {
+        const uint32_t op = (uint32_t)uni((int)s_op[i]) & kOpMask;
+        float v;
+        if (op < H_ADD) {
+            const uint32_t pay = (uint32_t)uni((int)s_pay[i]);
+            v = op == H_CONST ? bits2f(pay) : xr[pay];
+        } else {
+            const uint32_t kid = (uint32_t)uni((int)s_kid[i]);
+            const float a = val[(kid & 1023u) * kWave + lane];
+            if (op < H_UN) {
+                v = binary_value(op, a, val[((kid >> 10) & 1023u) * kWave + lane]);
+            } else if (op < H_IF) {
+                v = op_unary<false>(op, a);
+            } else {
+                const float b = val[((kid >> 10) & 1023u) * kWave + lane], c = val[(kid >> 20) * kWave + lane];
+                v = a > 0.0f ? b : c;
+            }
+        }
+        val[i * kWave + lane] = v;
+    }
 }
 
 // the rule of function node `op` in operand k, and which of its operands the rule reads: one index in bits 0..9, an IF's other branch
@@ -128,8 +178,8 @@ __device__ inline void backprop_step(uint32_t rule, float s, float b, float &t, 
     if (state == BP_REQUIRED) { state = ns; t = d; }
 }
 
-template <bool FUSED>
-__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_backprop_kernel(BackpropParams p) {
+template <bool FUSED, bool MID = false>
+__global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_backprop_kernel(std::conditional_t<MID, BackpropMidParams, BackpropParams> p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t bp_lds[];
     const int L = p.gp_len;
     const int K = p.K;
@@ -143,8 +193,11 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_backprop_kernel(Backpro
     uint32_t *s_path = (uint32_t *)(s_par + L);
     int *s_cnt = (int *)(s_path + L);
     int *s_meta = s_cnt + 4 * W;
+    uint32_t *s_mop = (uint32_t *)(s_meta + 4), *s_mkid = s_mop + L, *s_mpay = s_mkid + L;   // (MID) the mate's table and length
+    int *s_mmeta = (int *)(s_mpay + L);
     float *val = p.tape ? p.tape + ((size_t)blockIdx.x * W + w) * 2 * L * kWave
-                        : (float *)(bp_lds + backprop_head_words(p.KB, L, W)) + (size_t)w * 2 * L * kWave;
+                        : (float *)(bp_lds + (MID ? backprop_mid_head_words(p.KB, L, W) : backprop_head_words(p.KB, L, W))) +
+                              (size_t)w * 2 * L * kWave;
     const int ntiles = (p.D + kWave - 1) / kWave;
     const float nanf_ = __builtin_nanf("");
 
@@ -158,6 +211,21 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_backprop_kernel(Backpro
             const int at = uni(p.pos[t]);
             int status = cls != TREE_OK ? BP_MALFORMED : (at < 0 || at >= len) ? BP_POSITION : BP_OK;
             int steps = 0;
+            if constexpr (MID) if (status == BP_OK) {
+                // the mate: its row in range, well-formed; its table first, built with the words that then hold the parent table
+                const int m = uni(p.mate[t]);
+                status = BP_MATE;
+                if (m >= 0 && m < p.n_mates) {
+                    const size_t mrow = (size_t)m * L;
+                    int mlen = uni((int)p.msize[mrow]);
+                    mlen = mlen < 0 ? 0 : (mlen > L ? L : mlen);
+                    if (uni(classify_tree(p.mtype + mrow, p.mvalue + mrow, mlen, false, p.var_len, 1, kMaxStack)) == TREE_OK) {
+                        build_operand_table<false>(p.mtype, p.mvalue, mrow, mlen, p.var_len, 1, s_mop, s_mkid, s_mpay, s_par);
+                        if (lane == 0) s_mmeta[0] = mlen;
+                        status = BP_OK;
+                    }
+                }
+            }
             if (status == BP_OK) {
                 build_operand_table<false>(p.type, p.value, row, len, p.var_len, 1, s_op, s_kid, s_pay, s_par);
                 // the parent of every node: index | operand << 10 (the root's word stays 0)
@@ -224,30 +292,22 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_backprop_kernel(Backpro
             const bool valid = d < p.D;
             const int dc = valid ? d : p.D - 1;
             const float *xr = p.X + (size_t)dc * p.var_len;
-            // ---- forward: execution order, every node's value on the tape ----
-            for (int i = len - 1; i >= 0; --i) {
-                const uint32_t op = (uint32_t)uni((int)s_op[i]) & kOpMask;
-                float v;
-                if (op < H_ADD) {
-                    const uint32_t pay = (uint32_t)uni((int)s_pay[i]);
-                    v = op == H_CONST ? bits2f(pay) : xr[pay];
-                } else {
-                    const uint32_t kid = (uint32_t)uni((int)s_kid[i]);
-                    const float a = val[(kid & 1023u) * kWave + lane];
-                    if (op < H_UN) {
-                        v = binary_value(op, a, val[((kid >> 10) & 1023u) * kWave + lane]);
-                    } else if (op < H_IF) {
-                        v = op_unary<false>(op, a);
-                    } else {
-                        const float b = val[((kid >> 10) & 1023u) * kWave + lane], c = val[(kid >> 20) * kWave + lane];
-                        v = a > 0.0f ? b : c;
-                    }
-                }
-                val[i * kWave + lane] = v;
+            // ---- forward: execution order, every node's value on the tape (MID: the mate first, its root value kept) ----
+            float mroot = 0.0f;
+            if constexpr (MID) {
+                backprop_forward(s_mop, s_mkid, s_mpay, uni(s_mmeta[0]), xr, val, lane);
+                mroot = val[lane];
             }
+            backprop_forward(s_op, s_kid, s_pay, len, xr, val, lane);
             // ---- downward: from the root's step to the step above pos ----
-            float tgt = p.y[dc];
+            float tgt;
             int st = BP_REQUIRED;
+            if (MID) {   // the midpoint of the two roots: two scalings and one addition; not finite: IMPOSSIBLE from the start
+                tgt = 0.5f * val[lane] + 0.5f * mroot;
+                if (!finite_f(tgt)) st = BP_IMPOSSIBLE;
+            } else {
+                tgt = p.y[dc];
+            }
             for (int j = steps - 1; j >= 0; --j) {
                 const uint32_t word = (uint32_t)uni((int)s_path[j]);
                 backprop_step(word >> 20, val[(word & 1023u) * kWave + lane], val[((word >> 10) & 1023u) * kWave + lane], tgt, st);
@@ -369,15 +429,16 @@ static int backprop_check(unsigned pop_size, unsigned data_points, unsigned gp_l
     return 0;
 }
 
-template <bool FUSED, int KB>
-static int backprop_launch(BackpropParams &p, hipStream_t stream) {
+template <bool FUSED, int KB, bool MID = false>
+static int backprop_launch(std::conditional_t<MID, BackpropMidParams, BackpropParams> &p, hipStream_t stream) {
     p.KB = KB;
     TapePlan plan;
-    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, backprop_lds_head_words<KB>, &plan)) return rc;
+    if (const int rc = plan_tape_launch(p.pop, p.D, p.gp_len, stream, MID ? backprop_mid_lds_head_words<KB> : backprop_lds_head_words<KB>, &plan))
+        return rc;
     p.tape = plan.tape;
     static LdsGrant grant;
-    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_backprop_kernel<FUSED>})) return (int)e;
-    hipLaunchKernelGGL(sr_backprop_kernel<FUSED>, dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
+    if (const hipError_t e = grant_tape_lds(grant, {(const void *)sr_backprop_kernel<FUSED, MID>})) return (int)e;
+    hipLaunchKernelGGL((sr_backprop_kernel<FUSED, MID>), dim3((unsigned)plan.blocks), dim3(plan.W * 64), plan.lds, stream, p);
     return (int)hipGetLastError();
 }
 
@@ -413,4 +474,44 @@ extern "C" int evogp_hip_sr_backprop_match(unsigned pop_size, unsigned data_poin
     if (n_lib <= 64) return backprop_launch<true, 64>(p, stream);
     if (n_lib <= 256) return backprop_launch<true, 256>(p, stream);
     return backprop_launch<true, kBackpropMaxLib>(p, stream);
+}
+
+// ---- the midpoint builds: the root target from a mate (n_mates rows of the same width, mate i32[pop]) instead of the labels ----
+extern "C" int evogp_hip_sr_desired_mid(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                        const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                        unsigned n_mates, const float *mvalue, const int16_t *mtype, const int16_t *msize, const int *mate,
+                                        const int *pos, float *desired, unsigned char *state, int *status, evogp_stream_t stream_) {
+    if (const int rc = backprop_check(pop_size, data_points, gp_len, var_len, out_len)) return rc;
+    if (n_mates == 0 || n_mates > 0x7FFFFFFFu) return EVOGP_E_BADARG;
+    if (!value || !type || !size || !variables || !mvalue || !mtype || !msize || !mate || !pos || !desired || !state || !status)
+        return EVOGP_E_NULLPTR;
+    if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    BackpropMidParams p{};
+    p.value = value; p.type = type; p.size = size; p.X = variables; p.pos = pos;
+    p.mvalue = mvalue; p.mtype = mtype; p.msize = msize; p.mate = mate; p.n_mates = (int)n_mates;
+    p.desired = desired; p.state = state; p.status = status;
+    p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len;
+    return backprop_launch<false, 0, true>(p, (hipStream_t)stream_);
+}
+
+extern "C" int evogp_hip_sr_agx_match(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                      const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                      unsigned n_mates, const float *mvalue, const int16_t *mtype, const int16_t *msize, const int *mate,
+                                      const int *pos, unsigned n_lib, const float *lib_t, double *dist, int *best, float *cnst,
+                                      double *const_dist, int *counts, int *status, evogp_stream_t stream_) {
+    if (const int rc = backprop_check(pop_size, data_points, gp_len, var_len, out_len)) return rc;
+    if (n_mates == 0 || n_mates > 0x7FFFFFFFu || n_lib == 0 || n_lib > (unsigned)kBackpropMaxLib) return EVOGP_E_BADARG;
+    if (!value || !type || !size || !variables || !mvalue || !mtype || !msize || !mate || !pos || !lib_t || !dist || !best || !cnst ||
+        !const_dist || !counts || !status)
+        return EVOGP_E_NULLPTR;
+    if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    BackpropMidParams p{};
+    p.value = value; p.type = type; p.size = size; p.X = variables; p.pos = pos; p.lib_t = lib_t;
+    p.mvalue = mvalue; p.mtype = mtype; p.msize = msize; p.mate = mate; p.n_mates = (int)n_mates;
+    p.dist = dist; p.best = best; p.cnst = cnst; p.const_dist = const_dist; p.counts = counts; p.status = status;
+    p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len; p.K = (int)n_lib;
+    const hipStream_t stream = (hipStream_t)stream_;
+    if (n_lib <= 64) return backprop_launch<true, 64, true>(p, stream);
+    if (n_lib <= 256) return backprop_launch<true, 256, true>(p, stream);
+    return backprop_launch<true, kBackpropMaxLib, true>(p, stream);
 }

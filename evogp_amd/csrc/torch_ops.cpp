@@ -711,16 +711,17 @@ struct BackpropCall {
     int64_t D, var_len;
 };
 
+// (labels == nullptr: the midpoint ops, which take their target from a mate)
 BackpropCall check_backprop(const char *op, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
-                            const Tensor &labels, const Tensor &pos) {
+                            const Tensor *labels, const Tensor &pos) {
     BackpropCall c{Forest::infer(value, type, size), 0, 0};
     TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
                 ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
     TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, "too many data points: ", variables.size(0));
     c.D = variables.size(0), c.var_len = variables.size(1);
     check_tensor(variables, {c.D, c.var_len}, "variables", c.f.dev, at::kFloat);
-    if (labels.dim() == 2) check_tensor(labels, {c.D, 1}, "labels", c.f.dev, at::kFloat);   // (D,) or (D, 1)
-    else check_tensor(labels, {c.D}, "labels", c.f.dev, at::kFloat);
+    if (labels && labels->dim() == 2) check_tensor(*labels, {c.D, 1}, "labels", c.f.dev, at::kFloat);   // (D,) or (D, 1)
+    else if (labels) check_tensor(*labels, {c.D}, "labels", c.f.dev, at::kFloat);
     check_tensor(pos, {c.f.pop}, "pos", c.f.dev, at::kInt);
     return c;
 }
@@ -729,7 +730,7 @@ BackpropCall check_backprop(const char *op, const Tensor &value, const Tensor &t
 // the tree to hit the label (evogp_hip_sr_desired)
 std::tuple<Tensor, Tensor, Tensor> tree_SR_desired(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables,
                                                    const Tensor &labels, const Tensor &pos) {
-    const BackpropCall c = check_backprop("tree_SR_desired", value, type, size, variables, labels, pos);
+    const BackpropCall c = check_backprop("tree_SR_desired", value, type, size, variables, &labels, pos);
     c10::DeviceGuard guard(c.f.dev);
     Tensor desired = empty({c.f.pop, c.D}, at::kFloat, c.f.dev), state = empty({c.f.pop, c.D}, at::kByte, c.f.dev);
     Tensor status = empty({c.f.pop}, at::kInt, c.f.dev);
@@ -746,7 +747,7 @@ std::tuple<Tensor, Tensor, Tensor> tree_SR_desired(const Tensor &value, const Te
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_SR_backprop_match(const Tensor &value, const Tensor &type, const Tensor &size,
                                                                                 const Tensor &variables, const Tensor &labels, const Tensor &pos,
                                                                                 const Tensor &lib) {
-    const BackpropCall c = check_backprop("tree_SR_backprop_match", value, type, size, variables, labels, pos);
+    const BackpropCall c = check_backprop("tree_SR_backprop_match", value, type, size, variables, &labels, pos);
     TORCH_CHECK(lib.dim() == 2 && lib.size(0) >= 1 && lib.size(0) <= EVOGP_BACKPROP_MAX_LIB,
                 "tree_SR_backprop_match: lib must be a (K, data_points) tensor with K in [1, ", EVOGP_BACKPROP_MAX_LIB, "], but got shape ", lib.sizes());
     const int64_t K = lib.size(0);
@@ -761,6 +762,64 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_SR_backprop_matc
                                          lib_t.data_ptr<float>(), dist.data_ptr<double>(), best.data_ptr<int>(), cnst.data_ptr<float>(),
                                          const_dist.data_ptr<double>(), counts.data_ptr<int>(), status.data_ptr<int>(), current_stream(c.f.dev)),
              "tree_SR_backprop_match");
+    return {best, dist, cnst, const_dist, counts, status};
+}
+
+// the mates of the two midpoint ops: a forest of n_mates >= 1 rows of the recipients' width on their device, and mate (pop,) int32 (its
+// RANGE is the kernel's to report: status 4)
+Forest check_mates(const char *op, const BackpropCall &c, const Tensor &mvalue, const Tensor &mtype, const Tensor &msize, const Tensor &mate) {
+    TORCH_CHECK(mvalue.dim() == 2 && mvalue.size(0) >= 1 && mvalue.size(0) <= 0x7FFFFFFF, op,
+                ": mate_value must be a (n_mates, gp_len) tensor with n_mates > 0, but got shape ", mvalue.sizes());
+    const int64_t n = mvalue.size(0);
+    check_tensor(mvalue, {n, c.f.gp_len}, "mate_value", c.f.dev, at::kFloat);
+    check_tensor(mtype, {n, c.f.gp_len}, "mate_type", c.f.dev, at::kShort);
+    check_tensor(msize, {n, c.f.gp_len}, "mate_size", c.f.dev, at::kShort);
+    check_tensor(mate, {c.f.pop}, "mate", c.f.dev, at::kInt);
+    Forest m = c.f;
+    m.pop = n, m.value = mvalue.data_ptr<float>(), m.type = mtype.data_ptr<int16_t>(), m.size = msize.data_ptr<int16_t>();
+    return m;
+}
+
+// tree_SR_desired with the root target taken from a mate: 0.5 * T_t + 0.5 * T_mate[t] on every row (evogp_hip_sr_desired_mid); status 4: a
+// mate index outside the mates, or a malformed mate
+std::tuple<Tensor, Tensor, Tensor> tree_SR_desired_mid(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &mvalue,
+                                                       const Tensor &mtype, const Tensor &msize, const Tensor &variables, const Tensor &pos,
+                                                       const Tensor &mate) {
+    const BackpropCall c = check_backprop("tree_SR_desired_mid", value, type, size, variables, nullptr, pos);
+    const Forest m = check_mates("tree_SR_desired_mid", c, mvalue, mtype, msize, mate);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor desired = empty({c.f.pop, c.D}, at::kFloat, c.f.dev), state = empty({c.f.pop, c.D}, at::kByte, c.f.dev);
+    Tensor status = empty({c.f.pop}, at::kInt, c.f.dev);
+    check_rc(evogp_hip_sr_desired_mid((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type,
+                                      c.f.size, variables.data_ptr<float>(), (unsigned)m.pop, m.value, m.type, m.size, mate.data_ptr<int>(),
+                                      pos.data_ptr<int>(), desired.data_ptr<float>(), state.data_ptr<uint8_t>(), status.data_ptr<int>(),
+                                      current_stream(c.f.dev)),
+             "tree_SR_desired_mid");
+    return {desired, state, status};
+}
+
+// tree_SR_backprop_match with the root target taken from a mate (evogp_hip_sr_agx_match)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> tree_SR_agx_match(const Tensor &value, const Tensor &type, const Tensor &size,
+                                                                           const Tensor &mvalue, const Tensor &mtype, const Tensor &msize,
+                                                                           const Tensor &variables, const Tensor &pos, const Tensor &mate,
+                                                                           const Tensor &lib) {
+    const BackpropCall c = check_backprop("tree_SR_agx_match", value, type, size, variables, nullptr, pos);
+    const Forest m = check_mates("tree_SR_agx_match", c, mvalue, mtype, msize, mate);
+    TORCH_CHECK(lib.dim() == 2 && lib.size(0) >= 1 && lib.size(0) <= EVOGP_BACKPROP_MAX_LIB,
+                "tree_SR_agx_match: lib must be a (K, data_points) tensor with K in [1, ", EVOGP_BACKPROP_MAX_LIB, "], but got shape ", lib.sizes());
+    const int64_t K = lib.size(0);
+    check_tensor(lib, {K, c.D}, "lib", c.f.dev, at::kFloat);
+    c10::DeviceGuard guard(c.f.dev);
+    Tensor lib_t = lib.t().contiguous();
+    Tensor best = empty({c.f.pop}, at::kInt, c.f.dev), dist = empty({c.f.pop, K}, at::kDouble, c.f.dev);
+    Tensor cnst = empty({c.f.pop}, at::kFloat, c.f.dev), const_dist = empty({c.f.pop}, at::kDouble, c.f.dev);
+    Tensor counts = empty({c.f.pop, 3}, at::kInt, c.f.dev), status = empty({c.f.pop}, at::kInt, c.f.dev);
+    check_rc(evogp_hip_sr_agx_match((unsigned)c.f.pop, (unsigned)c.D, (unsigned)c.f.gp_len, (unsigned)c.var_len, 1u, c.f.value, c.f.type, c.f.size,
+                                    variables.data_ptr<float>(), (unsigned)m.pop, m.value, m.type, m.size, mate.data_ptr<int>(),
+                                    pos.data_ptr<int>(), (unsigned)K, lib_t.data_ptr<float>(), dist.data_ptr<double>(), best.data_ptr<int>(),
+                                    cnst.data_ptr<float>(), const_dist.data_ptr<double>(), counts.data_ptr<int>(), status.data_ptr<int>(),
+                                    current_stream(c.f.dev)),
+             "tree_SR_agx_match");
     return {best, dist, cnst, const_dist, counts, status};
 }
 
@@ -1348,6 +1407,10 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_SR_desired(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor pos) -> (Tensor desired, Tensor state, Tensor status)");
     m.def("tree_SR_backprop_match(Tensor value, Tensor node_type, Tensor subtree_size, Tensor X, Tensor y, Tensor pos, Tensor lib)"
           " -> (Tensor best, Tensor dist, Tensor const, Tensor const_dist, Tensor counts, Tensor status)");
+    m.def("tree_SR_desired_mid(Tensor value, Tensor node_type, Tensor subtree_size, Tensor mate_value, Tensor mate_type, Tensor mate_size, Tensor X,"
+          " Tensor pos, Tensor mate) -> (Tensor desired, Tensor state, Tensor status)");
+    m.def("tree_SR_agx_match(Tensor value, Tensor node_type, Tensor subtree_size, Tensor mate_value, Tensor mate_type, Tensor mate_size, Tensor X,"
+          " Tensor pos, Tensor mate, Tensor lib) -> (Tensor best, Tensor dist, Tensor const, Tensor const_dist, Tensor counts, Tensor status)");
     m.def("tree_dimensions(Tensor value, Tensor node_type, Tensor subtree_size, Tensor var_units, Tensor label_units, bool check_root) -> (Tensor units, Tensor flags, Tensor violations)");
     m.def("tree_structure(Tensor value, Tensor node_type, Tensor subtree_size, Tensor cost, Tensor operand_limit, Tensor rule_outer, Tensor rule_inner, Tensor rule_limit, int max_depth, int max_complexity)"
           " -> (Tensor complexity, Tensor height, Tensor depth, Tensor nest, Tensor flags, Tensor violations)");
@@ -1402,6 +1465,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_derivative_loss", &tree_SR_derivative_loss);
     m.impl("tree_SR_desired", &tree_SR_desired);
     m.impl("tree_SR_backprop_match", &tree_SR_backprop_match);
+    m.impl("tree_SR_desired_mid", &tree_SR_desired_mid);
+    m.impl("tree_SR_agx_match", &tree_SR_agx_match);
     m.impl("tree_dimensions", &tree_dimensions);
     m.impl("tree_structure", &tree_structure);
 }

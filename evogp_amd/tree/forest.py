@@ -22,6 +22,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
     input gradients       SR_input_gradients, SR_derivative_loss: d tree / d x on the data rows; the derivative loss and violations
     backpropagation       SR_desired_semantics, SR_backprop_match: the values a subtree would have to return; the nearest library member
+    midpoint              SR_midpoint_semantics, SR_midpoint_match: the same towards the midpoint of a tree and its mate (no labels)
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
     genetic operators     mutate, crossover
@@ -830,16 +831,71 @@ class Forest:
         ``const_dist`` (pop,) float64 the best constant (the mean of the desired values) and its distance; ``counts`` (pop, 3) int32
         the REQUIRED, FREE and IMPOSSIBLE rows.  ``ValueError`` as for ``SR_desired_semantics``, and for a library of another shape."""
         inputs, labels, positions = self._backprop_args("SR_backprop_match", inputs, labels, positions)
+        library = self._library_semantics("SR_backprop_match", library, inputs)
+        return torch.ops.evogp_hip.tree_SR_backprop_match(*self._tensors(), inputs, labels, positions, library)
+
+    def _library_semantics(self, what: str, library, inputs: Tensor) -> Tensor:
+        """the (K, D) float32 semantics a match op takes, from a tensor or from a library Forest"""
         if isinstance(library, Forest):
             if library.input_len != self.input_len or library.output_len != 1:
-                raise ValueError(f"SR_backprop_match: the library forest should have {self.input_len} inputs and one output, but has "
+                raise ValueError(f"{what}: the library forest should have {self.input_len} inputs and one output, but has "
                                  f"{library.input_len} and {library.output_len}")
             library = library.batch_forward(inputs)[:, :, 0]
         library = check_tensor(library, self.batch_node_value.device)
         if library.dim() != 2 or library.shape[1] != inputs.shape[0] or not 1 <= library.shape[0] <= BACKPROP_MAX_LIBRARY:
-            raise ValueError(f"SR_backprop_match: library should have shape (K, {inputs.shape[0]}) with 1 <= K <= {BACKPROP_MAX_LIBRARY}, "
+            raise ValueError(f"{what}: library should have shape (K, {inputs.shape[0]}) with 1 <= K <= {BACKPROP_MAX_LIBRARY}, "
                              f"but got {tuple(library.shape)}")
-        return torch.ops.evogp_hip.tree_SR_backprop_match(*self._tensors(), inputs, labels, positions, library.contiguous().to(torch.float32))
+        return library.contiguous().to(torch.float32)
+
+    # ---- approximately geometric semantic crossover: the target is the midpoint of two parents ----
+    def _midpoint_args(self, what: str, inputs: Tensor, positions: Tensor, mates, mate_index):
+        """the datapoints, the positions, the mates and the mate index as the two ops take them; the RANGE of ``mate_index`` is the
+        kernel's to report (status 4, no host synchronisation)"""
+        self._single_output(what, ValueError)
+        if not isinstance(mates, Forest) or mates.output_len != 1:
+            raise ValueError(f"{what}: mates should be a single-output Forest")
+        if mates.input_len != self.input_len or mates.max_tree_len != self.max_tree_len:
+            raise ValueError(f"{what}: mates should have input_len {self.input_len} and max_tree_len {self.max_tree_len}, but have "
+                             f"{mates.input_len} and {mates.max_tree_len}")
+        dev = self.batch_node_value.device
+        inputs = check_tensor(inputs, dev)
+        assert inputs.dim() == 2 and inputs.shape[1] == self.input_len, f"inputs shape should be (datapoints, {self.input_len}), but got {tuple(inputs.shape)}"
+        positions = check_tensor(positions, dev)
+        if tuple(positions.shape) != (self.pop_size,):
+            raise ValueError(f"{what}: positions should have shape ({self.pop_size},), but got {tuple(positions.shape)}")
+        if positions.dtype.is_floating_point or positions.dtype == torch.bool:
+            raise ValueError(f"{what}: positions should be integers, but got {positions.dtype}")
+        if mate_index is None:
+            if mates.pop_size != self.pop_size:
+                raise ValueError(f"{what}: without a mate_index the mates should have {self.pop_size} trees, but have {mates.pop_size}")
+            mate_index = torch.arange(self.pop_size, dtype=torch.int32, device=dev)
+        else:
+            mate_index = check_tensor(mate_index, dev)
+            if tuple(mate_index.shape) != (self.pop_size,) or mate_index.dtype.is_floating_point or mate_index.dtype == torch.bool:
+                raise ValueError(f"{what}: mate_index should be ({self.pop_size},) integers, but got {tuple(mate_index.shape)} {mate_index.dtype}")
+        return (inputs.contiguous().to(torch.float32), positions.contiguous().to(torch.int32), mates._tensors(),
+                mate_index.contiguous().to(torch.int32))
+
+    def SR_midpoint_semantics(self, inputs: Tensor, positions: Tensor, mates: "Forest", mate_index: Optional[Tensor] = None):
+        """``(desired, state, status)`` as ``SR_desired_semantics``, with the labels replaced by a MATE (approximately geometric semantic
+        crossover, Pawlak, Wieloch & Krawiec 2015; csrc/sr_backprop.hip; one HIP pass, no host synchronisation, no
+        labels).  Tree t is paired with tree ``mate_index[t]`` of ``mates`` -- a single-output Forest of the same ``input_len`` and
+        ``max_tree_len``; ``None``: with tree t, and then ``mates.pop_size == pop_size``.  On row d the root target is the midpoint
+        ``0.5 * T_t(x_d) + 0.5 * T_mate(x_d)`` in float32: REQUIRED where it is finite, IMPOSSIBLE at every position where it is not.
+        So at ``positions[t] == 0`` the desired values are the midpoints.  ``status`` gains 4: the mate index is outside the mates, or
+        the mate's row is malformed (decided after 1 and 2, before 3).  ``ValueError`` for a multi-output forest on either side, another
+        ``input_len`` or ``max_tree_len``, ``positions`` or ``mate_index`` that is not (pop,) integers."""
+        inputs, positions, mate_rows, mate_index = self._midpoint_args("SR_midpoint_semantics", inputs, positions, mates, mate_index)
+        return torch.ops.evogp_hip.tree_SR_desired_mid(*self._tensors(), *mate_rows, inputs, positions, mate_index)
+
+    def SR_midpoint_match(self, inputs: Tensor, positions: Tensor, mates: "Forest", library, mate_index: Optional[Tensor] = None):
+        """``(best, dist, const, const_dist, counts, status)`` as ``SR_backprop_match``, for the desired values of
+        ``SR_midpoint_semantics``: the library member nearest to what the subtree at ``positions[t]`` would have to return for tree t
+        to land on the midpoint between itself and its mate.  Same HIP pass, no (pop, D) array, no host synchronisation.
+        ``ValueError`` as for ``SR_midpoint_semantics``, and for a bad library as in ``SR_backprop_match``."""
+        inputs, positions, mate_rows, mate_index = self._midpoint_args("SR_midpoint_match", inputs, positions, mates, mate_index)
+        library = self._library_semantics("SR_midpoint_match", library, inputs)
+        return torch.ops.evogp_hip.tree_SR_agx_match(*self._tensors(), *mate_rows, inputs, positions, mate_index, library)
 
     # ---- dimensional analysis --------------------------------------------------------------------
     def SR_dimensions(self, input_units, label_units=None):

@@ -855,6 +855,25 @@ int evogp_hip_sr_backprop_match(unsigned pop_size, unsigned data_points, unsigne
                                 const int *pos, unsigned n_lib, const float *lib_t /* [D][n_lib] */, double *dist /* [pop][n_lib] */,
                                 int *best, float *cnst, double *const_dist, int *counts /* [pop][3] */, int *status, evogp_stream_t stream);
 
+/* Approximately geometric semantic crossover (AGX, the second operator of the same paper; tests/agx_ref.py restates
+ * it): the two entries above with the labels replaced by a MATE.  The mates are a second forest of n_mates rows of the same gp_len and
+ * var_len, one output; mate i32[pop] names the mate's row of every tree.  With a = T_t(x_d) and b = T_mate[t](x_d) as
+ * evogp_hip_sr_gradient's forward walk computes them, the root target on row d is mid = 0.5f * a + 0.5f * b (two scalings and one float32
+ * addition): (mid, REQUIRED) where mid is finite, IMPOSSIBLE from the root down where it is not (a NaN or an infinity in either parent,
+ * inf - inf).  From there the rule table of section 3.24 applies unchanged, so at pos = 0 the desired values are the midpoints.  status
+ * gains 4: mate[t] is outside [0, n_mates), or the mate's row is malformed; the codes are decided in the order 1, 2, 4, 3.  No mate size
+ * word but the root's is read.  The outputs, the library, the order of summation and the order of the argument checks are those of the
+ * two entries above; n_mates == 0 is EVOGP_E_BADARG.  One launch each, no (pop, D) array, no float atomics, no host synchronisation. */
+int evogp_hip_sr_desired_mid(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len, const float *value,
+                             const int16_t *type, const int16_t *size, const float *variables, unsigned n_mates, const float *mvalue,
+                             const int16_t *mtype, const int16_t *msize, const int *mate /* [pop] */, const int *pos,
+                             float *desired /* [pop][D] */, unsigned char *state /* [pop][D] */, int *status /* [pop] */, evogp_stream_t stream);
+int evogp_hip_sr_agx_match(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len, const float *value,
+                           const int16_t *type, const int16_t *size, const float *variables, unsigned n_mates, const float *mvalue,
+                           const int16_t *mtype, const int16_t *msize, const int *mate /* [pop] */, const int *pos, unsigned n_lib,
+                           const float *lib_t /* [D][n_lib] */, double *dist /* [pop][n_lib] */, int *best, float *cnst, double *const_dist,
+                           int *counts /* [pop][3] */, int *status, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -937,7 +956,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
