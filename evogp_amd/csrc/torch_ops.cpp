@@ -1024,6 +1024,31 @@ Tensor tree_batch_argmax_count(int64_t pop_size, int64_t data_points, int64_t gp
     return counts;
 }
 
+// (hits int32[pop][G][C], predicted int32[pop][G][C], loss float64[pop][G]) of a multi-output forest over up to 8 row splits
+// (evogp_hip_batch_class_stats); groups: int32[D] or None (every row in split 0, n_groups = 1)
+Tensor3 tree_batch_class_stats(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                               const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &labels,
+                               const c10::optional<Tensor> &groups, int64_t n_groups) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    TORCH_CHECK(data_points > 0 && var_len > 0, "data_points and var_len must be larger than 0");
+    TORCH_CHECK(out_len >= 2 && out_len <= 16, "out_len must be in [2, 16], but got ", out_len);
+    TORCH_CHECK(n_groups >= 1 && n_groups <= 8, "n_groups must be in [1, 8], but got ", n_groups);
+    check_tensor(variables, {data_points, var_len}, "variables", f.dev, at::kFloat);
+    check_tensor(labels, {data_points}, "labels", f.dev, at::kInt);
+    const bool split = groups.has_value() && groups->defined();
+    if (split) check_tensor(*groups, {data_points}, "groups", f.dev, at::kInt);
+    else TORCH_CHECK(n_groups == 1, "n_groups must be 1 without groups, but got ", n_groups);
+    c10::DeviceGuard guard(f.dev);
+    Tensor hits = empty({pop_size, n_groups, out_len}, at::kInt, f.dev), predicted = empty({pop_size, n_groups, out_len}, at::kInt, f.dev);
+    Tensor loss = empty({pop_size, n_groups}, at::kDouble, f.dev);
+    check_rc(evogp_hip_batch_class_stats((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value,
+                                         f.type, f.size, variables.data_ptr<float>(), labels.data_ptr<int>(),
+                                         split ? groups->data_ptr<int>() : nullptr, (unsigned)n_groups, hits.data_ptr<int>(),
+                                         predicted.data_ptr<int>(), loss.data_ptr<double>(), current_stream(f.dev)),
+             "tree_batch_class_stats");
+    return {hits, predicted, loss};
+}
+
 // the operation lists of a multi-output forest (evaluate_prepared.hip): -> (workspace uint8[bytes], info int32[16]; info[0] = trees
 // the lists cannot express, which tree_evaluate_prepared then has to send through the stack interpreter)
 std::tuple<Tensor, Tensor> tree_evaluate_prepare(int64_t pop_size, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
@@ -1328,6 +1353,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor variables) -> Tensor results");
     m.def("tree_batch_argmax_count(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor variables, Tensor labels) -> Tensor counts");
+    m.def("tree_batch_class_stats(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor variables, Tensor labels, Tensor? groups, int n_groups) -> (Tensor hits, Tensor predicted, Tensor loss)");
     m.def("tree_evaluate_prepare(int pop_size, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type, Tensor subtree_size)"
           " -> (Tensor workspace, Tensor info)");
     m.def("tree_evaluate_prepared(int pop_size, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type, Tensor subtree_size,"
@@ -1423,6 +1450,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_generate_masked", &tree_generate_masked);
     m.impl("tree_batch_evaluate", &tree_batch_evaluate);
     m.impl("tree_batch_argmax_count", &tree_batch_argmax_count);
+    m.impl("tree_batch_class_stats", &tree_batch_class_stats);
     m.impl("tree_evaluate_prepare", &tree_evaluate_prepare);
     m.impl("tree_evaluate_prepared", &tree_evaluate_prepared);
     m.impl("breed_default", &breed_default);

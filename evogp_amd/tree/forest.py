@@ -212,6 +212,57 @@ class Forest:
             f"x shape[1] should be {self.input_len}, but got {tuple(x.shape)}")
         return torch.ops.evogp_hip.tree_batch_evaluate(*self._shape(x), *self._tensors(), x.contiguous().to(torch.float32))
 
+    def class_stats(self, inputs: Tensor, labels: Tensor, groups: Optional[Tensor] = None, n_groups: Optional[int] = None):
+        """``(hits, predicted, loss)`` of a classifier forest (one output per class) in one interpretation (csrc/cls_stats.hip), over up
+        to 8 row splits at once: ``hits[t, g, c]`` int32, the rows of split g with label c that tree t predicts as c; ``predicted[t, g,
+        c]`` int32, the rows of split g it predicts as c; ``loss[t, g]`` float64, its mean soft-max cross-entropy over split g (every
+        row's loss clamped to ``-log(1e-15)`` as the reference clips the probabilities).  The prediction is ``Classification``'s:
+        ``argmax(clip(softmax(outputs)))``.  The ``(pop, D, classes)`` outputs are never stored, nothing synchronises with the host,
+        and the result is bit-identical from run to run.
+
+        ``labels``: ``(D,)`` int, or float holding integers (checked here, one host sync; pass int labels to avoid it).  ``groups``:
+        None (every row in split 0), a ``(D,)`` bool (``False`` -> 0, ``True`` -> 1) or a ``(D,)`` int tensor with ``n_groups`` splits
+        (default 2 for bool; required for int, at most 8).  A row whose group lies outside ``[0, n_groups)`` or whose label lies outside
+        ``[0, output_len)`` is looked at in no output: a tree may be NaN there.  A row WITH a split where an output is NaN or the largest
+        output is infinite makes ``loss[t, g]`` of that split NaN; an empty split gives NaN; a malformed tree predicts class 0 with loss
+        NaN.  ``ValueError`` for a single-output forest, more than 16 outputs, a shape or a dtype."""
+        dev = self.batch_node_value.device
+        if not 2 <= self.output_len <= 16:
+            raise ValueError(f"class_stats works on forests with 2 to 16 outputs (one per class), but output_len is {self.output_len}")
+        inputs, labels = check_tensor(inputs, dev), check_tensor(labels, dev)
+        n = inputs.shape[0]
+        if inputs.dim() != 2 or inputs.shape != (n, self.input_len) or n == 0:
+            raise ValueError(f"inputs shape should be (D, {self.input_len}) with D > 0, but got {tuple(inputs.shape)}")
+        if labels.shape != (n,):
+            raise ValueError(f"labels shape should be ({n},), but got {tuple(labels.shape)}")
+        if labels.dtype == torch.bool or labels.is_complex():
+            raise ValueError(f"labels should be an int tensor or a float tensor of integers, but got {labels.dtype}")
+        if labels.is_floating_point():
+            if not bool(torch.all(labels == torch.round(labels))):
+                raise ValueError("labels should hold integers: a label like 1.5 names no class")
+            labels = labels.clamp(-1.0, float(self.output_len))   # (out of range stays out of range, whatever the cast does beyond int32)
+        else:
+            labels = labels.clamp(-1, self.output_len)
+        if groups is None:
+            if n_groups not in (None, 1):
+                raise ValueError(f"n_groups should be 1 (or None) without groups, but got {n_groups}")
+            n_groups = 1
+        else:
+            groups = check_tensor(groups, dev)
+            if groups.shape != (n,) or groups.is_floating_point() or groups.is_complex():
+                raise ValueError(f"groups should be a ({n},) bool or int tensor, but got {groups.dtype}{tuple(groups.shape)}")
+            if groups.dtype == torch.bool:
+                n_groups = 2 if n_groups is None else n_groups
+            elif n_groups is None:
+                raise ValueError("n_groups is required with int groups")
+            else:
+                groups = groups.clamp(-1, 8)
+            if not 1 <= int(n_groups) <= 8:
+                raise ValueError(f"n_groups should be in [1, 8], but got {n_groups}")
+            groups = groups.to(torch.int32).contiguous()
+        return tuple(torch.ops.evogp_hip.tree_batch_class_stats(*self._shape(inputs), *self._tensors(), inputs.contiguous().to(torch.float32),
+                                                                labels.to(torch.int32).contiguous(), groups, int(n_groups)))
+
     def _sr_data(self, inputs: Tensor, labels: Tensor):
         """the dataset as the kernels take it: on the forest's device, shapes checked, contiguous float32"""
         inputs, labels = check_tensor(inputs, self.batch_node_value.device), check_tensor(labels, self.batch_node_value.device)

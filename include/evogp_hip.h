@@ -581,6 +581,31 @@ int evogp_hip_batch_argmax_count(unsigned pop_size, unsigned data_points, unsign
                                  const float *variables, const int *labels, unsigned *counts,
                                  evogp_stream_t stream);
 
+/* Classification statistics and the soft-max cross-entropy of a multi-output forest in one interpretation (csrc/cls_stats.hip): for
+ * every tree t, every row split g < n_groups (1 <= n_groups <= 8, else EVOGP_E_BADARG) and every class c < out_len (2 <= out_len <= 16)
+ *   hits[t][g][c]      i32  rows of split g with label c that tree t predicts as c
+ *   predicted[t][g][c] i32  rows of split g that tree t predicts as c
+ *   loss[t][g]         f64  mean soft-max cross-entropy of tree t over the counted rows of split g
+ * Rows: groups is i32[data_points] or NULL (every row in split 0).  Row d belongs to split groups[d] when 0 <= groups[d] < n_groups and is
+ * COUNTED when besides 0 <= labels[d] < out_len; a row that is not counted is looked at in no output (a tree may be NaN there).
+ * Prediction: the rule of evogp_hip_batch_argmax_count -- first maximum, index 0 when an output is NaN or the maximum is infinite,
+ * near-ties as torch.argmax(clip(softmax(.))) settles them -- so the sum of hits[t] equals its counts[t] when every row is counted.
+ * Cross-entropy of a counted row with float32 outputs x_o and label y, in float32: m = max_o x_o; a NaN output or an infinite m POISONS
+ * the row: loss[t][g] of its split, and only of its split, is NaN; otherwise s = sum_o expf(x_o - m) with o ascending and
+ * l = logf(s) - (x_y - m) clamped to [0, 34.538776] (= -log(1e-15)).  loss[t][g] = (sum of l in float64) / (number of counted rows of g
+ * = sum_c predicted[t][g][c]); an empty split gives NaN.  A malformed tree has every output NaN: class 0 on every counted row, loss NaN.
+ * Sums: the counts by integer atomics; the float64 sums without atomics -- a lane's rows ascending, the 64 lanes by the fixed wave
+ * reduction, the row tiles in tile order -- and every l enters as a part on the 2^-20 grid plus its remainder, so that both column sums are
+ * exact for data_points < 2^26: the loss is bit-identical from run to run, independent of the population around the tree, and a split's
+ * column equals that of a call on the split's rows alone.  No (pop, data_points, out_len) array is written, nothing synchronises with the
+ * host; the partial sums (16 bytes per tree, tile of 64 or 128 rows and split, the population in slices of at most 128 MiB) live in the
+ * stream's workspace (evogp_hip_release_workspaces), so a call of a new shape cannot be captured into a graph before one eager call.
+ * The outputs must not alias the inputs or one another.  Errors as evogp_hip_batch_argmax_count: BADARG, NULLPTR, UNSUPPORTED. */
+int evogp_hip_batch_class_stats(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                const int *labels, const int *groups /* may be NULL */, unsigned n_groups, int *hits, int *predicted,
+                                double *loss, evogp_stream_t stream);
+
 /* Prepared forward pass of a MULTI-OUTPUT population (no counterpart in the reference's ABI).  The
  * reference's rollout problems call `evaluate` once per environment step on the same forest, 1000 times per generation
  * (src/evogp/problem/brax_problem.py:54-93).  In multi-output mode only nodes flagged OUT are observable and their operands
