@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 
 from ..tree import Forest
-from .semantic_library import SemanticLibrary
+from .semantic_library import LibraryRefresh, SemanticLibrary
 
 
 class BaseCrossover:
@@ -113,7 +113,7 @@ class CombinedDefaultCrossover(BaseCrossover):
 
 
 # ---- approximately geometric semantic crossover (no counterpart in the reference) ------------------------------------------------------
-class ApproxGeometricCrossover(BaseCrossover):
+class ApproxGeometricCrossover(LibraryRefresh, BaseCrossover):
     """The approximately geometric semantic crossover (AGX) of Pawlak, Wieloch & Krawiec (IEEE TEVC 2015), next to their Random Desired
     Operator (``SemanticBackpropMutation``): the recipient is inverted from its root down to a random node towards the MIDPOINT of its
     own and its mate's predictions on ``datapoints`` (``Forest.SR_midpoint_match``, csrc/sr_backprop.hip), and the
@@ -122,15 +122,17 @@ class ApproxGeometricCrossover(BaseCrossover):
     parents in semantic space.  It needs no labels.
 
     ``library``, ``descriptor``, ``library_size``: as for ``SemanticBackpropMutation``; a ``SemanticLibrary`` may be shared with it,
-    and ``update_library`` on either then reaches both.  Pairs and the recipient's position are drawn as ``DefaultCrossover.draw`` draws
+    and ``update_library`` on either then reaches both; ``refresh_every``, ``refresh_max_size``: the periodic rebuild from the subtrees of
+    the forest handed to the call (``LibraryRefresh``; with a shared library set it on one operator only).  Pairs and the recipient's position are drawn as ``DefaultCrossover.draw`` draws
     them (the donor position is unused); a pair of one tree with itself is not excluded: its midpoint is the tree's own predictions, so
     the subtree is replaced by the library member nearest to what it already computes.  An offspring without a match (``best == -1``:
     a function on the path has no inverse, no row is REQUIRED, or no library member is finite there) takes the offspring of the same
     index from ``fallback`` -- any ``BaseCrossover``, called once with the same arguments -- or is a copy of its recipient.  No host
-    synchronisation of its own."""
+    synchronisation of its own (a rebuild of the library has two)."""
 
     def __init__(self, datapoints: torch.Tensor, library=None, descriptor=None, library_size: int = 256, allow_constant: bool = True,
-                 fallback: BaseCrossover = None):
+                 fallback: BaseCrossover = None, refresh_every: int = 0, refresh_max_size=None):
+        self._init_refresh(refresh_every, refresh_max_size)
         if not isinstance(datapoints, torch.Tensor) or datapoints.dim() != 2 or datapoints.shape[0] == 0:
             raise ValueError(f"datapoints should be a (D, input_len) tensor, but got {tuple(getattr(datapoints, 'shape', ()))}")
         if fallback is not None and not isinstance(fallback, BaseCrossover):
@@ -148,16 +150,12 @@ class ApproxGeometricCrossover(BaseCrossover):
     def semantics(self) -> torch.Tensor:
         return self.semantic_library.semantics
 
-    def update_library(self, forest: Forest) -> None:
-        """the library becomes the semantically distinct members of ``forest`` on the datapoints (``SemanticLibrary.update_library``);
-        a shared library changes for every operator that holds it.  One host synchronisation."""
-        self.semantic_library.update_library(forest)
-
     def draw(self, tree_sizes: torch.Tensor, n_parents: int, target_cnt: int, device):
         """the draws of ``DefaultCrossover``: pairs and positions; the donor position is drawn and not used"""
         return DefaultCrossover().draw(tree_sizes, n_parents, target_cnt, device)
 
     def __call__(self, forest: Forest, survivor_indices: torch.Tensor, target_cnt: int, fitness: torch.Tensor):
+        self._refresh(forest)
         parents = forest[survivor_indices]
         sizes = parents.batch_subtree_size[:, 0]
         left, right, left_pos, _ = self.draw(sizes, len(parents), target_cnt, sizes.device)

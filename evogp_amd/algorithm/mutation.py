@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from ..tree import MAX_STACK, Forest, GenerateDescriptor, NType
-from .semantic_library import SemanticLibrary
+from .semantic_library import LibraryRefresh, SemanticLibrary
 
 
 class BaseMutation:
@@ -81,7 +81,7 @@ class DefaultMutation(BaseMutation):
 
 
 # ---- semantic backpropagation (no counterpart in the reference) --------------------------------------------------------------------
-class SemanticBackpropMutation(BaseMutation):
+class SemanticBackpropMutation(LibraryRefresh, BaseMutation):
     """The Random Desired Operator of Pawlak, Wieloch & Krawiec (IEEE TEVC 2015): a mutating tree is inverted from its root down to a
     random node on the rows of the dataset (``Forest.SR_backprop_match``, csrc/sr_backprop.hip), which gives the values
     the subtree at that node would have to return for the tree to hit the labels, and the subtree is replaced by the member of a LIBRARY
@@ -91,7 +91,9 @@ class SemanticBackpropMutation(BaseMutation):
     ``library``: a single-output Forest (at most 1024 trees), or a ``SemanticLibrary`` (semantic_library.py) shared with other operators,
     ``ApproxGeometricCrossover`` among them.  Without one it is built from ``descriptor``: the one-node tree of every variable and ``library_size`` random trees, reduced to one member per semantics (``semantic_unique(datapoints, keep="smallest")``)
     and truncated to 1024; its semantics are computed once.  ``update_library(forest)`` replaces it by the semantically distinct members
-    of a forest, e.g. of the population.  A library narrower than the forest is padded to the forest's ``max_tree_len``; a wider one
+    of a forest, e.g. of the population, ``update_library(forest, source="subtrees")`` by its distinct SUBTREES, and ``refresh_every=n``
+    does the latter on every n-th call from the forest being mutated, with subtrees of at most ``refresh_max_size`` nodes
+    (``LibraryRefresh``; with a shared library set it on one operator only).  A library narrower than the forest is padded to the forest's ``max_tree_len``; a wider one
     is a ``ValueError`` at the call.
 
     The mutating trees and their positions are drawn as ``DefaultMutation`` draws them.  A mutating tree without a match (``best ==
@@ -104,7 +106,8 @@ class SemanticBackpropMutation(BaseMutation):
 
     def __init__(self, mutation_rate: float, datapoints: torch.Tensor, labels: torch.Tensor, library=None,
                  descriptor: Optional[GenerateDescriptor] = None, library_size: int = 256, allow_constant: bool = True,
-                 fallback: Optional[BaseMutation] = None):
+                 fallback: Optional[BaseMutation] = None, refresh_every: int = 0, refresh_max_size: Optional[int] = None):
+        self._init_refresh(refresh_every, refresh_max_size)
         if datapoints.dim() != 2 or labels.shape[0] != datapoints.shape[0] or labels.numel() != datapoints.shape[0]:
             raise ValueError(f"datapoints should be (D, input_len) and labels (D,) or (D, 1), but got {tuple(datapoints.shape)} and {tuple(labels.shape)}")
         if fallback is not None and not isinstance(fallback, BaseMutation):
@@ -124,12 +127,8 @@ class SemanticBackpropMutation(BaseMutation):
     def semantics(self) -> torch.Tensor:
         return self.semantic_library.semantics
 
-    def update_library(self, forest: Forest) -> None:
-        """the library becomes the semantically distinct members of ``forest`` on the datapoints (``SemanticLibrary.update_library``);
-        a shared library changes for every operator that holds it.  One host synchronisation."""
-        self.semantic_library.update_library(forest)
-
     def __call__(self, forest: Forest, skip_rows: int = 0) -> Forest:
+        self._refresh(forest)
         dev = forest.batch_node_value.device
         mask = _keep_rows(torch.rand(forest.pop_size, device=dev) < self.mutation_rate, skip_rows)
         rows = torch.nonzero(mask).squeeze(1)   # (the one synchronisation)

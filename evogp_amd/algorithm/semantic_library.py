@@ -53,13 +53,28 @@ class SemanticLibrary:
             return library
         return cls(datapoints, library, descriptor, library_size, owner)
 
-    def update_library(self, forest: Forest) -> None:
+    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None) -> None:
         """the library becomes the semantically distinct members of ``forest`` on the datapoints (the smallest tree of every class, in
-        index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation."""
+        index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation.
+
+        ``source="subtrees"``: the members are drawn from the SUBTREES of ``forest`` instead -- the population-based library of the
+        paper.  ``forest.subtree_library(datapoints, 1024, min_size, max_size)`` names up to 1024 distinct subtrees of ``min_size`` to
+        ``max_size`` nodes, the most frequent first (csrc/sr_subtree_sig.hip; 64-bit signatures decide, nothing verifies them), and
+        these go through the reduction above, which computes the semantics from the extracted trees themselves.  A forest of trees
+        that are all too large to be donors still yields a library of their parts.  Two host synchronisations; ``ValueError`` when
+        no subtree is eligible.  ``min_size`` and ``max_size`` belong to ``source="subtrees"`` alone."""
         from ..tree.forest import BACKPROP_MAX_LIBRARY
 
         if not isinstance(forest, Forest) or forest.output_len != 1 or forest.input_len != self.datapoints.shape[1]:
             raise ValueError(f"the library should be a single-output Forest of {self.datapoints.shape[1]} inputs")
+        if source not in ("trees", "subtrees"):
+            raise ValueError(f"source should be 'trees' or 'subtrees', but got {source!r}")
+        if source == "subtrees":
+            forest = forest.subtree_library(self.datapoints, BACKPROP_MAX_LIBRARY, min_size, max_size)[0]
+            if forest.pop_size == 0:
+                raise ValueError(f"the forest has no well-formed subtree of {min_size} to {max_size} nodes to build a library from")
+        elif min_size != 1 or max_size is not None:
+            raise ValueError("min_size and max_size select subtrees: they need source='subtrees'")
         unique, _, _ = forest.semantic_unique(self.datapoints, keep="smallest")
         self.library = unique[:BACKPROP_MAX_LIBRARY] if unique.pop_size > BACKPROP_MAX_LIBRARY else unique
         self.semantics = self.library.batch_forward(self.datapoints)[:, :, 0].contiguous()
@@ -90,3 +105,32 @@ class SemanticLibrary:
             cv, ct, cs = leaf_rows(const, NType.CONST, max_tree_len)
             value, node_type, size = (torch.where(nearer[:, None], c, a) for c, a in ((cv, value), (ct, node_type), (cs, size)))
         return Forest(input_len, 1, value, node_type, size, func_mask=self.library.func_mask)
+
+
+class LibraryRefresh:
+    """what ``SemanticBackpropMutation`` and ``ApproxGeometricCrossover`` share around their ``semantic_library``: ``update_library`` and
+    the periodic rebuild from the population's subtrees.  ``refresh_every = n > 0``: every n-th call of the operator first rebuilds the
+    library from the subtrees of at most ``refresh_max_size`` nodes (None: any size) of the forest the operator was handed
+    (``update_library(forest, source="subtrees", max_size=refresh_max_size)``, which waits for the host twice); 0: never.  Operators that SHARE a ``SemanticLibrary``
+    should set it on one of them only: a rebuild by either reaches both, and two would do the work twice per generation."""
+
+    def _init_refresh(self, refresh_every, refresh_max_size) -> None:
+        if isinstance(refresh_every, bool) or not isinstance(refresh_every, int) or refresh_every < 0:
+            raise ValueError(f"refresh_every should be a non-negative integer, but got {refresh_every!r}")
+        if refresh_max_size is not None and (isinstance(refresh_max_size, bool) or not isinstance(refresh_max_size, int) or refresh_max_size < 1):
+            raise ValueError(f"refresh_max_size should be None or a positive integer, but got {refresh_max_size!r}")
+        self.refresh_every, self.refresh_max_size, self._refresh_calls = refresh_every, refresh_max_size, 0
+
+    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None) -> None:
+        """the library becomes the semantically distinct members of ``forest`` on the datapoints, or with ``source="subtrees"`` of its
+        subtrees of ``min_size`` to ``max_size`` nodes (``SemanticLibrary.update_library``); a shared library changes for every
+        operator that holds it.  One host synchronisation, two with ``source="subtrees"``."""
+        self.semantic_library.update_library(forest, source, min_size, max_size)
+
+    def _refresh(self, forest: Forest) -> None:
+        """called once per call of the operator, before it reads the library"""
+        if not self.refresh_every:
+            return
+        self._refresh_calls += 1
+        if self._refresh_calls % self.refresh_every == 0:
+            self.update_library(forest, source="subtrees", max_size=self.refresh_max_size)

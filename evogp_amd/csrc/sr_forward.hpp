@@ -1,4 +1,4 @@
-// sr_forward.hpp — what the tape kernels (sr_grad.hip, sr_lm.hip, sr_subtree.hip) share: the value of a node from its operands' values, the
+// sr_forward.hpp — what the tape kernels (sr_grad.hip, sr_lm.hip, sr_subtree.hip, sr_subtree_sig.hip) share: the value of a node from its operands' values, the
 // per-row error, the OPERAND TABLE wave 0 of a workgroup builds for its tree (for every function node the indices of the nodes
 // whose pushed values it pops) and, on the host, the LAUNCH PLAN of the three passes (plan_tape_launch).  The forward semantics are
 // run_general's (interp.hpp).
@@ -70,15 +70,18 @@ inline float *grad_workspace(hipStream_t stream, size_t bytes, int *rc) { return
 struct TapePlan {
     int W;          // waves per workgroup
     long blocks;    // workgroups (each takes trees blocks apart)
-    size_t lds;     // dynamic LDS of a workgroup in bytes: the kernel's head and, for rows of at most kTapeLdsLen nodes, its W x 2 tapes
-    float *tape;    // global tapes [blocks * W][2][gp_len][64] of longer rows; nullptr: the tapes are in LDS
+    size_t lds;     // dynamic LDS of a workgroup in bytes: the kernel's head and, for rows of at most kTapeLdsLen nodes, its W x tape_words tapes
+    float *tape;    // global tapes [blocks * W][tape_words][gp_len][64] of longer rows; nullptr: the tapes are in LDS
 };
 
 // The plan of one pass over `pop` rows of `gp_len` words and D data points on `stream`; head_words(L, W) is the kernel's own LDS in
 // front of the tapes (its layout stays next to the kernel that carves it).  Returns 0, or the error of the workspace request.
 // THE CONTRACT: W and blocks depend on nothing but (pop, D, gp_len) and the device, so the gradient, the normal-equation and the
 // subtree pass split the rows of a tree among the same waves and sum them in the same order: their losses are equal bit for bit.
-inline int plan_tape_launch(int pop, int D, int gp_len, hipStream_t stream, size_t (*head_words)(int L, int W), TapePlan *plan) {
+// tape_words: 32-bit words a wave keeps per node and lane (two float tapes in the three passes above, the value tape alone in
+// sr_subtree_sig.hip); it sizes the LDS and the global workspace and therefore `blocks` of an LDS-tape launch, never W.
+inline int plan_tape_launch(int pop, int D, int gp_len, hipStream_t stream, size_t (*head_words)(int L, int W), TapePlan *plan,
+                            int tape_words = 2) {
     const DeviceInfo &dev = device_info();
     const int ntiles = (D + kWave - 1) / kWave;
     const bool lds_tape = gp_len <= kTapeLdsLen;
@@ -88,7 +91,7 @@ inline int plan_tape_launch(int pop, int D, int gp_len, hipStream_t stream, size
     size_t lds = head_words(gp_len, W) * 4;
     long blocks;
     if (lds_tape) {
-        lds += (size_t)W * 2 * gp_len * kWave * sizeof(float);
+        lds += (size_t)W * tape_words * gp_len * kWave * sizeof(float);
         const long per_cu = (long)(dev.lds_per_cu / lds);
         blocks = (long)dev.num_cus * (per_cu < 1 ? 1 : per_cu);
     } else {
@@ -98,7 +101,7 @@ inline int plan_tape_launch(int pop, int D, int gp_len, hipStream_t stream, size
     *plan = {W, blocks, lds, nullptr};
     if (!lds_tape) {
         int rc = 0;
-        plan->tape = grad_workspace(stream, (size_t)blocks * W * 2 * gp_len * kWave * sizeof(float), &rc);
+        plan->tape = grad_workspace(stream, (size_t)blocks * W * tape_words * gp_len * kWave * sizeof(float), &rc);
         if (!plan->tape) return rc;
     }
     return 0;

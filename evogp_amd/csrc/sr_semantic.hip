@@ -25,6 +25,7 @@
 #include "dedup.hpp"
 #include "interp.hpp"
 #include "launch.hpp"
+#include "sem_key.hpp"
 #include "sr_params.hpp"
 
 namespace evogp {
@@ -46,16 +47,7 @@ struct SemParams {
     int pop, D, gp_len, var_len, batch, ntiles;
 };
 
-// the key of a prediction: -0.0 is +0.0, every NaN is the canonical quiet NaN
-__device__ inline uint32_t sem_key(float p) {
-    const uint32_t u = f2bits(p), mag = u & 0x7FFFFFFFu;
-    return mag == 0u ? 0u : (mag > 0x7F800000u ? 0x7FC00000u : u);
-}
-// the term of row d in a tree's sum
-__device__ inline unsigned long long sem_term(float p, unsigned long long d) {
-    return mix64((unsigned long long)sem_key(p) ^ ((d + 1ull) * kDedupGold));
-}
-__device__ inline unsigned long long sem_finish(unsigned long long sum, int D) { return mix64(sum + (unsigned long long)D); }
+// sem_key, sem_term and sem_finish (the key of a prediction, the term of a row, the last mix) are sem_key.hpp's
 
 // ---- 1. the register interpreter (sr_scale_kernel's decomposition) -----------------------------------------------------------------------
 template <int VL, bool LEAN>

@@ -938,6 +938,45 @@ Tensor tree_SR_semantic_classes(int64_t pop_size, int64_t data_points, int64_t g
     return class_id;
 }
 
+// int64[pop][gp_len]: the bits of the signature of every subtree's values on the rows of `variables`, 0 on tails and malformed rows
+// (evogp_hip_sr_subtree_signatures)
+Tensor tree_SR_subtree_signatures(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                                  const Tensor &type, const Tensor &size, const Tensor &variables) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    const float *X = check_semantic("tree_SR_subtree_signatures", f, data_points, var_len, out_len, variables);
+    c10::DeviceGuard guard(f.dev);
+    Tensor sig = empty({pop_size, gp_len}, at::kLong, f.dev);
+    check_rc(evogp_hip_sr_subtree_signatures((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len,
+                                             f.value, f.type, f.size, X, (unsigned long long *)sig.data_ptr<int64_t>(), current_stream(f.dev)),
+             "tree_SR_subtree_signatures");
+    return sig;
+}
+
+// (member int32[k], count int32[k], n_classes int32[1]): the k largest classes of equal signature among the eligible nodes, each by its
+// (size, flat index)-smallest member (evogp_hip_subtree_library_select); the workspace comes from torch's caching allocator
+Tensor3 subtree_library_select(const Tensor &sig, const Tensor &size, int64_t min_size, int64_t max_size, int64_t k) {
+    TORCH_CHECK(sig.is_cuda() && sig.is_contiguous() && sig.scalar_type() == at::kLong && sig.dim() == 2 && sig.numel() > 0,
+                "sig must be a non-empty contiguous int64 (pop_size, gp_len) CUDA tensor");
+    const int64_t pop = sig.size(0), gp_len = sig.size(1);
+    check_sizes(pop, gp_len);
+    TORCH_CHECK(pop * gp_len <= 0x7FFFFFFF, "sig must hold fewer than 2^31 words, but got shape ", sig.sizes());
+    const c10::Device dev = sig.device();
+    check_tensor(size, {pop, gp_len}, "size", dev, at::kShort);
+    TORCH_CHECK(min_size >= 1, "min_size must be at least 1, but got ", min_size);
+    TORCH_CHECK(max_size >= min_size && max_size <= 0x7FFFFFFF, "max_size must be in [min_size, 2^31), but got ", max_size, " with min_size ", min_size);
+    TORCH_CHECK(k >= 1 && k <= EVOGP_BACKPROP_MAX_LIB, "k must be in [1, ", EVOGP_BACKPROP_MAX_LIB, "], but got ", k);
+    c10::DeviceGuard guard(dev);
+    Tensor member = empty({k}, at::kInt, dev), count = empty({k}, at::kInt, dev), n_classes = empty({1}, at::kInt, dev);
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_subtree_library_select_workspace_bytes((unsigned)pop, (unsigned)gp_len, &bytes), "subtree_library_select");
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, dev);
+    check_rc(evogp_hip_subtree_library_select((unsigned)pop, (unsigned)gp_len, (const unsigned long long *)sig.data_ptr<int64_t>(),
+                                              size.data_ptr<int16_t>(), (int)min_size, (int)max_size, (int)k, member.data_ptr<int>(),
+                                              count.data_ptr<int>(), n_classes.data_ptr<int>(), ws.data_ptr(), current_stream(dev)),
+             "subtree_library_select");
+    return {member, count, n_classes};
+}
+
 // (front int32, crowding float32, order int32) of a population on (err, cx) (evogp_hip_pareto_rank); the workspace comes from torch's
 // caching allocator
 Tensor3 pareto_rank(const Tensor &err, const Tensor &cx, int64_t cx_bound) {
@@ -1410,6 +1449,9 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor variables) -> Tensor");
     m.def("tree_SR_semantic_classes(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor variables, Tensor hash) -> Tensor");
+    m.def("tree_SR_subtree_signatures(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor variables) -> Tensor");
+    m.def("subtree_library_select(Tensor sig, Tensor size, int min_size, int max_size, int k) -> (Tensor member, Tensor count, Tensor n_classes)");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
     m.def("tree_SR_weighted_loss(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
@@ -1479,6 +1521,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_classes", &tree_classes);
     m.impl("tree_SR_semantic_hash", &tree_SR_semantic_hash);
     m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
+    m.impl("tree_SR_subtree_signatures", &tree_SR_subtree_signatures);
+    m.impl("subtree_library_select", &subtree_library_select);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
     m.impl("tree_SR_weighted_scaling", &tree_SR_weighted_scaling);

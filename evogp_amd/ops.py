@@ -84,3 +84,21 @@ def tree_SR_semantic_classes(pop_size, data_points, gp_len, var_len, out_len, va
     compared and may be any tensor in which equal trees carry equal words (``tree_SR_semantic_hash``'s, normally)"""
     return torch.ops.evogp_hip.tree_SR_semantic_classes(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size,
                                                         variables, hash)
+
+
+def tree_SR_subtree_signatures(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables):
+    """int64 ``(pop, gp_len)``: ``torch.ops.evogp_hip.tree_SR_subtree_signatures`` (csrc/sr_subtree_sig.hip), ``tree_SR_semantic_hash``'s
+    signature of EVERY SUBTREE of every single-output tree: entry ``[t, i]`` is the word ``tree_SR_semantic_hash`` gives the row that
+    holds the nodes ``[i, i + size[t, i])`` alone (so column 0 is ``tree_SR_semantic_hash`` itself); 0 on the tail and on malformed rows"""
+    return torch.ops.evogp_hip.tree_SR_subtree_signatures(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size,
+                                                          variables)
+
+
+def subtree_library_select(sig, size, min_size, max_size, k):
+    """``(member, count, n_classes)``: ``torch.ops.evogp_hip.subtree_library_select`` (csrc/sr_subtree_sig.hip).  Among the nodes with
+    ``sig != 0`` and ``min_size <= size <= max_size`` (``sig`` int64, ``size`` int16, both ``(pop, gp_len)``), the classes of equal
+    signature ordered by (count descending, representative ascending), a class's representative being its member of smallest (size,
+    flat index).  ``member`` int32 ``(k,)``: the representatives' flat indices ``t * gp_len + i``, -1 past the last class; ``count`` int32
+    ``(k,)``: the class sizes, 0 there; ``n_classes`` int32 ``(1,)``.  ``1 <= k <= 1024``.  Signatures alone decide: a collision merges
+    two classes"""
+    return torch.ops.evogp_hip.subtree_library_select(sig, size, min_size, max_size, k)

@@ -14,6 +14,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     structural duplicates structure_hash, duplicate_classes, unique (csrc/dedup.hip); ``dedup=True`` elsewhere runs once per class
     semantic duplicates   semantic_hash, semantic_classes, semantic_unique: trees equal on every data row
     subtrees              SR_subtree_errors, simplify: the loss of every subtree; the smaller tree that is no worse
+    subtree library       SR_subtree_signatures, subtree_library: the signature of every subtree; the distinct subtrees of a forest
     linear scaling        SR_scaled_fitness, apply_scaling: the loss under the least-squares slope and intercept; the tree with them
     weighted losses       SR_weighted_loss: sample weights, Huber / pinball / log-cosh, training and validation columns in one pass
     weighted scaling      SR_weighted_scaled_fitness: linear scaling fitted on one weight row, scored on up to 8, in one pass
@@ -528,6 +529,50 @@ class Forest:
         index order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` predicting what tree t predicts on every row, and
         ``counts`` (int64) the number of trees per representative.  ONE host synchronisation."""
         return self._unique(*self.semantic_classes(inputs, keep))
+
+    # ---- subtree signatures and the population-built library ------------------------------------
+    def SR_subtree_signatures(self, inputs: Tensor) -> Tensor:
+        """(pop, max_tree_len) int64: ``semantic_hash``'s signature of EVERY SUBTREE on the rows of ``inputs`` ``(D, input_len)``.  Entry
+        ``[t, i]`` is the word ``semantic_hash`` gives the row that holds the nodes ``[i, i + size[t, i])`` alone, so column 0 is
+        ``semantic_hash(inputs)`` and two subtrees anywhere in the forest that take the same values on every row carry one word.  0 on
+        the tail of a row and on malformed trees.  One forward walk per tree (csrc/sr_subtree_sig.hip); deterministic, no host
+        synchronisation; single-output forests (``ValueError`` otherwise)."""
+        inputs = self._semantic_rows("SR_subtree_signatures", inputs)
+        return torch.ops.evogp_hip.tree_SR_subtree_signatures(*self._shape(inputs), *self._tensors(), inputs)
+
+    def subtree_library(self, inputs: Tensor, k: int = BACKPROP_MAX_LIBRARY, min_size: int = 1, max_size: Optional[int] = None):
+        """``(library, counts, tree, node)``: the semantically distinct subtrees of this forest on ``inputs``, the most frequent first.
+        The subtrees of ``min_size <= size <= max_size`` nodes (``max_size=None``: any) fall into classes of equal signature
+        (``SR_subtree_signatures``); a class is represented by its member of fewest nodes (ties: the smallest tree index, then node
+        index), and the classes are ordered by (members descending, representative ascending).  ``library`` is a Forest of the first
+        ``m = min(k, classes)`` representatives at this forest's ``max_tree_len``: row j holds the nodes ``[node[j], node[j] + size)`` of
+        tree ``tree[j]`` word for word from position 0, zeros behind them, and carries this forest's ``func_mask``.  ``counts`` (m,) int32:
+        the members per class; ``tree``, ``node`` (m,) int64.  Signatures alone decide a class: a collision of two 64-bit words merges two
+        semantics and costs one member, so compute the library's semantics from ``library`` itself.  ONE host synchronisation (to read
+        m); ``ValueError`` for a multi-output forest, ``k`` outside 1 .. 1024 or sizes with ``1 <= min_size <= max_size`` violated."""
+        inputs = self._semantic_rows("subtree_library", inputs)
+        L = self.max_tree_len
+        max_size = L if max_size is None else max_size
+        for name, v in (("k", k), ("min_size", min_size), ("max_size", max_size)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} should be an integer, but got {v!r}")
+        if not 1 <= k <= BACKPROP_MAX_LIBRARY:
+            raise ValueError(f"k should be in [1, {BACKPROP_MAX_LIBRARY}], but got {k}")
+        if min_size < 1 or max_size < min_size:
+            raise ValueError(f"sizes should satisfy 1 <= min_size <= max_size, but got min_size {min_size} and max_size {max_size}")
+        if self.pop_size * L >= 2 ** 31:
+            raise ValueError(f"subtree_library takes forests of fewer than 2^31 words, but got {self.pop_size} x {L}")
+        value, ntype, size = self._tensors()
+        sig = torch.ops.evogp_hip.tree_SR_subtree_signatures(*self._shape(inputs), value, ntype, size, inputs)
+        member, counts, n_classes = torch.ops.evogp_hip.subtree_library_select(sig, size, min_size, min(max_size, L), k)
+        m = min(k, int(n_classes.item()))   # (the host sync)
+        flat = member[:m].to(torch.int64)
+        tree, node = flat // L, flat % L
+        cols = torch.arange(L, device=value.device)[None, :]
+        live = cols < size[tree, node].to(torch.int64)[:, None]
+        src = (node[:, None] + cols).clamp(max=L - 1)
+        rows = tuple(torch.where(live, a[tree[:, None], src], torch.zeros((), dtype=a.dtype, device=a.device)) for a in (value, ntype, size))
+        return Forest(self.input_len, 1, *rows, func_mask=self.func_mask), counts[:m], tree, node
 
     def SR_subtree_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(node_err, node_const)``, both (pop, max_tree_len): ``node_err[t, i]`` is the loss the subtree rooted at node i of tree t

@@ -899,6 +899,43 @@ int evogp_hip_sr_agx_match(unsigned pop_size, unsigned data_points, unsigned gp_
                            const float *lib_t /* [D][n_lib] */, double *dist /* [pop][n_lib] */, int *best, float *cnst, double *const_dist,
                            int *counts /* [pop][3] */, int *status, evogp_stream_t stream);
 
+/* The semantic signature of EVERY SUBTREE, and a library of semantically distinct subtrees chosen from those signatures (the
+ * population-based library of the same paper; csrc/sr_subtree_sig.hip; tests/sublib_ref.py restates both).
+ * evogp_hip_sr_subtree_signatures, single-output forests only: with v_i the float32 value of the subtree rooted at node i as
+ * evogp_hip_sr_subtree_errors' forward walk computes it and sig() the signature of evogp_hip_sr_semantic_hash above (same key, same
+ * terms, same last mix),
+ *     sig_out[t][i] = sig of the row of values v_i(X[0]), ..., v_i(X[D - 1])        for i < len(t), tree t well formed
+ *     sig_out[t][i] = 0                    on the tail [len, gp_len) and on every entry of a malformed tree
+ * so sig_out[t][0] is evogp_hip_sr_semantic_hash's word of tree t and sig_out[t][i] is its word for the row that holds the nodes
+ * [i, i + size[t][i]) from position 0, bit for bit.  One launch with the plan of the tape passes (a workgroup per tree, its waves split
+ * the 64-row tiles); the per-node sum is integer and modular, so no order of lanes, tiles or waves changes it.  No atomics, no labels,
+ * nothing synchronises with the host.  Rows of more than 64 nodes use the per-stream tape buffer of evogp_hip_sr_gradient, under the same
+ * rules.  EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, out_len != 1; then a NULL pointer: EVOGP_E_NULLPTR.
+ *
+ * evogp_hip_subtree_library_select: sig u64[pop][gp_len] (the entry above, or any array in which equal words mean "the same"), size
+ * i16[pop][gp_len] (the forest's subtree sizes), 1 <= min_size <= max_size, 1 <= k <= EVOGP_BACKPROP_MAX_LIB, pop * gp_len < 2^31.
+ *     ELIGIBLE         the flat index f = t * gp_len + i with sig[f] != 0 and min_size <= size[f] <= max_size.  A live subtree whose
+ *                      signature happens to be exactly 0 is dropped (one word in 2^64).
+ *     CLASS            the eligible nodes of one signature; its COUNT is their number
+ *     REPRESENTATIVE   the member with the smallest (size, f)
+ *     ORDER            the classes by (count descending, representative's f ascending) -- a total order
+ *     member_out i32[k]   the representative's flat index of the j-th class in that order, -1 past the last class
+ *     count_out i32[k]    its count, 0 there
+ *     n_classes_out i32[1]   the number of classes (it may exceed k)
+ * The outputs are fully determined by the inputs: bit-identical from run to run.  Signatures CHOOSE the classes and nothing verifies
+ * them: a collision merges two semantics into one class and costs the library one member, never a wrong result -- whoever uses the
+ * library recomputes its semantics from the extracted trees.  Two stable sorts over the pop * gp_len words with 64-bit integer atomics
+ * (minimum) for the representatives; everything on the caller's stream, nothing synchronises with the host, the engine allocates nothing.
+ * workspace: evogp_hip_subtree_library_select_workspace_bytes(pop, gp_len) bytes, no zeroing needed.  EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024,
+ * pop * gp_len >= 2^31, min_size < 1, max_size < min_size, k outside 1 .. 1024; then a NULL pointer: EVOGP_E_NULLPTR. */
+int evogp_hip_sr_subtree_signatures(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                    const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                    unsigned long long *sig_out /* [pop][gp_len] */, evogp_stream_t stream);
+int evogp_hip_subtree_library_select_workspace_bytes(unsigned pop_size, unsigned gp_len, unsigned long long *bytes);
+int evogp_hip_subtree_library_select(unsigned pop_size, unsigned gp_len, const unsigned long long *sig, const int16_t *size, int min_size,
+                                     int max_size, int k, int *member_out /* [k] */, int *count_out /* [k] */, int *n_classes_out /* [1] */,
+                                     void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -981,7 +1018,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match, then evogp_hip_sr_subtree_signatures and evogp_hip_subtree_library_select with its _workspace_bytes were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
