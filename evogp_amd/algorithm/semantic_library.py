@@ -53,7 +53,8 @@ class SemanticLibrary:
             return library
         return cls(datapoints, library, descriptor, library_size, owner)
 
-    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None) -> None:
+    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None, *,
+                       sig: Optional[torch.Tensor] = None) -> None:
         """the library becomes the semantically distinct members of ``forest`` on the datapoints (the smallest tree of every class, in
         index order, at most 1024): a population-derived library when ``forest`` is the population.  One host synchronisation.
 
@@ -62,7 +63,9 @@ class SemanticLibrary:
         ``max_size`` nodes, the most frequent first (csrc/sr_subtree_sig.hip; 64-bit signatures decide, nothing verifies them), and
         these go through the reduction above, which computes the semantics from the extracted trees themselves.  A forest of trees
         that are all too large to be donors still yields a library of their parts.  Two host synchronisations; ``ValueError`` when
-        no subtree is eligible.  ``min_size`` and ``max_size`` belong to ``source="subtrees"`` alone."""
+        no subtree is eligible.  ``min_size`` and ``max_size`` belong to ``source="subtrees"`` alone, and so does ``sig``:
+        ``forest.SR_subtree_signatures(datapoints)`` from a caller that already has it (one signature pass per generation then serves
+        this and ``forest.remove_introns(datapoints, sig=sig)``); None computes it."""
         from ..tree.forest import BACKPROP_MAX_LIBRARY
 
         if not isinstance(forest, Forest) or forest.output_len != 1 or forest.input_len != self.datapoints.shape[1]:
@@ -70,11 +73,11 @@ class SemanticLibrary:
         if source not in ("trees", "subtrees"):
             raise ValueError(f"source should be 'trees' or 'subtrees', but got {source!r}")
         if source == "subtrees":
-            forest = forest.subtree_library(self.datapoints, BACKPROP_MAX_LIBRARY, min_size, max_size)[0]
+            forest = forest.subtree_library(self.datapoints, BACKPROP_MAX_LIBRARY, min_size, max_size, sig=sig)[0]
             if forest.pop_size == 0:
                 raise ValueError(f"the forest has no well-formed subtree of {min_size} to {max_size} nodes to build a library from")
-        elif min_size != 1 or max_size is not None:
-            raise ValueError("min_size and max_size select subtrees: they need source='subtrees'")
+        elif min_size != 1 or max_size is not None or sig is not None:
+            raise ValueError("min_size, max_size and sig select subtrees: they need source='subtrees'")
         unique, _, _ = forest.semantic_unique(self.datapoints, keep="smallest")
         self.library = unique[:BACKPROP_MAX_LIBRARY] if unique.pop_size > BACKPROP_MAX_LIBRARY else unique
         self.semantics = self.library.batch_forward(self.datapoints)[:, :, 0].contiguous()
@@ -121,11 +124,13 @@ class LibraryRefresh:
             raise ValueError(f"refresh_max_size should be None or a positive integer, but got {refresh_max_size!r}")
         self.refresh_every, self.refresh_max_size, self._refresh_calls = refresh_every, refresh_max_size, 0
 
-    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None) -> None:
+    def update_library(self, forest: Forest, source: str = "trees", min_size: int = 1, max_size: Optional[int] = None, *,
+                       sig: Optional[torch.Tensor] = None) -> None:
         """the library becomes the semantically distinct members of ``forest`` on the datapoints, or with ``source="subtrees"`` of its
         subtrees of ``min_size`` to ``max_size`` nodes (``SemanticLibrary.update_library``); a shared library changes for every
-        operator that holds it.  One host synchronisation, two with ``source="subtrees"``."""
-        self.semantic_library.update_library(forest, source, min_size, max_size)
+        operator that holds it.  One host synchronisation, two with ``source="subtrees"``.  ``sig``: the forest's
+        ``SR_subtree_signatures`` on the library's datapoints, when the caller already has them."""
+        self.semantic_library.update_library(forest, source, min_size, max_size, sig=sig)
 
     def _refresh(self, forest: Forest) -> None:
         """called once per call of the operator, before it reads the library"""

@@ -952,6 +952,35 @@ Tensor tree_SR_subtree_signatures(int64_t pop_size, int64_t data_points, int64_t
     return sig;
 }
 
+// int16[pop][gp_len]: for every node the descendant that takes its value on every row of `variables`, or the node itself
+// (evogp_hip_sr_subtree_introns); sig proposes (tree_SR_subtree_signatures' output, or anything), the tape verifies
+Tensor tree_SR_subtree_introns(int64_t pop_size, int64_t data_points, int64_t gp_len, int64_t var_len, int64_t out_len, const Tensor &value,
+                               const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &sig) {
+    const Forest f(pop_size, gp_len, value, type, size);
+    const float *X = check_semantic("tree_SR_subtree_introns", f, data_points, var_len, out_len, variables);
+    check_tensor(sig, {pop_size, gp_len}, "sig", f.dev, at::kLong);
+    c10::DeviceGuard guard(f.dev);
+    Tensor rep = empty({pop_size, gp_len}, at::kShort, f.dev);
+    check_rc(evogp_hip_sr_subtree_introns((unsigned)pop_size, (unsigned)data_points, (unsigned)gp_len, (unsigned)var_len, (unsigned)out_len, f.value,
+                                          f.type, f.size, X, (const unsigned long long *)sig.data_ptr<int64_t>(), rep.data_ptr<int16_t>(),
+                                          current_stream(f.dev)),
+             "tree_SR_subtree_introns");
+    return rep;
+}
+
+// every node replaced by its rep, from the root down (evogp_hip_remove_introns): a new forest and the nodes each tree lost
+Tensor4 tree_remove_introns(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &rep) {
+    const Forest f = Forest::infer(value, type, size);
+    check_tensor(rep, {f.pop, f.gp_len}, "rep", f.dev, at::kShort);
+    c10::DeviceGuard guard(f.dev);
+    const ForestOut out(f.pop, f.gp_len, f.dev);
+    Tensor removed = empty({f.pop}, at::kInt, f.dev);
+    check_rc(evogp_hip_remove_introns((unsigned)f.pop, (unsigned)f.gp_len, f.value, f.type, f.size, rep.data_ptr<int16_t>(), out.value, out.type,
+                                      out.size, removed.data_ptr<int>(), current_stream(f.dev)),
+             "tree_remove_introns");
+    return out.with(removed);
+}
+
 // (member int32[k], count int32[k], n_classes int32[1]): the k largest classes of equal signature among the eligible nodes, each by its
 // (size, flat index)-smallest member (evogp_hip_subtree_library_select); the workspace comes from torch's caching allocator
 Tensor3 subtree_library_select(const Tensor &sig, const Tensor &size, int64_t min_size, int64_t max_size, int64_t k) {
@@ -1451,6 +1480,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor variables, Tensor hash) -> Tensor");
     m.def("tree_SR_subtree_signatures(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor variables) -> Tensor");
+    m.def("tree_SR_subtree_introns(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor variables, Tensor sig) -> Tensor");
+    m.def("tree_remove_introns(Tensor value, Tensor node_type, Tensor subtree_size, Tensor rep) -> (Tensor value, Tensor node_type,"
+          " Tensor subtree_size, Tensor removed)");
     m.def("subtree_library_select(Tensor sig, Tensor size, int min_size, int max_size, int k) -> (Tensor member, Tensor count, Tensor n_classes)");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
@@ -1523,6 +1556,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_semantic_classes", &tree_SR_semantic_classes);
     m.impl("tree_SR_subtree_signatures", &tree_SR_subtree_signatures);
     m.impl("subtree_library_select", &subtree_library_select);
+    m.impl("tree_SR_subtree_introns", &tree_SR_subtree_introns);
+    m.impl("tree_remove_introns", &tree_remove_introns);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
     m.impl("tree_SR_weighted_scaling", &tree_SR_weighted_scaling);

@@ -102,3 +102,19 @@ def subtree_library_select(sig, size, min_size, max_size, k):
     ``(k,)``: the class sizes, 0 there; ``n_classes`` int32 ``(1,)``.  ``1 <= k <= 1024``.  Signatures alone decide: a collision merges
     two classes"""
     return torch.ops.evogp_hip.subtree_library_select(sig, size, min_size, max_size, k)
+
+
+def tree_SR_subtree_introns(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size, variables, sig):
+    """int16 ``(pop, gp_len)``: ``torch.ops.evogp_hip.tree_SR_subtree_introns`` (csrc/sr_introns.hip).  ``rep[t, i]`` is the descendant
+    of node i that takes the value of the subtree at i on EVERY row of ``variables`` (equal bit patterns, or both NaN), or i itself.  ``sig``
+    int64 ``(pop, gp_len)`` proposes -- ``tree_SR_subtree_signatures``' output on the same rows finds the introns, any other array finds
+    fewer -- and the tape verifies, so ``rep`` never names an unequal node; i on the tail and on malformed rows"""
+    return torch.ops.evogp_hip.tree_SR_subtree_introns(pop_size, data_points, gp_len, var_len, out_len, value, node_type, subtree_size,
+                                                       variables, sig)
+
+
+def tree_remove_introns(value, node_type, subtree_size, rep):
+    """``(value, node_type, subtree_size, removed)``: ``torch.ops.evogp_hip.tree_remove_introns`` (csrc/sr_introns.hip): every node
+    replaced by ``rep`` (int16 ``(pop, gp_len)``; an entry that is no descendant of its node counts as the node) from the root down, zero
+    tails, malformed rows copied; ``removed`` int32 ``(pop,)``: the nodes each tree lost"""
+    return torch.ops.evogp_hip.tree_remove_introns(value, node_type, subtree_size, rep)

@@ -54,7 +54,8 @@ class StandardPipeline(BasePipeline):
         hides a host sync), and the fitness vector is brought to the host AFTER ``algorithm.step`` has queued the
         selection / breeding kernels, so the copy overlaps them instead of idling the GPU."""
         # Lamarckian constant tuning / simplification: the optimised trees are scored and bred
-        if getattr(self.problem, "const_opt_steps", 0) > 0 or getattr(self.problem, "simplify_every", 0) > 0:
+        if (getattr(self.problem, "const_opt_steps", 0) > 0 or getattr(self.problem, "simplify_every", 0) > 0
+                or getattr(self.problem, "intron_removal_every", 0) > 0):
             self.algorithm.forest = self.problem.optimize(self.algorithm.forest)
         forest = self.algorithm.forest  # step() builds a new forest; the best tree comes from this one
         scores = getattr(self.problem, "scores", None)

@@ -31,7 +31,7 @@ class SymbolicRegression(BaseProblem):
                  loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
                  validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None,
                  scaling_loss: Optional[str] = None, derivative_labels: Optional[Tensor] = None, derivative_wrt=None,
-                 derivative_weight=1.0, sampled_monotonic=None):
+                 derivative_weight=1.0, sampled_monotonic=None, intron_removal_every: int = 0):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -121,7 +121,13 @@ class SymbolicRegression(BaseProblem):
         ``monotonic``, but held on the ROWS of the dataset instead of proven on a box: a tree whose partial derivative in the variable
         leaves its range, or is NaN, on any datapoint gets NaN from ``evaluate`` and -inf from ``scores`` (the optimistic companion
         of ``monotonic``; the two may be combined).  Alone it only masks: the fitness of the other trees is the plain one, bit for
-        bit.  Its variables are appended to ``derivative_wrt`` where that lacks them (they carry no label and no weight)."""
+        bit.  Its variables are appended to ``derivative_wrt`` where that lacks them (they carry no label and no weight).
+
+        ``intron_removal_every`` = k > 0 (single-output problems): every k-th call of ``optimize`` first takes the semantic introns out
+        of the forest (``Forest.remove_introns`` on the datapoints: nodes that take the value of one of their own descendants on every
+        row, ``x + 0``, ``max(x, x)``, ``neg(neg(x))``, ...), before ``simplify_every`` and the constant tuning.  No prediction changes
+        on any row of ``datapoints``, so it goes with every loss, weights, ``validation_mask``, ``linear_scaling`` and the constraints;
+        ``ValueError`` for labels of more than one column and together with ``multigene`` (the pass works on single-output trees)."""
         assert execute_mode in _MODES, f"execute_mode should be one of {_MODES}, but got {execute_mode}"
         assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
         self.execute_mode = execute_mode
@@ -133,6 +139,9 @@ class SymbolicRegression(BaseProblem):
         self.simplify_every = int(simplify_every)
         self.dedup = bool(dedup)
         self._optimize_calls = 0
+        if isinstance(intron_removal_every, bool) or not isinstance(intron_removal_every, int) or intron_removal_every < 0:
+            raise ValueError(f"intron_removal_every should be a non-negative integer, but got {intron_removal_every!r}")
+        self.intron_removal_every, self._intron_calls = intron_removal_every, 0
         self.linear_scaling = bool(linear_scaling)
         if datapoints is not None and labels is not None:
             self.datapoints, self.labels = datapoints, labels
@@ -157,6 +166,10 @@ class SymbolicRegression(BaseProblem):
         if self._box_check:
             self.input_lower, self.input_upper = self._input_box(input_bounds, float(input_margin))
         self.multigene = bool(multigene)
+        if self.intron_removal_every > 0:
+            self._one_label_column("intron_removal_every")
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with intron_removal_every > 0: that pass works on single-output trees")
         if self.multigene:
             self._one_label_column("multigene", "fits one label column, (D, 1)")
             for name, on in (("linear_scaling", self.linear_scaling), ("const_opt_steps > 0", self.const_opt_steps > 0),
@@ -675,7 +688,12 @@ class SymbolicRegression(BaseProblem):
 
     def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:
         """``forest`` simplified (``Forest.simplify``, on every ``simplify_every``-th call) and then with its constants tuned by
-        ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest itself when both are 0)."""
+        ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest itself when both are 0).  In front of
+        both, on every ``intron_removal_every``-th call, the forest without its semantic introns (``Forest.remove_introns``)."""
+        if self.intron_removal_every > 0:
+            self._intron_calls += 1
+            if self._intron_calls % self.intron_removal_every == 0:
+                forest = forest.remove_introns(self.datapoints, dedup=self.dedup)[0]
         if self.simplify_every > 0:
             self._optimize_calls += 1
             if self._optimize_calls % self.simplify_every == 0:

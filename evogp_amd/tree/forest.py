@@ -15,6 +15,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     semantic duplicates   semantic_hash, semantic_classes, semantic_unique: trees equal on every data row
     subtrees              SR_subtree_errors, simplify: the loss of every subtree; the smaller tree that is no worse
     subtree library       SR_subtree_signatures, subtree_library: the signature of every subtree; the distinct subtrees of a forest
+    introns               SR_subtree_introns, remove_introns: the nodes that take a descendant's value on every row, and the forest without them
     linear scaling        SR_scaled_fitness, apply_scaling: the loss under the least-squares slope and intercept; the tree with them
     weighted losses       SR_weighted_loss: sample weights, Huber / pinball / log-cosh, training and validation columns in one pass
     weighted scaling      SR_weighted_scaled_fitness: linear scaling fitted on one weight row, scored on up to 8, in one pass
@@ -540,7 +541,8 @@ class Forest:
         inputs = self._semantic_rows("SR_subtree_signatures", inputs)
         return torch.ops.evogp_hip.tree_SR_subtree_signatures(*self._shape(inputs), *self._tensors(), inputs)
 
-    def subtree_library(self, inputs: Tensor, k: int = BACKPROP_MAX_LIBRARY, min_size: int = 1, max_size: Optional[int] = None):
+    def subtree_library(self, inputs: Tensor, k: int = BACKPROP_MAX_LIBRARY, min_size: int = 1, max_size: Optional[int] = None,
+                        sig: Optional[Tensor] = None):
         """``(library, counts, tree, node)``: the semantically distinct subtrees of this forest on ``inputs``, the most frequent first.
         The subtrees of ``min_size <= size <= max_size`` nodes (``max_size=None``: any) fall into classes of equal signature
         (``SR_subtree_signatures``); a class is represented by its member of fewest nodes (ties: the smallest tree index, then node
@@ -549,7 +551,8 @@ class Forest:
         tree ``tree[j]`` word for word from position 0, zeros behind them, and carries this forest's ``func_mask``.  ``counts`` (m,) int32:
         the members per class; ``tree``, ``node`` (m,) int64.  Signatures alone decide a class: a collision of two 64-bit words merges two
         semantics and costs one member, so compute the library's semantics from ``library`` itself.  ONE host synchronisation (to read
-        m); ``ValueError`` for a multi-output forest, ``k`` outside 1 .. 1024 or sizes with ``1 <= min_size <= max_size`` violated."""
+        m); ``ValueError`` for a multi-output forest, ``k`` outside 1 .. 1024 or sizes with ``1 <= min_size <= max_size`` violated.
+        ``sig``: ``SR_subtree_signatures(inputs)`` when the caller already has it (``remove_introns`` takes the same), None to compute it."""
         inputs = self._semantic_rows("subtree_library", inputs)
         L = self.max_tree_len
         max_size = L if max_size is None else max_size
@@ -563,7 +566,10 @@ class Forest:
         if self.pop_size * L >= 2 ** 31:
             raise ValueError(f"subtree_library takes forests of fewer than 2^31 words, but got {self.pop_size} x {L}")
         value, ntype, size = self._tensors()
-        sig = torch.ops.evogp_hip.tree_SR_subtree_signatures(*self._shape(inputs), value, ntype, size, inputs)
+        if sig is None:
+            sig = torch.ops.evogp_hip.tree_SR_subtree_signatures(*self._shape(inputs), value, ntype, size, inputs)
+        elif not isinstance(sig, Tensor) or sig.dtype != torch.int64 or tuple(sig.shape) != (self.pop_size, L):
+            raise ValueError(f"sig should be the int64 ({self.pop_size}, {L}) tensor of SR_subtree_signatures")
         member, counts, n_classes = torch.ops.evogp_hip.subtree_library_select(sig, size, min_size, min(max_size, L), k)
         m = min(k, int(n_classes.item()))   # (the host sync)
         flat = member[:m].to(torch.int64)
@@ -573,6 +579,41 @@ class Forest:
         src = (node[:, None] + cols).clamp(max=L - 1)
         rows = tuple(torch.where(live, a[tree[:, None], src], torch.zeros((), dtype=a.dtype, device=a.device)) for a in (value, ntype, size))
         return Forest(self.input_len, 1, *rows, func_mask=self.func_mask), counts[:m], tree, node
+
+    # ---- exact semantic intron removal -----------------------------------------------------------
+    def SR_subtree_introns(self, inputs: Tensor, sig: Optional[Tensor] = None) -> Tensor:
+        """(pop, max_tree_len) int16 ``rep``: ``rep[t, i]`` is the descendant of node i whose subtree takes the value of the subtree at i
+        on EVERY row of ``inputs`` ``(D, input_len)`` -- equal float32 bit patterns, or both NaN; ``+0.0`` and ``-0.0`` are different -- or
+        i itself: the node computes nothing (``x + 0``, ``1 * x``, ``max(x, x)``, ``neg(neg(x))``, ``IF(c, a, a)``, ``(x * 2) / 2``, ...).
+        Among the equal descendants the signatures name the one of fewest nodes (then least index); the tape then verifies that one on
+        every row, so ``rep`` never names an unequal node, whatever ``sig`` holds.  ``sig``: ``SR_subtree_signatures(inputs)`` when the
+        caller already has it (the library refresh computes it too), None to compute it here.  i on the tail and on malformed rows.
+        Two walks per tree with ``sig=None``, one otherwise (csrc/sr_introns.hip); deterministic, no host synchronisation;
+        single-output forests (``ValueError`` otherwise)."""
+        inputs = self._semantic_rows("SR_subtree_introns", inputs)
+        shape, tensors = self._shape(inputs), self._tensors()
+        if sig is None:
+            sig = torch.ops.evogp_hip.tree_SR_subtree_signatures(*shape, *tensors, inputs)
+        elif not isinstance(sig, Tensor) or sig.dtype != torch.int64 or tuple(sig.shape) != (self.pop_size, self.max_tree_len):
+            raise ValueError(f"sig should be the int64 ({self.pop_size}, {self.max_tree_len}) tensor of SR_subtree_signatures")
+        return torch.ops.evogp_hip.tree_SR_subtree_introns(*shape, *tensors, inputs, sig.contiguous())
+
+    def remove_introns(self, inputs: Tensor, sig: Optional[Tensor] = None, dedup: bool = False):
+        """``(forest, removed)``: every tree without its semantic introns on ``inputs`` -- from the root down, a node becomes
+        ``SR_subtree_introns``' ``rep`` of it -- and the number of nodes each tree lost (int32 ``(pop,)``).  The new tree's prediction has,
+        on every row of ``inputs``, the bit pattern of the old one's (or both are NaN): every loss on these rows is unchanged.  A new
+        Forest with this forest's ``func_mask`` (this one is untouched), zero tails, malformed rows copied.  Removing the introns of the
+        result returns it unchanged unless a candidate that the verdict refused (``-0.0`` against ``+0.0``, a collision) was itself
+        dropped by the rewrite: the node then meets its next candidate in a second pass.  ``sig`` as in ``SR_subtree_introns``.  No host synchronisation.
+
+        ``dedup=True``: the same result, bit for bit, with the dataset passes run once per DISTINCT tree (``duplicate_classes``): the
+        other rows enter them as empty trees and take the ``rep`` of their class's first row before the rewrite, which runs on every
+        row.  A ``sig`` given with ``dedup=True`` is read on the first rows alone."""
+        source, gather = self._once_per_class(dedup)
+        rep = gather(source.SR_subtree_introns(inputs, sig))
+        value, ntype, size, removed = torch.ops.evogp_hip.tree_remove_introns(*self._tensors(), rep.contiguous())
+        # (a rewritten tree's functions are a subset of the old tree's)
+        return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), removed
 
     def SR_subtree_errors(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True):
         """``(node_err, node_const)``, both (pop, max_tree_len): ``node_err[t, i]`` is the loss the subtree rooted at node i of tree t
@@ -585,7 +626,7 @@ class Forest:
         return torch.ops.evogp_hip.tree_SR_subtree_errors(*self._shape(inputs), use_MSE, *self._tensors(), inputs, labels)
 
     def simplify(self, inputs: Tensor, labels: Tensor, use_MSE: bool = True, hoist: bool = True, fold_constants: bool = True,
-                 dedup: bool = False):
+                 dedup: bool = False, introns: bool = False):
         """``(forest, loss)``: every tree rewritten into a tree that is no larger and, on this dataset, no worse, in two launches with
         no host synchronisation.  ``hoist``: the tree becomes its subtree of least finite error (then least size, then least index),
         so a tree that is NaN as a whole but has a finite subtree is rescued.  ``fold_constants``: every function node whose subtree
@@ -595,7 +636,10 @@ class Forest:
 
         ``dedup=True``: the same result, bit for bit, with the pass over the dataset run once per DISTINCT tree
         (``duplicate_classes``): the other rows enter it as empty trees and take the subtree errors of their class's first row before
-        the rewrite, which runs on every row.  No host synchronisation is added."""
+        the rewrite, which runs on every row.  No host synchronisation is added.
+
+        ``introns=True``: the forest after hoist and fold then goes through ``remove_introns(inputs)``: nodes that take the value of one
+        of their descendants on every row leave.  The predictions keep their bits, so the returned loss is the one above."""
         self._single_output("simplify")
         inputs, labels = self._sr_data(inputs, labels)
         value, ntype, size = self._tensors()
@@ -604,7 +648,10 @@ class Forest:
         value, ntype, size, _, loss = torch.ops.evogp_hip.tree_prune(self.output_len, bool(hoist), bool(fold_constants), value, ntype, size,
                                                                      gather(node_err), gather(node_const))
         # (a rewritten tree's functions are a subset of the old tree's)
-        return Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask), loss
+        forest = Forest(self.input_len, self.output_len, value, ntype, size, func_mask=self.func_mask)
+        if introns:
+            forest = forest.remove_introns(inputs, dedup=dedup)[0]
+        return forest, loss
 
     # ---- linear scaling ------------------------------------------------------------------------
     def SR_scaled_fitness(self, inputs: Tensor, labels: Tensor, dedup: bool = False):

@@ -936,6 +936,40 @@ int evogp_hip_subtree_library_select(unsigned pop_size, unsigned gp_len, const u
                                      int max_size, int k, int *member_out /* [k] */, int *count_out /* [k] */, int *n_classes_out /* [1] */,
                                      void *workspace, evogp_stream_t stream);
 
+/* Exact semantic intron removal (no counterpart in the reference; csrc/sr_introns.hip; tests/intron_ref.py
+ * restates both entries), single-output forests only: a node whose subtree takes the value of one of its own descendants on EVERY data
+ * row computes nothing (x + 0, 1 * x, max(x, x), neg(neg(x)), IF(c, a, a), (x * 2) / 2, ...) and is replaced by that descendant.
+ *     E(a, b)     two float32 values are EQUAL when they have one bit pattern or are both NaN; +0.0 and -0.0 are NOT equal
+ *     n, span(i)  the live length size[t][0] kept inside [0, gp_len], and size[t][i] kept inside [1, n - i] (evogp_hip_prune_rows' reading)
+ * evogp_hip_sr_subtree_introns: sig u64[pop][gp_len] is evogp_hip_sr_subtree_signatures' output for the same forest and rows -- or any
+ * array whatever: SIGNATURES PROPOSE, THE TAPE VERIFIES.  For a well-formed tree (classify_tree == TREE_OK) and i < n
+ *     cand(i)        sig[t][i] != 0: the j with i < j < i + span(i) and sig[t][j] == sig[t][i] of smallest (span(j), j); i if there is
+ *                    none or sig[t][i] == 0
+ *     rep_out[t][i]  cand(i) when cand(i) != i and E(v_i(X[d]), v_cand(i)(X[d])) on every row d < D, v_i the float32 value of the subtree
+ *                    at node i as evogp_hip_sr_subtree_signatures' forward walk computes it; otherwise i.  A candidate that fails is
+ *                    NOT replaced by the next one (the causes: -0 against +0, or a collision of two 64-bit words; a known miss)
+ *     rep_out[t][i]  i on the tail [n, gp_len) and on every entry of a malformed tree
+ * Every function of the interpreter decides by comparison or propagates NaN (max / min are a >= b ? a : b), so a subtree replaced by one
+ * that is E-equal on every row leaves every ancestor E-equal on every row.  One launch with the plan of the tape passes and one tape word
+ * per node and lane; a tree without any candidate walks nothing.  No atomics, no float reductions, nothing synchronises with the host,
+ * bit-identical from run to run.  Rows of more than 64 nodes use the per-stream tape buffer of evogp_hip_sr_gradient, under the same
+ * rules.  EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, out_len != 1; then a NULL pointer: EVOGP_E_NULLPTR.
+ *
+ * evogp_hip_remove_introns: the rewrite.  rep i16[pop][gp_len] is trusted in nothing: an entry with rep[t][i] <= i or rep[t][i] >= i +
+ * span(i) counts as i.  For a well-formed tree, R(i) emits node rep[i] and then R(c) for each child c of rep[i] (the children of a node
+ * r are found by their spans from r + 1); the new tree is R(0).  The decision is hierarchical: the rep of a node that is itself dropped
+ * deletes nothing.  A kept node's new size is the number of kept nodes in its span; [new_len, gp_len) is zero in all three arrays;
+ * removed_out[t] = n - new_len.  A malformed row is copied as it is, with removed_out[t] = 0.  Not in place: an output array that is its
+ * input is EVOGP_E_BADARG, as are a zero size and gp_len > 1024; then a NULL pointer: EVOGP_E_NULLPTR.  One wave per tree, nothing
+ * synchronises with the host. */
+int evogp_hip_sr_subtree_introns(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
+                                 const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                                 const unsigned long long *sig /* [pop][gp_len] */, int16_t *rep_out /* [pop][gp_len] */,
+                                 evogp_stream_t stream);
+int evogp_hip_remove_introns(unsigned pop_size, unsigned gp_len, const float *value, const int16_t *type, const int16_t *size,
+                             const int16_t *rep /* [pop][gp_len] */, float *value_out, int16_t *type_out, int16_t *size_out,
+                             int *removed_out /* [pop] */, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -1018,7 +1052,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match, then evogp_hip_sr_subtree_signatures and evogp_hip_subtree_library_select with its _workspace_bytes were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match, then evogp_hip_sr_subtree_signatures and evogp_hip_subtree_library_select with its _workspace_bytes, then evogp_hip_sr_subtree_introns and evogp_hip_remove_introns were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
