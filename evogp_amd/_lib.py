@@ -88,6 +88,8 @@ PROTOTYPES = {
     "evogp_hip_subtree_library_select": [_u, _u, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_subtree_introns": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_remove_introns": [_u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_pair_moments_workspace_bytes": [_u, _u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_sr_pair_moments": [_u, _u, _u, _u, _u, _u, _vp, _vp, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_gene_fitness": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_wrap_linear":[_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_tree_intervals": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -31,6 +31,30 @@ class DefaultCrossover(BaseCrossover):
         return parents.crossover(left, right, left_pos, right_pos)
 
 
+class SemanticMateCrossover(DefaultCrossover):
+    """DefaultCrossover with a geometric choice of the second parent (``SemanticMate``): the first parents and their
+    positions are drawn as ``DefaultCrossover.draw`` draws them, ``right`` is what ``mate(parents, left)`` chooses for them, and the
+    donor position is drawn after that, as ``word % size[right]``.  A subclass, so ``GeneticProgramming`` composes its step from the
+    operators instead of taking the fused one.  No host synchronisation."""
+
+    def __init__(self, mate):
+        if not callable(mate):
+            raise ValueError(f"mate should be a SemanticMate or a callable (parents, left) -> (right, score), but got {type(mate).__name__}")
+        self.mate = mate
+
+    def pairs(self, parents: Forest, target_cnt: int):
+        """the index tensors of one round: ``(left, right, left_pos, right_pos)``, int32"""
+        sizes = parents.batch_subtree_size[:, 0]
+        left, _, left_pos, _ = self.draw(sizes, len(parents), target_cnt, sizes.device)
+        right = self.mate(parents, left)[0].to(torch.int32)
+        word = torch.randint(0, torch.iinfo(torch.int32).max, (target_cnt,), dtype=torch.int32, device=sizes.device)
+        return left, right, left_pos, (word % sizes[right]).to(torch.int32)
+
+    def __call__(self, forest: Forest, survivor_indices: torch.Tensor, target_cnt: int, fitness: torch.Tensor):
+        parents = forest[survivor_indices]
+        return parents.crossover(*self.pairs(parents, target_cnt))
+
+
 # ---- the non-default crossovers ---------------------------------------------------------------------------------------
 # Reference: crossover/diversity.py, crossover/leaf_biased.py.  ``crossover_rate`` of the offspring are recombined, the
 # rest are verbatim copies of random survivors.  Here both kinds come out of ONE tree_crossover launch over the whole
@@ -127,12 +151,16 @@ class ApproxGeometricCrossover(LibraryRefresh, BaseCrossover):
     them (the donor position is unused); a pair of one tree with itself is not excluded: its midpoint is the tree's own predictions, so
     the subtree is replaced by the library member nearest to what it already computes.  An offspring without a match (``best == -1``:
     a function on the path has no inverse, no row is REQUIRED, or no library member is finite there) takes the offspring of the same
-    index from ``fallback`` -- any ``BaseCrossover``, called once with the same arguments -- or is a copy of its recipient.  No host
-    synchronisation of its own (a rebuild of the library has two)."""
+    index from ``fallback`` -- any ``BaseCrossover``, called once with the same arguments -- or is a copy of its recipient.  ``mate``: a
+    ``SemanticMate`` (or any callable ``(parents, left) -> (right, score)``) that replaces the uniformly drawn mates -- ``right`` only;
+    None leaves every draw and every result as it is.  No host synchronisation of its own (a rebuild of the library has two)."""
 
     def __init__(self, datapoints: torch.Tensor, library=None, descriptor=None, library_size: int = 256, allow_constant: bool = True,
-                 fallback: BaseCrossover = None, refresh_every: int = 0, refresh_max_size=None):
+                 fallback: BaseCrossover = None, refresh_every: int = 0, refresh_max_size=None, mate=None):
         self._init_refresh(refresh_every, refresh_max_size)
+        if mate is not None and not callable(mate):
+            raise ValueError(f"mate should be None, a SemanticMate or a callable (parents, left) -> (right, score), but got {type(mate).__name__}")
+        self.mate = mate
         if not isinstance(datapoints, torch.Tensor) or datapoints.dim() != 2 or datapoints.shape[0] == 0:
             raise ValueError(f"datapoints should be a (D, input_len) tensor, but got {tuple(getattr(datapoints, 'shape', ()))}")
         if fallback is not None and not isinstance(fallback, BaseCrossover):
@@ -159,6 +187,8 @@ class ApproxGeometricCrossover(LibraryRefresh, BaseCrossover):
         parents = forest[survivor_indices]
         sizes = parents.batch_subtree_size[:, 0]
         left, right, left_pos, _ = self.draw(sizes, len(parents), target_cnt, sizes.device)
+        if self.mate is not None:
+            right = self.mate(parents, left)[0].to(torch.int32)
         new, found = self.apply(parents, left, right, left_pos)
         if self.fallback is not None:
             other = self.fallback(forest, survivor_indices, target_cnt, fitness)

@@ -981,6 +981,48 @@ Tensor4 tree_remove_introns(const Tensor &value, const Tensor &type, const Tenso
     return out.with(removed);
 }
 
+// (own float64 (E,), moments float64 (E, M, 3)): the residual moments of first[e] of forest A against candidates[e, m] of forest B on the
+// rows of `variables` (evogp_hip_sr_pair_moments); labels (D,) or None (every label 0); the workspace comes from torch's caching allocator
+std::tuple<Tensor, Tensor> tree_SR_pair_moments(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &mvalue,
+                                                const Tensor &mtype, const Tensor &msize, const Tensor &variables,
+                                                const c10::optional<Tensor> &labels, const Tensor &first, const Tensor &candidates) {
+    const char *op = "tree_SR_pair_moments";
+    const Forest a = Forest::infer(value, type, size);
+    TORCH_CHECK(mvalue.dim() == 2 && mvalue.size(0) >= 1 && mvalue.size(0) <= 0x7FFFFFFF && mvalue.size(1) >= 1 && mvalue.size(1) <= kMaxStack, op,
+                ": mate_value must be a (n_mates, mate_gp_len) tensor with n_mates > 0 and mate_gp_len in (0, ", kMaxStack, "], but got shape ",
+                mvalue.sizes());
+    const int64_t pop_b = mvalue.size(0), len_b = mvalue.size(1);
+    check_tensor(mvalue, {pop_b, len_b}, "mate_value", a.dev, at::kFloat);
+    check_tensor(mtype, {pop_b, len_b}, "mate_type", a.dev, at::kShort);
+    check_tensor(msize, {pop_b, len_b}, "mate_size", a.dev, at::kShort);
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, op, ": variables has too many data points: ", variables.size(0));
+    const int64_t D = variables.size(0), var_len = variables.size(1);
+    check_tensor(variables, {D, var_len}, "variables", a.dev, at::kFloat);
+    if (labels.has_value()) check_tensor(*labels, {D}, "labels", a.dev, at::kFloat);
+    TORCH_CHECK(first.dim() == 1 && first.size(0) <= 0x7FFFFFFF, op, ": first must be an (events,) tensor, but got shape ", first.sizes());
+    const int64_t E = first.size(0);
+    check_tensor(first, {E}, "first", a.dev, at::kInt);
+    TORCH_CHECK(candidates.dim() == 2 && candidates.size(1) >= 1 && candidates.size(1) <= EVOGP_PAIR_MAX_CANDIDATES, op,
+                ": candidates must be an (events, M) tensor with M in [1, ", EVOGP_PAIR_MAX_CANDIDATES, "], but got shape ", candidates.sizes());
+    const int64_t M = candidates.size(1);
+    check_tensor(candidates, {E, M}, "candidates", a.dev, at::kInt);
+    c10::DeviceGuard guard(a.dev);
+    Tensor own = empty({E}, at::kDouble, a.dev), moments = empty({E, M, 3}, at::kDouble, a.dev);
+    if (E == 0) return {own, moments};   // nothing to launch
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_pair_moments_workspace_bytes((unsigned)E, (unsigned)M, &bytes), op);
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, a.dev);
+    check_rc(evogp_hip_sr_pair_moments((unsigned)E, (unsigned)M, (unsigned)D, (unsigned)var_len, (unsigned)a.pop, (unsigned)a.gp_len, a.value, a.type,
+                                       a.size, (unsigned)pop_b, (unsigned)len_b, mvalue.data_ptr<float>(), mtype.data_ptr<int16_t>(),
+                                       msize.data_ptr<int16_t>(), variables.data_ptr<float>(),
+                                       labels.has_value() ? labels->data_ptr<float>() : nullptr, first.data_ptr<int>(), candidates.data_ptr<int>(),
+                                       own.data_ptr<double>(), moments.data_ptr<double>(), ws.data_ptr(), current_stream(a.dev)),
+             op);
+    return {own, moments};
+}
+
 // (member int32[k], count int32[k], n_classes int32[1]): the k largest classes of equal signature among the eligible nodes, each by its
 // (size, flat index)-smallest member (evogp_hip_subtree_library_select); the workspace comes from torch's caching allocator
 Tensor3 subtree_library_select(const Tensor &sig, const Tensor &size, int64_t min_size, int64_t max_size, int64_t k) {
@@ -1484,6 +1526,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor variables, Tensor sig) -> Tensor");
     m.def("tree_remove_introns(Tensor value, Tensor node_type, Tensor subtree_size, Tensor rep) -> (Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor removed)");
+    m.def("tree_SR_pair_moments(Tensor value, Tensor node_type, Tensor subtree_size, Tensor mate_value, Tensor mate_type, Tensor mate_size,"
+          " Tensor variables, Tensor? labels, Tensor first, Tensor candidates) -> (Tensor own, Tensor moments)");
     m.def("subtree_library_select(Tensor sig, Tensor size, int min_size, int max_size, int k) -> (Tensor member, Tensor count, Tensor n_classes)");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
@@ -1558,6 +1602,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("subtree_library_select", &subtree_library_select);
     m.impl("tree_SR_subtree_introns", &tree_SR_subtree_introns);
     m.impl("tree_remove_introns", &tree_remove_introns);
+    m.impl("tree_SR_pair_moments", &tree_SR_pair_moments);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
     m.impl("tree_SR_weighted_scaling", &tree_SR_weighted_scaling);

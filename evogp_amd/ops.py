@@ -118,3 +118,13 @@ def tree_remove_introns(value, node_type, subtree_size, rep):
     replaced by ``rep`` (int16 ``(pop, gp_len)``; an entry that is no descendant of its node counts as the node) from the root down, zero
     tails, malformed rows copied; ``removed`` int32 ``(pop,)``: the nodes each tree lost"""
     return torch.ops.evogp_hip.tree_remove_introns(value, node_type, subtree_size, rep)
+
+
+def tree_SR_pair_moments(value, node_type, subtree_size, mate_value, mate_type, mate_size, variables, labels, first, candidates):
+    """``(own, moments)``: ``torch.ops.evogp_hip.tree_SR_pair_moments`` (csrc/sr_pair.hip).  Event e pairs tree ``first[e]`` (int32
+    ``(E,)``) of the forest with the trees ``candidates[e, m]`` (int32 ``(E, M)``, ``M <= 16``) of the mate forest (any ``gp_len``, the same
+    ``var_len``); with ``r = (double)p - (double)labels`` (``labels`` float32 ``(D,)`` or None: 0) ``own`` float64 ``(E,)`` is ``sum r_a^2`` and
+    ``moments`` float64 ``(E, M, 3)`` is ``sum r_b^2, sum r_a r_b, sum (p_a - p_b)^2``; NaN by the rule of the unusable tree.  A word
+    depends on its pair and the dataset alone, bit for bit"""
+    return torch.ops.evogp_hip.tree_SR_pair_moments(value, node_type, subtree_size, mate_value, mate_type, mate_size, variables, labels, first,
+                                                    candidates)

@@ -24,6 +24,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     derivative bounds     SR_derivative_intervals, monotone_mask: bounds of the partial derivatives; the trees proven monotone
     input gradients       SR_input_gradients, SR_derivative_loss: d tree / d x on the data rows; the derivative loss and violations
     backpropagation       SR_desired_semantics, SR_backprop_match: the values a subtree would have to return; the nearest library member
+    pairs                 SR_pair_moments, semantic_distance: the residual inner products of pairs of trees; their distance
     midpoint              SR_midpoint_semantics, SR_midpoint_match: the same towards the midpoint of a tree and its mate (no labels)
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
@@ -52,6 +53,7 @@ _PREPARED_FORWARD = __import__("os").environ.get("EVOGP_PREPARED_FORWARD", "1") 
 LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes (include/evogp_hip.h EVOGP_LM_MAX_CONSTS)
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
+PAIR_MAX_CANDIDATES = 16     # candidates per event of SR_pair_moments (include/evogp_hip.h EVOGP_PAIR_MAX_CANDIDATES)
 BACKPROP_MAX_LIBRARY = 1024  # library members per SR_backprop_match call (include/evogp_hip.h EVOGP_BACKPROP_MAX_LIB)
 XGRAD_MAX_VARS = 8  #variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
 LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
@@ -530,6 +532,57 @@ class Forest:
         index order as a Forest, ``inverse`` (pop,) int64 with ``forest[inverse[t]]`` predicting what tree t predicts on every row, and
         ``counts`` (int64) the number of trees per representative.  ONE host synchronisation."""
         return self._unique(*self.semantic_classes(inputs, keep))
+
+    # ---- pairwise semantic moments -------------------------------------------------------------
+    def SR_pair_moments(self, inputs: Tensor, labels: Optional[Tensor], first: Tensor, candidates: Tensor, mates: Optional["Forest"] = None):
+        """``(own, moments)``: how far apart pairs of trees are on a dataset, and what combining them gives (csrc/sr_pair.hip,
+        include/evogp_hip.h evogp_hip_sr_pair_moments).  Event e pairs tree ``first[e]`` of this forest with the trees
+        ``candidates[e, m]`` of ``mates`` (a single-output Forest of the same ``input_len``, any ``max_tree_len``; None: this forest),
+        ``M <= 16``.  With ``r_t = (double)p_t - (double)y`` over the float32 predictions of ``batch_forward`` (``labels=None``: y = 0):
+        ``own[e] = sum r_a^2`` float64 ``(E,)``, ``moments[e, m] = (sum r_b^2, sum r_a r_b, sum (p_a - p_b)^2)`` float64 ``(E, M, 3)``.
+        ``candidates`` of shape ``(E,)`` is read as ``(E, 1)`` and ``moments`` then comes back as ``(E, 3)``.  A malformed tree, a tree
+        with a prediction that is not finite, or an index outside its forest is unusable: an unusable first tree makes ``own[e]`` and
+        ``moments[e]`` NaN, an unusable candidate its three words.  The words of a pair depend on its two trees and the dataset alone,
+        bit for bit.  No (pop, D) array, no host synchronisation; ``ValueError`` for a multi-output forest on either side, another
+        ``input_len``, ``M`` outside 1 .. 16 or a shape mismatch, before anything is launched."""
+        inputs = self._semantic_rows("SR_pair_moments", inputs)
+        other = self if mates is None else mates
+        if not isinstance(other, Forest) or other.output_len != 1 or other.input_len != self.input_len:
+            raise ValueError(f"SR_pair_moments: mates should be a single-output Forest with {self.input_len} inputs, but got "
+                             f"{type(other).__name__} with {getattr(other, 'input_len', '?')} inputs and {getattr(other, 'output_len', '?')} outputs")
+        device = self.batch_node_value.device
+        if labels is not None:
+            labels = check_tensor(labels, device)
+            if labels.dim() == 2 and labels.shape[1] == 1:
+                labels = labels[:, 0]
+            if labels.shape != (inputs.shape[0],):
+                raise ValueError(f"labels shape should be ({inputs.shape[0]},) or ({inputs.shape[0]}, 1), but got {tuple(labels.shape)}")
+            labels = labels.contiguous().to(torch.float32)
+        first, candidates = (check_tensor(t, device) for t in (first, candidates))
+        for name, t in (("first", first), ("candidates", candidates)):
+            if t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"{name} should hold integers, but got {t.dtype}")
+        if first.dim() != 1:
+            raise ValueError(f"first shape should be (E,), but got {tuple(first.shape)}")
+        flat = candidates.dim() == 1
+        if flat:
+            candidates = candidates[:, None]
+        if candidates.dim() != 2 or candidates.shape[0] != first.shape[0]:
+            raise ValueError(f"candidates shape should be ({first.shape[0]},) or ({first.shape[0]}, M), but got {tuple(candidates.shape)}")
+        if not 1 <= candidates.shape[1] <= PAIR_MAX_CANDIDATES:
+            raise ValueError(f"SR_pair_moments takes 1 to {PAIR_MAX_CANDIDATES} candidates per event, but got {candidates.shape[1]}")
+        own, moments = torch.ops.evogp_hip.tree_SR_pair_moments(*self._tensors(), *other._tensors(), inputs, labels,
+                                                                first.to(torch.int32).contiguous(), candidates.to(torch.int32).contiguous())
+        return own, (moments[:, 0] if flat else moments)
+
+    def semantic_distance(self, inputs: Tensor, first: Tensor, second: Tensor, mates: Optional["Forest"] = None) -> Tensor:
+        """(E,) float64: the Euclidean distance between the float32 prediction vectors of tree ``first[e]`` of this forest and tree
+        ``second[e]`` of ``mates`` (None: this forest) on the rows of ``inputs``: ``sqrt(SR_pair_moments(...)[1][:, 2])``.  NaN where
+        either tree is unusable.  No host synchronisation."""
+        second = check_tensor(second, self.batch_node_value.device)
+        if second.dim() != 1:
+            raise ValueError(f"second shape should be (E,), but got {tuple(second.shape)}")
+        return torch.sqrt(self.SR_pair_moments(inputs, None, first, second, mates)[1][:, 2])
 
     # ---- subtree signatures and the population-built library ------------------------------------
     def SR_subtree_signatures(self, inputs: Tensor) -> Tensor:

@@ -970,6 +970,42 @@ int evogp_hip_remove_introns(unsigned pop_size, unsigned gp_len, const float *va
                              const int16_t *rep /* [pop][gp_len] */, float *value_out, int16_t *type_out, int16_t *size_out,
                              int *removed_out /* [pop] */, evogp_stream_t stream);
 
+/* Pairwise semantic moments (no counterpart in the reference; csrc/sr_pair.hip; tests/pair_ref.py restates it):
+ * how far apart two single-output models are on a dataset, and what combining them gives.  For `events` events, one FIRST tree of forest
+ * A (pop_a rows of gp_len_a words) against n_cand <= EVOGP_PAIR_MAX_CANDIDATES CANDIDATE trees of forest B (pop_b rows of gp_len_b
+ * words; the same arrays as A, or others of the same var_len): first i32[events] indexes A, candidates i32[events][n_cand] indexes B.
+ *     p_t[d]   the float32 prediction of tree t on row d of variables (data_points, var_len): evogp_hip_batch_evaluate's bits
+ *     r_t[d]   (double)p_t[d] - (double)labels[d]; labels == NULL: every label is 0, the moments are those of the predictions
+ * With a = first[e], b = candidates[e][m]:
+ *     own_out[e]            = sum_d r_a[d]^2                                   f64[events]
+ *     moments_out[e][m][0]  = sum_d r_b[d]^2                                   f64[events][n_cand][3]
+ *     moments_out[e][m][1]  = sum_d r_a[d] * r_b[d]
+ *     moments_out[e][m][2]  = sum_d ((double)p_a[d] - (double)p_b[d])^2        (taken directly, not as Saa - 2 Sab + Sbb)
+ * A tree is UNUSABLE when it is malformed (the structural pre-pass of the SR kernels refuses it), when its prediction is not finite on
+ * some row, or when its index lies outside its forest.  An unusable first tree makes own_out[e] and every word of moments_out[e] NaN; an
+ * unusable candidate makes its three words NaN.  Decided on the device by flags; a word of usable trees is always finite.
+ * The D terms of a word are added in ONE order that depends on data_points alone (csrc/sr_pair_order.hpp: the rows of a lane in a tile
+ * of 256, the 64 lanes, the tiles of a wave slot, the wave slots), in explicit fma / add calls, in every kernel of the pass.  So the
+ * words of a pair are a function of its two trees, variables and labels: bit for bit the same in another event or slot, under another
+ * n_cand or events, next to other candidates, in other populations, whichever kernel takes it; Sab and Sdd of (a, b) equal those of
+ * (b, a); moments_out[e][m][0] equals own_out[e'] where candidates[e][m] and first[e'] are one tree; run to run.
+ * Launches: the register interpreter (LEAN then FULL build) over batches of events, a first tree interpreted once per row tile and its
+ * candidates after it (n_cand + 1 interpretations per event and tile), then the scratch-stack kernel over the events with a tree deeper
+ * than 16 operands; var_len > 32: the scratch-stack kernel alone, a wave per pair.  No float atomics, no (pop, D) array, everything on
+ * the caller's stream, nothing synchronises with the host, the engine allocates nothing.  workspace:
+ * evogp_hip_sr_pair_moments_workspace_bytes(events, n_cand) bytes (a mark byte per event; no zeroing needed).
+ * Before any launch: EVOGP_E_BADARG for n_cand == 0 or > 16, a zero data_points / var_len / pop / gp_len, gp_len > 1024, a size
+ * >= 2^31; then EVOGP_E_NULLPTR for a NULL pointer other than labels.  events == 0 is EVOGP_OK and launches nothing (first, candidates,
+ * the outputs and the workspace may then be NULL).  The ABI is single-output by construction: there is no out_len. */
+#define EVOGP_PAIR_MAX_CANDIDATES 16
+int evogp_hip_sr_pair_moments_workspace_bytes(unsigned events, unsigned n_cand, unsigned long long *bytes);
+int evogp_hip_sr_pair_moments(unsigned events, unsigned n_cand, unsigned data_points, unsigned var_len, unsigned pop_a, unsigned gp_len_a,
+                              const float *value_a, const int16_t *type_a, const int16_t *size_a, unsigned pop_b, unsigned gp_len_b,
+                              const float *value_b, const int16_t *type_b, const int16_t *size_b, const float *variables,
+                              const float *labels /* [data_points] or NULL */, const int *first /* [events] */,
+                              const int *candidates /* [events][n_cand] */, double *own_out /* [events] */,
+                              double *moments_out /* [events][n_cand][3] */, void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
@@ -1052,7 +1088,7 @@ int evogp_hip_get_sr_division(void);
  * 9: evogp_hip_sr_subtree_errors, evogp_hip_prune_rows; evogp_hip_sr_normal_eq and evogp_hip_sr_lm_step, then evogp_hip_tree_hash,
  * evogp_hip_tree_classes_workspace_bytes and evogp_hip_tree_classes, then evogp_hip_sr_linear_scaling and evogp_hip_wrap_linear, then evogp_hip_tree_intervals,
  * then evogp_hip_tree_derivative_intervals, then evogp_hip_sr_gene_fitness, then evogp_hip_tree_dimensions, then evogp_hip_sr_semantic_hash, evogp_hip_sr_semantic_classes and their
- * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match, then evogp_hip_sr_subtree_signatures and evogp_hip_subtree_library_select with its _workspace_bytes, then evogp_hip_sr_subtree_introns and evogp_hip_remove_introns were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
+ * _workspace_bytes, then evogp_hip_tree_structure, then evogp_hip_sr_weighted_loss, then evogp_hip_sr_weighted_gradient and evogp_hip_sr_weighted_normal_eq, then evogp_hip_sr_weighted_scaling, then evogp_hip_sr_input_gradient and evogp_hip_sr_derivative_loss, then evogp_hip_sr_desired and evogp_hip_sr_backprop_match, then evogp_hip_sr_desired_mid and evogp_hip_sr_agx_match, then evogp_hip_sr_subtree_signatures and evogp_hip_subtree_library_select with its _workspace_bytes, then evogp_hip_sr_subtree_introns and evogp_hip_remove_introns, then evogp_hip_sr_pair_moments and its _workspace_bytes were added to 9 without a bump: purely additive, no existing signature or behaviour changed). */
 int evogp_hip_abi_version(void);
 
 #ifdef __cplusplus
