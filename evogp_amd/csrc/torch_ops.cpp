@@ -1023,6 +1023,66 @@ std::tuple<Tensor, Tensor> tree_SR_pair_moments(const Tensor &value, const Tenso
     return {own, moments};
 }
 
+// (r2 int32 (D,), consts int64 (G, 2), status int32 (G,)): the doubled mid-ranks of `values` within the segments of seg_start, and Q, Q2
+// of `payload` (None: of the ranks themselves) per segment (evogp_hip_rank_rows)
+Tensor3 rank_rows(const Tensor &values, const c10::optional<Tensor> &payload, const Tensor &seg_start, int64_t max_segment) {
+    const char *op = "rank_rows";
+    TORCH_CHECK(values.is_cuda() && values.dim() == 1 && values.size(0) >= 1 && values.size(0) <= 0x7FFFFFFF, op,
+                ": values must be a non-empty (data_points,) CUDA tensor, but got shape ", values.sizes());
+    const int64_t D = values.size(0);
+    const c10::Device dev = values.device();
+    check_tensor(values, {D}, "values", dev, at::kFloat);
+    if (payload.has_value()) check_tensor(*payload, {D}, "payload", dev, at::kInt);
+    TORCH_CHECK(seg_start.dim() == 1 && seg_start.size(0) >= 2 && seg_start.size(0) - 1 <= D, op,
+                ": seg_start must be a (n_segments + 1,) tensor with 1 <= n_segments <= data_points, but got shape ", seg_start.sizes());
+    const int64_t G = seg_start.size(0) - 1;
+    check_tensor(seg_start, {G + 1}, "seg_start", dev, at::kInt);
+    TORCH_CHECK(max_segment >= 1 && max_segment <= EVOGP_RANK_MAX_SEGMENT && max_segment <= D, op, ": max_segment must lie in [1, min(",
+                EVOGP_RANK_MAX_SEGMENT, ", data_points)], but got ", max_segment);
+    c10::DeviceGuard guard(dev);
+    Tensor r2 = empty({D}, at::kInt, dev), consts = empty({G, 2}, at::kLong, dev), status = empty({G}, at::kInt, dev);
+    check_rc(evogp_hip_rank_rows((unsigned)D, (unsigned)G, (unsigned)max_segment, values.data_ptr<float>(),
+                                 payload.has_value() ? payload->data_ptr<int>() : nullptr, seg_start.data_ptr<int>(), r2.data_ptr<int>(),
+                                 (long long *)consts.data_ptr<int64_t>(), status.data_ptr<int>(), current_stream(dev)),
+             op);
+    return {r2, consts, status};
+}
+
+// (words int64 (pop, G, 2), fused float64 (pop, 3), scores float64 (pop, G), status uint8 (pop,)), an output that is not wanted empty: the
+// rank words of every tree per row segment, the fused Spearman (metric 0) or AUC (metric 1) sums and the scores they add (evogp_hip_sr_rank_stats); the workspace comes from torch's caching allocator
+Tensor4 tree_SR_rank_stats(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &payload,
+                           const Tensor &seg_start, int64_t max_segment, int64_t metric, bool want_words, bool want_fused, bool want_scores) {
+    const char *op = "tree_SR_rank_stats";
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0 && variables.size(0) <= 0x7FFFFFFF, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    const int64_t D = variables.size(0), var_len = variables.size(1);
+    check_tensor(variables, {D, var_len}, "variables", f.dev, at::kFloat);
+    check_tensor(payload, {D}, "payload", f.dev, at::kInt);
+    TORCH_CHECK(seg_start.dim() == 1 && seg_start.size(0) >= 2 && seg_start.size(0) - 1 <= D, op,
+                ": seg_start must be a (n_segments + 1,) tensor with 1 <= n_segments <= data_points, but got shape ", seg_start.sizes());
+    const int64_t G = seg_start.size(0) - 1;
+    check_tensor(seg_start, {G + 1}, "seg_start", f.dev, at::kInt);
+    TORCH_CHECK(max_segment >= 1 && max_segment <= EVOGP_RANK_MAX_SEGMENT && max_segment <= D, op, ": max_segment must lie in [1, min(",
+                EVOGP_RANK_MAX_SEGMENT, ", data_points)], but got ", max_segment);
+    TORCH_CHECK(metric == EVOGP_RANK_SPEARMAN || metric == EVOGP_RANK_AUC, op, ": metric must be 0 (spearman) or 1 (auc), but got ", metric);
+    TORCH_CHECK(want_words || want_fused || want_scores, op, ": nothing to compute: no output is wanted");
+    c10::DeviceGuard guard(f.dev);
+    Tensor words = empty({want_words ? f.pop : 0, G, 2}, at::kLong, f.dev), fused = empty({want_fused ? f.pop : 0, 3}, at::kDouble, f.dev);
+    Tensor scores = empty({want_scores ? f.pop : 0, G}, at::kDouble, f.dev), status = empty({f.pop}, at::kByte, f.dev);
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_rank_stats_workspace_bytes((unsigned)f.pop, (unsigned)G, &bytes), op);
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_sr_rank_stats((unsigned)f.pop, (unsigned)D, (unsigned)f.gp_len, (unsigned)var_len, (unsigned)G, (unsigned)max_segment,
+                                     f.value, f.type, f.size, variables.data_ptr<float>(), payload.data_ptr<int>(), seg_start.data_ptr<int>(),
+                                     (int)metric, want_words ? (long long *)words.data_ptr<int64_t>() : nullptr,
+                                     want_fused ? fused.data_ptr<double>() : nullptr,
+                                     want_scores ? scores.data_ptr<double>() : nullptr, status.data_ptr<uint8_t>(), ws.data_ptr(),
+                                     current_stream(f.dev)),
+             op);
+    return {words, fused, scores, status};
+}
+
 // (member int32[k], count int32[k], n_classes int32[1]): the k largest classes of equal signature among the eligible nodes, each by its
 // (size, flat index)-smallest member (evogp_hip_subtree_library_select); the workspace comes from torch's caching allocator
 Tensor3 subtree_library_select(const Tensor &sig, const Tensor &size, int64_t min_size, int64_t max_size, int64_t k) {
@@ -1528,6 +1588,10 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor removed)");
     m.def("tree_SR_pair_moments(Tensor value, Tensor node_type, Tensor subtree_size, Tensor mate_value, Tensor mate_type, Tensor mate_size,"
           " Tensor variables, Tensor? labels, Tensor first, Tensor candidates) -> (Tensor own, Tensor moments)");
+    m.def("rank_rows(Tensor values, Tensor? payload, Tensor seg_start, int max_segment) -> (Tensor r2, Tensor consts, Tensor status)");
+    m.def("tree_SR_rank_stats(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor payload, Tensor seg_start,"
+          " int max_segment, int metric, bool want_words, bool want_fused, bool want_scores) -> (Tensor words, Tensor fused, Tensor scores,"
+          " Tensor status)");
     m.def("subtree_library_select(Tensor sig, Tensor size, int min_size, int max_size, int k) -> (Tensor member, Tensor count, Tensor n_classes)");
     m.def("tree_SR_linear_scaling(int pop_size, int data_points, int gp_len, int var_len, int out_len, Tensor value, Tensor node_type,"
           " Tensor subtree_size, Tensor X, Tensor y) -> (Tensor loss, Tensor coef)");
@@ -1603,6 +1667,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_subtree_introns", &tree_SR_subtree_introns);
     m.impl("tree_remove_introns", &tree_remove_introns);
     m.impl("tree_SR_pair_moments", &tree_SR_pair_moments);
+    m.impl("rank_rows", &rank_rows);
+    m.impl("tree_SR_rank_stats", &tree_SR_rank_stats);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);
     m.impl("tree_SR_weighted_scaling", &tree_SR_weighted_scaling);

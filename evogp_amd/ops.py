@@ -9,7 +9,7 @@ reference's extension module does (src/evogp/tree/__init__.py:2, torch_wrapper.c
   ``CUDA`` key; there is deliberately no CPU implementation (the reference has none, torch_wrapper.cu:301) and no fallback;
 * the extra ops of this engine in the ``evogp_hip`` namespace (no counterpart in the reference).  The list lives in
   csrc/torch_ops.cpp, one schema per op in its ``TORCH_LIBRARY(evogp_hip)`` block; evogp_amd/tree/forest.py says which
-  method calls which.  The six functions below spell out six of them for callers that hold raw tensors, not a Forest.
+  method calls which.  The functions below spell out some of them for callers that hold raw tensors, not a Forest.
 
 Every implementation validates like the reference's wrapper, allocates its outputs and calls the C ABI of
 include/evogp_hip.h (``libevogp_hip.so``, loaded by ``_lib``) on torch's current stream; no Python runs per call.
@@ -128,3 +128,22 @@ def tree_SR_pair_moments(value, node_type, subtree_size, mate_value, mate_type, 
     depends on its pair and the dataset alone, bit for bit"""
     return torch.ops.evogp_hip.tree_SR_pair_moments(value, node_type, subtree_size, mate_value, mate_type, mate_size, variables, labels, first,
                                                     candidates)
+
+
+def rank_rows(values, payload, seg_start, max_segment):
+    """``(r2, consts, status)``: ``torch.ops.evogp_hip.rank_rows`` (csrc/sr_rank.hip).  ``values`` float32 ``(D,)`` are mid-ranked within
+    the contiguous segments ``seg_start`` int32 ``(G + 1,)`` (each of at most ``max_segment <= 8192`` rows): ``r2`` int32 ``(D,)`` is the
+    doubled mid-rank, ``#less + #less-or-equal + 1``; ``consts`` int64 ``(G, 2)`` is ``sum q, sum q^2`` of ``payload`` int32 ``(D,)`` per
+    segment, or of ``r2`` when ``payload`` is None; ``status`` int32 ``(G,)`` is 1 for a segment that holds a NaN (its ``r2`` is 0)"""
+    return torch.ops.evogp_hip.rank_rows(values, payload, seg_start, max_segment)
+
+
+def tree_SR_rank_stats(value, node_type, subtree_size, variables, payload, seg_start, max_segment, metric, want_words, want_fused,
+                       want_scores):
+    """``(words, fused, scores, status)``: ``torch.ops.evogp_hip.tree_SR_rank_stats`` (csrc/sr_rank.hip).  Per tree and row segment the float32
+    predictions are sorted inside the evaluation kernel; with ``R2`` their doubled mid-ranks and ``payload`` int32 ``(D,)`` in [0, 16384],
+    ``words`` int64 ``(pop, G, 2)`` is ``sum R2 * payload, sum R2^2``; ``fused`` float64 ``(pop, 3)`` is the sum, the sum of squares and the
+    count of the defined segment scores of ``metric`` (0 Spearman, 1 AUC), added in ascending segment; ``scores`` float64 ``(pop, G)`` is those scores themselves, NaN where undefined; ``status`` uint8 ``(pop,)`` is 1
+    for a malformed tree or one with a NaN prediction (words 0, fused and scores NaN).  An output that is not wanted comes back empty"""
+    return torch.ops.evogp_hip.tree_SR_rank_stats(value, node_type, subtree_size, variables, payload, seg_start, max_segment, metric,
+                                                  want_words, want_fused, want_scores)

@@ -4,6 +4,7 @@ from .symbolic_regression import SymbolicRegression
 from .classification import Classification
 from .transformation import Transformation
 from .custom_loss import CustomLoss
+from .rank_fitness import RankFitness
 from .rollout import LinearTrackingEnv, PendulumEnv, RolloutProblem
 
-__all__ = ["BaseProblem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]
+__all__ = ["BaseProblem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RankFitness", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]

@@ -38,7 +38,7 @@ bit-identical to the single-device one.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -54,11 +54,56 @@ LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes 
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
 PAIR_MAX_CANDIDATES = 16     # candidates per event of SR_pair_moments (include/evogp_hip.h EVOGP_PAIR_MAX_CANDIDATES)
+RANK_MAX_SEGMENT = 8192      # rows per segment of SR_rank_stats (include/evogp_hip.h EVOGP_RANK_MAX_SEGMENT)
+RANK_MAX_PAYLOAD = 16384     # largest payload word of SR_rank_stats: a doubled mid-rank within a segment
+RANK_METRICS = {"spearman": 0, "auc": 1}  # include/evogp_hip.h EVOGP_RANK_*
 BACKPROP_MAX_LIBRARY = 1024  # library members per SR_backprop_match call (include/evogp_hip.h EVOGP_BACKPROP_MAX_LIB)
 XGRAD_MAX_VARS = 8  #variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
 LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
+
+
+class RankSegments(NamedTuple):
+    """the row segments of the rank statistics, prepared once: ``perm`` int64 ``(D,)`` or None brings the rows of a group together
+    (stable), ``seg_start`` int32 ``(G + 1,)`` cuts the permuted rows, ``max_segment`` is the longest segment, ``rows`` is D"""
+    perm: Optional[Tensor]
+    seg_start: Tensor
+    max_segment: int
+    rows: int
+
+    def take(self, t: Tensor) -> Tensor:
+        return t if self.perm is None else t[self.perm]
+
+
+def rank_segments(segments, rows: int, device) -> RankSegments:
+    """``segments`` of the rank methods as a ``RankSegments``: None is one segment of all rows; a ``(D,)`` integer tensor of group
+    ids in any order is one segment per distinct id, in ascending id, the rows of a group in their given order (ONE host
+    synchronisation, for the segment lengths); a ``RankSegments`` passes through.  ``ValueError`` for a segment longer than 8192 rows,
+    an empty id tensor, or a shape or dtype that does not fit."""
+    if isinstance(segments, RankSegments):
+        if segments.rows != rows:
+            raise ValueError(f"the prepared segments cover {segments.rows} rows, but the data has {rows}")
+        return segments
+    if segments is None:
+        if not 1 <= rows <= RANK_MAX_SEGMENT:
+            raise ValueError(f"a segment holds 1 to {RANK_MAX_SEGMENT} rows, but the data has {rows} in one segment: pass segments")
+        return RankSegments(None, torch.tensor([0, rows], dtype=torch.int32, device=device), rows, rows)
+    ids = check_tensor(segments, device)
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError(f"segments should hold integer group ids, but got {ids.dtype}")
+    if ids.numel() == 0:
+        raise ValueError("segments holds no group id")
+    if ids.shape != (rows,):
+        raise ValueError(f"segments shape should be ({rows},), but got {tuple(ids.shape)}")
+    perm = torch.argsort(ids, stable=True)
+    counts = torch.unique_consecutive(ids[perm], return_counts=True)[1].cpu()   # the host synchronisation
+    longest = int(counts.max())
+    if longest > RANK_MAX_SEGMENT:
+        raise ValueError(f"a segment holds at most {RANK_MAX_SEGMENT} rows, but one group has {longest}")
+    start = torch.zeros(counts.numel() + 1, dtype=torch.int32)
+    start[1:] = torch.cumsum(counts, 0)
+    return RankSegments(perm, start.to(device), longest, rows)
 
 
 def check_loss(loss, param) -> Optional[float]:
@@ -583,6 +628,71 @@ class Forest:
         if second.dim() != 1:
             raise ValueError(f"second shape should be (E,), but got {tuple(second.shape)}")
         return torch.sqrt(self.SR_pair_moments(inputs, None, first, second, mates)[1][:, 2])
+
+    # ---- rank statistics: Spearman correlation and ROC-AUC ---------------------------------------
+    def _rank_call(self, inputs: Tensor, payload: Tensor, segs: RankSegments, metric: str, want: str):
+        """``(words, fused, scores, status)`` of the op on PREPARED arguments (rows already permuted, payload int32 and in range), the
+        outputs not named in ``want`` empty: no check, no host synchronisation"""
+        return torch.ops.evogp_hip.tree_SR_rank_stats(*self._tensors(), inputs, payload, segs.seg_start, segs.max_segment,
+                                                      RANK_METRICS[metric], "words" in want, "fused" in want, "scores" in want)
+
+    def _rank_rows(self, what: str, inputs: Tensor, column: Tensor, segments, name: str):
+        inputs = self._semantic_rows(what, inputs)
+        column = check_tensor(column, inputs.device)
+        if column.dim() == 2 and column.shape[1] == 1:
+            column = column[:, 0]
+        if column.shape != (inputs.shape[0],):
+            raise ValueError(f"{name} shape should be ({inputs.shape[0]},) or ({inputs.shape[0]}, 1), but got {tuple(column.shape)}")
+        segs = rank_segments(segments, inputs.shape[0], inputs.device)
+        return segs.take(inputs).contiguous(), segs.take(column).contiguous(), segs
+
+    def SR_rank_stats(self, inputs: Tensor, payload: Tensor, segments=None):
+        """``(words, usable)``: the exact rank words of every tree per row segment (csrc/sr_rank.hip, include/evogp_hip.h
+        evogp_hip_sr_rank_stats).  Within a segment the float32 predictions of ``batch_forward`` are mid-ranked (ties
+        share the average rank, -0.0 equals +0.0, +-inf are ordinary values); with ``R2`` the doubled mid-rank,
+        ``words[t, g] = (sum R2 * payload, sum R2^2)`` int64 ``(pop, G, 2)``.  ``payload`` ``(D,)`` holds integers in [0, 16384].
+        ``segments``: None (all rows are one segment, ``D <= 8192``), a ``(D,)`` integer tensor of group ids in any order (one segment
+        per id in ascending id; costs ONE host synchronisation for the segment lengths, ``rank_segments``), or a prepared
+        ``RankSegments``.  ``usable`` bool ``(pop,)``: False for a malformed tree or one with a NaN prediction; its words are 0.  The
+        words of (tree, segment) depend on the tree, the segment's rows and their payload alone, bit for bit.  ``ValueError`` before
+        anything is launched for a multi-output forest, a shape or dtype that does not fit, a segment longer than 8192 rows, an empty
+        id tensor or a payload outside [0, 16384] (checking the payload synchronises with the host once)."""
+        inputs, payload, segs = self._rank_rows("SR_rank_stats", inputs, payload, segments, "payload")
+        if payload.dtype.is_floating_point or payload.dtype == torch.bool:
+            raise ValueError(f"payload should hold integers, but got {payload.dtype}")
+        if int(payload.min()) < 0 or int(payload.max()) > RANK_MAX_PAYLOAD:
+            raise ValueError(f"payload should lie in [0, {RANK_MAX_PAYLOAD}]")
+        words, _, _, status = self._rank_call(inputs, payload.to(torch.int32), segs, "spearman", "words")
+        return words, status == 0
+
+    def _rank_metric(self, metric: str, inputs: Tensor, payload: Tensor, segs: RankSegments, per_segment: bool):
+        if per_segment:
+            return self._rank_call(inputs, payload, segs, metric, "scores")[2]   # (the doubles the fused sums add)
+        fused = self._rank_call(inputs, payload, segs, metric, "fused")[1]
+        count = torch.nan_to_num(fused[:, 2], nan=0.0)
+        return torch.where(count > 0, fused[:, 0] / count, torch.full_like(count, float("nan"))), count
+
+    def SR_spearman(self, inputs: Tensor, labels: Tensor, segments=None, per_segment: bool = False):
+        """Spearman rank correlation between every tree's predictions and ``labels`` ``(D,)`` within each row segment (``segments`` as
+        ``SR_rank_stats``): the labels are mid-ranked on the device, the trees by a sort inside the evaluation kernel; the predictions
+        are never stored.  ``per_segment=False``: ``(mean, defined_count)`` float64 ``(pop,)``, the mean over the segments where the
+        correlation is defined (the tree and the labels both take two values or more) and their number; NaN and 0 for a tree without
+        one, or an unusable tree.  ``per_segment=True``: float64 ``(pop, G)``, NaN where undefined.  ``ValueError`` as ``SR_rank_stats``,
+        and for a NaN label (one host synchronisation)."""
+        inputs, labels, segs = self._rank_rows("SR_spearman", inputs, labels, segments, "labels")
+        r2, _, status = torch.ops.evogp_hip.rank_rows(labels.to(torch.float32), None, segs.seg_start, segs.max_segment)
+        if bool(status.any()):
+            raise ValueError("labels holds a NaN")
+        return self._rank_metric("spearman", inputs, r2, segs, per_segment)
+
+    def SR_auc(self, inputs: Tensor, labels: Tensor, segments=None, per_segment: bool = False):
+        """ROC-AUC of every tree as a binary scorer against the 0/1 ``labels`` ``(D,)`` within each row segment: the Mann-Whitney
+        statistic of its mid-ranked predictions.  Returns what ``SR_spearman`` returns; a segment with one class only is undefined.
+        ``ValueError`` as ``SR_rank_stats``, and for labels other than 0 and 1 (one host synchronisation)."""
+        inputs, labels, segs = self._rank_rows("SR_auc", inputs, labels, segments, "labels")
+        if not bool(((labels == 0) | (labels == 1)).all()):
+            raise ValueError("SR_auc takes labels 0 and 1 only")
+        return self._rank_metric("auc", inputs, labels.to(torch.int32), segs, per_segment)
 
     # ---- subtree signatures and the population-built library ------------------------------------
     def SR_subtree_signatures(self, inputs: Tensor) -> Tensor:

@@ -1006,6 +1006,58 @@ int evogp_hip_sr_pair_moments(unsigned events, unsigned n_cand, unsigned data_po
                               const int *candidates /* [events][n_cand] */, double *own_out /* [events] */,
                               double *moments_out /* [events][n_cand][3] */, void *workspace, evogp_stream_t stream);
 
+/* Rank statistics (no counterpart in the reference; csrc/sr_rank.hip; tests/rank_ref.py restates it): scores that
+ * depend only on the ORDER of a single-output tree's predictions -- Spearman correlation and ROC-AUC -- from a sort per tree and row
+ * segment inside the evaluation kernel; no (pop, D) array.
+ *   SEGMENTS  The rows 0 .. data_points - 1 are cut into n_segments >= 1 contiguous segments by seg_start i32[n_segments + 1] (device
+ *             memory), seg_start[0] = 0, seg_start[G] = data_points, every segment of 1 <= n_g <= EVOGP_RANK_MAX_SEGMENT rows.
+ *             max_segment >= every n_g is the caller's promise (it selects the build: <= 1024 rows a wave sorts a tree alone, above
+ *             the workgroup does); rows past it, and a seg_start outside [0, data_points], are clamped away: no access leaves the
+ *             arrays, the words of such a call are unspecified.
+ *   KEY       of a prediction p (evogp_hip_batch_evaluate's float32 bits): the order-preserving u32 of the float, -0.0 taken as +0.0.
+ *             +-inf are ordinary keys.  A tree is UNUSABLE when it is malformed or when a prediction is a NaN on any row:
+ *             status_out[t] = 1, its words are 0 and its fused sums NaN.
+ *   R2        the doubled mid-rank within segment g:  R2_d = #{e : k_e < k_d} + #{e : k_e <= k_d} + 1, in [2, 2 n_g]; ties share
+ *             the average rank.
+ *   PAYLOAD   q i32[data_points], 0 <= q_d <= 16384: for Spearman the labels' own R2 within the segment (evogp_hip_rank_rows makes
+ *             them), for AUC the 0/1 label.
+ *   WORDS     per (tree, segment), i64:  S1 = sum_d R2_d q_d,  S2 = sum_d R2_d^2  (both < 2^42).  CONSTANTS per segment, from the
+ *             payload alone:  Q = sum q,  Q2 = sum q^2.
+ *   SCORES    in float64 from exact integers (csrc/sr_rank_formula.hpp), one multiplication, one square root, one division:
+ *             metric 0, Spearman:  A = n S1 - n(n+1) Q,  Bp = n S2 - (n(n+1))^2,  Bl = n Q2 - Q^2,  rho = A / sqrt(Bp * Bl); undefined
+ *                                  when Bp == 0 or Bl == 0 (a tree or labels constant on the segment, n == 1)
+ *             metric 1, AUC:       (S1 - Q(Q+1)) / (2 Q (n - Q)); undefined when Q == 0 or Q == n
+ *   FUSED     f64[pop][3]: the sum of the defined segments' scores added in ascending g, the sum of their squares added the same
+ *             way, and the count of defined segments.
+ *   PER SEGMENT  scores_out f64[pop][n_segments]: the score of every (tree, segment), NaN where it is undefined or the tree unusable:
+ *             the very doubles the fused sums add.
+ * evogp_hip_sr_rank_stats writes words_out i64[pop][n_segments][2], fused_out and scores_out (each may be NULL) and status_out u8[pop].
+ * A segment without rows (excluded above) gets words 0 and no score.
+ * Launches on the caller's stream: the payload's constants, the register interpreter (LEAN then FULL build) with the sort in its
+ * epilogue, the scratch-stack kernel for trees deeper than 16 operands and for var_len > 32.  Integer sums only: the result is a
+ * function of the tree, its segment's rows and their payload, bit for bit, whatever the batch, the neighbours or the population.
+ * Nothing synchronises with the host, the engine allocates nothing: workspace is evogp_hip_sr_rank_stats_workspace_bytes(pop,
+ * n_segments) bytes (no zeroing needed).
+ * evogp_hip_rank_rows: one workgroup per segment.  values f32[data_points] (or NULL) are mid-ranked within their segments into r2_out
+ * i32[data_points] (may be NULL); a segment that holds a NaN gets status_out[g] = 1 (i32[n_segments]) and r2 0.  consts_out
+ * i64[n_segments][2] (may be NULL) receives Q, Q2 of payload, or of the ranks written when payload is NULL.
+ * Before any launch: EVOGP_E_BADARG for a zero size, n_segments > data_points, max_segment > EVOGP_RANK_MAX_SEGMENT or > data_points,
+ * gp_len > 1024, a metric other than 0 or 1, a size >= 2^31; then EVOGP_E_NULLPTR.  Single-output by construction: there is no out_len. */
+#define EVOGP_RANK_MAX_SEGMENT 8192
+#define EVOGP_RANK_SPEARMAN 0
+#define EVOGP_RANK_AUC 1
+int evogp_hip_rank_rows(unsigned data_points, unsigned n_segments, unsigned max_segment, const float *values /* [data_points] or NULL */,
+                        const int *payload /* [data_points] or NULL */, const int *seg_start /* [n_segments + 1] */,
+                        int *r2_out /* [data_points] or NULL */, long long *consts_out /* [n_segments][2] or NULL */,
+                        int *status_out /* [n_segments] */, evogp_stream_t stream);
+int evogp_hip_sr_rank_stats_workspace_bytes(unsigned pop_size, unsigned n_segments, unsigned long long *bytes);
+int evogp_hip_sr_rank_stats(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned n_segments,
+                            unsigned max_segment, const float *value, const int16_t *type, const int16_t *size, const float *variables,
+                            const int *payload /* [data_points] */, const int *seg_start /* [n_segments + 1] */, int metric,
+                            long long *words_out /* [pop][n_segments][2] or NULL */, double *fused_out /* [pop][3] or NULL */,
+                            double *scores_out /* [pop][n_segments] or NULL */,
+                            unsigned char *status_out /* [pop] */, void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
