@@ -1023,6 +1023,37 @@ std::tuple<Tensor, Tensor> tree_SR_pair_moments(const Tensor &value, const Tenso
     return {own, moments};
 }
 
+// (G float64 (n, n), lin float64 (n, 2), usable bool (n,)): the Gram matrix of the prediction (residuals: residual) vectors of the trees
+// index[0 .. n) on the rows of `variables` (evogp_hip_sr_gram); labels (D,) or None; the workspace comes from torch's caching allocator
+Tensor3 tree_SR_gram(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const c10::optional<Tensor> &labels,
+                     const Tensor &index, bool residuals) {
+    const char *op = "tree_SR_gram";
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, op, ": variables has too many data points: ", variables.size(0));
+    const int64_t D = variables.size(0), var_len = variables.size(1);
+    check_tensor(variables, {D, var_len}, "variables", f.dev, at::kFloat);
+    if (labels.has_value()) check_tensor(*labels, {D}, "labels", f.dev, at::kFloat);
+    TORCH_CHECK(labels.has_value() || !residuals, op, ": residuals needs labels");
+    TORCH_CHECK(index.dim() == 1 && index.size(0) <= EVOGP_GRAM_MAX_TREES, op, ": index must be an (n,) tensor with n in [0, ",
+                EVOGP_GRAM_MAX_TREES, "], but got shape ", index.sizes());
+    const int64_t n = index.size(0);
+    check_tensor(index, {n}, "index", f.dev, at::kInt);
+    c10::DeviceGuard guard(f.dev);
+    Tensor G = empty({n, n}, at::kDouble, f.dev), lin = empty({n, 2}, at::kDouble, f.dev), usable = empty({n}, at::kBool, f.dev);
+    if (n == 0) return {G, lin, usable};   // nothing to launch
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_gram_workspace_bytes((unsigned)n, (unsigned)D, &bytes), op);
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_sr_gram((unsigned)n, (unsigned)D, (unsigned)var_len, (unsigned)f.pop, (unsigned)f.gp_len, f.value, f.type, f.size,
+                               variables.data_ptr<float>(), labels.has_value() ? labels->data_ptr<float>() : nullptr, index.data_ptr<int>(),
+                               residuals ? 1 : 0, G.data_ptr<double>(), lin.data_ptr<double>(), (unsigned char *)usable.data_ptr<bool>(),
+                               ws.data_ptr(), current_stream(f.dev)),
+             op);
+    return {G, lin, usable};
+}
+
 // (r2 int32 (D,), consts int64 (G, 2), status int32 (G,)): the doubled mid-ranks of `values` within the segments of seg_start, and Q, Q2
 // of `payload` (None: of the ranks themselves) per segment (evogp_hip_rank_rows)
 Tensor3 rank_rows(const Tensor &values, const c10::optional<Tensor> &payload, const Tensor &seg_start, int64_t max_segment) {
@@ -1588,6 +1619,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor subtree_size, Tensor removed)");
     m.def("tree_SR_pair_moments(Tensor value, Tensor node_type, Tensor subtree_size, Tensor mate_value, Tensor mate_type, Tensor mate_size,"
           " Tensor variables, Tensor? labels, Tensor first, Tensor candidates) -> (Tensor own, Tensor moments)");
+    m.def("tree_SR_gram(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor? labels, Tensor index,"
+          " bool residuals) -> (Tensor gram, Tensor lin, Tensor usable)");
     m.def("rank_rows(Tensor values, Tensor? payload, Tensor seg_start, int max_segment) -> (Tensor r2, Tensor consts, Tensor status)");
     m.def("tree_SR_rank_stats(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor payload, Tensor seg_start,"
           " int max_segment, int metric, bool want_words, bool want_fused, bool want_scores) -> (Tensor words, Tensor fused, Tensor scores,"
@@ -1668,6 +1701,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_remove_introns", &tree_remove_introns);
     m.impl("tree_SR_pair_moments", &tree_SR_pair_moments);
     m.impl("rank_rows", &rank_rows);
+    m.impl("tree_SR_gram", &tree_SR_gram);
     m.impl("tree_SR_rank_stats", &tree_SR_rank_stats);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);

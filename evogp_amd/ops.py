@@ -130,6 +130,15 @@ def tree_SR_pair_moments(value, node_type, subtree_size, mate_value, mate_type, 
                                                     candidates)
 
 
+def tree_SR_gram(value, node_type, subtree_size, variables, labels, index, residuals):
+    """``(G, lin, usable)``: ``torch.ops.evogp_hip.tree_SR_gram`` (csrc/sr_gram.hip).  For the trees ``index`` (int32 ``(n,)``, ``n <= 8192``)
+    of a single-output forest, with ``v = (double)p - (double)labels`` under ``residuals`` (``labels`` float32 ``(D,)``) and ``v = (double)p``
+    otherwise: ``G`` float64 ``(n, n)`` is ``sum_d v_i v_j`` on the float64 matrix cores, ``lin`` float64 ``(n, 2)`` is ``sum v_i, sum v_i y``
+    (0 without labels), ``usable`` bool ``(n,)``; the row, column and ``lin`` words of an unusable tree (malformed, a non-finite prediction, an
+    index outside the forest) are NaN.  A word depends on its two trees and the dataset alone, bit for bit, and ``G`` equals ``G.T``"""
+    return torch.ops.evogp_hip.tree_SR_gram(value, node_type, subtree_size, variables, labels, index, residuals)
+
+
 def rank_rows(values, payload, seg_start, max_segment):
     """``(r2, consts, status)``: ``torch.ops.evogp_hip.rank_rows`` (csrc/sr_rank.hip).  ``values`` float32 ``(D,)`` are mid-ranked within
     the contiguous segments ``seg_start`` int32 ``(G + 1,)`` (each of at most ``max_segment <= 8192`` rows): ``r2`` int32 ``(D,)`` is the

@@ -686,6 +686,20 @@ class SymbolicRegression(BaseProblem):
             fitness = torch.where(torch.isnan(loss), torch.full_like(loss, float("-inf")), -loss)
         return self._masked(forest, fitness, float("-inf")) if self._constrained else fitness
 
+    def ensemble(self, forest: Forest, k: int, ridge: float = 1e-6):
+        """``(index, weights, intercept, loss)``: the least-squares stacked ensemble (``Forest.fit_ensemble``) of the top
+        ``k`` trees by ``scores`` that have a finite score -- with ``semantic_dedup`` one per semantic class, the others being scored
+        -inf.  ``index`` int32 ``(n,)``, ``n <= k``, best first.  ONE host synchronisation (the number of finite scores)."""
+        self._one_label_column("ensemble")
+        if not 1 <= int(k) <= 8192:
+            raise ValueError(f"k should be in 1 .. 8192, but got {k}")
+        scores = self.scores(forest)
+        best, index = torch.topk(scores, min(int(k), forest.pop_size))
+        index = index[torch.isfinite(best)].to(torch.int32)
+        if index.numel() == 0:
+            raise ValueError("ensemble: no tree has a finite score")
+        return (index,) + tuple(forest.fit_ensemble(self.datapoints, self.labels, index, ridge))
+
     def optimize(self, forest: Forest, use_MSE: bool = True) -> Forest:
         """``forest`` simplified (``Forest.simplify``, on every ``simplify_every``-th call) and then with its constants tuned by
         ``const_opt_steps`` steps of ``Forest.optimize_constants`` on this dataset (the forest itself when both are 0).  In front of

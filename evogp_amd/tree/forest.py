@@ -25,6 +25,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     input gradients       SR_input_gradients, SR_derivative_loss: d tree / d x on the data rows; the derivative loss and violations
     backpropagation       SR_desired_semantics, SR_backprop_match: the values a subtree would have to return; the nearest library member
     pairs                 SR_pair_moments, semantic_distance: the residual inner products of pairs of trees; their distance
+    Gram matrix           SR_gram, semantic_cosine, fit_ensemble, ensemble_predict: the inner products of all trees of a set; the stacked ensemble
     midpoint              SR_midpoint_semantics, SR_midpoint_match: the same towards the midpoint of a tree and its mate (no labels)
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
@@ -54,6 +55,7 @@ LM_MAX_CONSTS = 8  # constants per tree the Levenberg-Marquardt optimiser tunes 
 GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evogp_hip.h EVOGP_GENES_MAX)
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
 PAIR_MAX_CANDIDATES = 16     # candidates per event of SR_pair_moments (include/evogp_hip.h EVOGP_PAIR_MAX_CANDIDATES)
+GRAM_MAX_TREES = 8192        # trees of one SR_gram call (include/evogp_hip.h EVOGP_GRAM_MAX_TREES)
 RANK_MAX_SEGMENT = 8192      # rows per segment of SR_rank_stats (include/evogp_hip.h EVOGP_RANK_MAX_SEGMENT)
 RANK_MAX_PAYLOAD = 16384     # largest payload word of SR_rank_stats: a doubled mid-rank within a segment
 RANK_METRICS = {"spearman": 0, "auc": 1}  # include/evogp_hip.h EVOGP_RANK_*
@@ -628,6 +630,80 @@ class Forest:
         if second.dim() != 1:
             raise ValueError(f"second shape should be (E,), but got {tuple(second.shape)}")
         return torch.sqrt(self.SR_pair_moments(inputs, None, first, second, mates)[1][:, 2])
+
+    # ---- the population Gram matrix and the stacked ensemble -------------------------------------
+    def _gram_args(self, what: str, inputs: Tensor, labels: Optional[Tensor], index: Optional[Tensor], need_labels: bool):
+        """(inputs float32 (D, input_len), labels float32 (D,) or None, index int32 (n,)), checked: ``ValueError`` before any launch"""
+        inputs = self._semantic_rows(what, inputs)
+        device = self.batch_node_value.device
+        if labels is None and need_labels:
+            raise ValueError(f"{what} needs labels")
+        if labels is not None:
+            labels = check_tensor(labels, device)
+            if labels.dim() == 2 and labels.shape[1] == 1:
+                labels = labels[:, 0]
+            if labels.shape != (inputs.shape[0],):
+                raise ValueError(f"labels shape should be ({inputs.shape[0]},) or ({inputs.shape[0]}, 1), but got {tuple(labels.shape)}")
+            if not labels.dtype.is_floating_point:
+                raise ValueError(f"labels should hold floats, but got {labels.dtype}")
+            labels = labels.contiguous().to(torch.float32)
+        if index is None:
+            index = torch.arange(self.pop_size, dtype=torch.int32, device=device)
+        index = check_tensor(index, device)
+        if index.dtype.is_floating_point or index.dtype == torch.bool:
+            raise ValueError(f"index should hold integers, but got {index.dtype}")
+        if index.dim() != 1 or not 1 <= index.shape[0] <= GRAM_MAX_TREES:
+            raise ValueError(f"{what} takes an index of shape (n,) with n in 1 .. {GRAM_MAX_TREES}, but got {tuple(index.shape)}")
+        return inputs, labels, index.to(torch.int32).contiguous()
+
+    def SR_gram(self, inputs: Tensor, labels: Optional[Tensor] = None, index: Optional[Tensor] = None, residuals: bool = False):
+        """``(G, lin, usable)``: how ALL the trees of a set relate to each other on a dataset (csrc/sr_gram.hip, include/evogp_hip.h
+        evogp_hip_sr_gram).  For the trees ``index`` ``(n,)`` (None: every tree; ``n <= 8192``), with ``p_i`` the float32
+        predictions of ``batch_forward`` and ``v_i = (double)p_i - (double)y`` under ``residuals=True``, ``v_i = (double)p_i`` otherwise:
+        ``G[i, j] = sum_d v_i v_j`` float64 ``(n, n)`` on the float64 matrix cores, ``lin[i] = (sum v_i, sum v_i y)`` float64 ``(n, 2)``
+        (the second word 0 without labels), ``usable`` bool ``(n,)``.  A malformed tree, a tree with a prediction that is not finite, or an
+        index outside the forest is unusable: its row and column of ``G`` and its ``lin`` words are NaN.  The order of summation is fixed
+        by ``D`` alone, so a word depends on its two trees and the dataset alone, bit for bit; ``G`` equals ``G.T``.  No ``(n, D)`` float64
+        copy, no host synchronisation; ``ValueError`` for a multi-output forest, a shape or dtype mismatch, ``residuals=True`` without
+        labels or ``n`` outside 1 .. 8192, before anything is launched."""
+        inputs, labels, index = self._gram_args("SR_gram", inputs, labels, index, bool(residuals))
+        return torch.ops.evogp_hip.tree_SR_gram(*self._tensors(), inputs, labels, index, bool(residuals))
+
+    def semantic_cosine(self, inputs: Tensor, labels: Optional[Tensor] = None, index: Optional[Tensor] = None) -> Tensor:
+        """``(n, n)`` float64: ``G_ij / sqrt(G_ii G_jj)`` of ``SR_gram`` -- the cosine of the angle between the residual vectors of two
+        trees when labels are given (Chen, Xue & Zhang's angle, over the whole set), between their prediction vectors otherwise.  NaN where
+        a tree is unusable or a diagonal is 0.  No host synchronisation."""
+        G = self.SR_gram(inputs, labels, index, residuals=labels is not None)[0]
+        d = torch.diagonal(G)
+        return G / torch.sqrt(d[:, None] * d[None, :])
+
+    def fit_ensemble(self, inputs: Tensor, labels: Tensor, index: Optional[Tensor] = None, ridge: float = 0.0):
+        """``(weights (n,), intercept, loss)`` in float64: the least-squares stacked ensemble ``intercept + sum_i weights[i] T_i(x)`` of the
+        trees ``index`` on ``(inputs, labels)``, from ONE ``SR_gram`` pass and an ``n x n`` solve
+        (``evogp_amd.problem.ensemble.ensemble_weights``: centred normal equations, ``ridge * trace / n`` on the diagonal, Cholesky;
+        ``ridge == 0``: the minimum-norm solution).  An unusable member has weight exactly 0 and stays out of the system.  ``loss`` is the
+        training mean squared error, never above the best member's.  ``intercept`` and ``loss`` are 0-dim tensors."""
+        from ..problem.ensemble import ensemble_weights
+        if not ridge >= 0.0:
+            raise ValueError(f"ridge should be >= 0, but got {ridge}")
+        inputs, labels, index = self._gram_args("fit_ensemble", inputs, labels, index, True)
+        G, lin, _ = torch.ops.evogp_hip.tree_SR_gram(*self._tensors(), inputs, labels, index, False)
+        y = labels.to(torch.float64)
+        return ensemble_weights(G, lin, y.sum(), (y * y).sum(), inputs.shape[0], ridge)
+
+    def ensemble_predict(self, x: Tensor, index: Tensor, weights: Tensor, intercept) -> Tensor:
+        """``(batch,)`` float64: ``intercept + sum_i weights[i] T_index[i](x)`` -- ``batch_forward`` of the ``n`` member rows and a float64
+        weighted sum.  A member of weight 0 (an unusable tree of ``fit_ensemble``) does not enter, whatever it predicts."""
+        self._single_output("ensemble_predict", ValueError)
+        device = self.batch_node_value.device
+        index, weights = check_tensor(index, device), check_tensor(weights, device).to(torch.float64)
+        if index.dim() != 1 or weights.shape != index.shape:
+            raise ValueError(f"index and weights should both be (n,), but got {tuple(index.shape)} and {tuple(weights.shape)}")
+        inside = (index >= 0) & (index < self.pop_size)
+        members = self[index.to(torch.int64).clamp(0, self.pop_size - 1)]
+        p = members.batch_forward(x)[:, :, 0].to(torch.float64)
+        live = (inside & (weights != 0))[:, None]
+        return (torch.where(live, p, 0.0) * torch.where(live, weights[:, None], 0.0)).sum(0) + torch.as_tensor(intercept, dtype=torch.float64, device=device)
 
     # ---- rank statistics: Spearman correlation and ROC-AUC ---------------------------------------
     def _rank_call(self, inputs: Tensor, payload: Tensor, segs: RankSegments, metric: str, want: str):

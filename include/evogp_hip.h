@@ -1058,6 +1058,43 @@ int evogp_hip_sr_rank_stats(unsigned pop_size, unsigned data_points, unsigned gp
                             double *scores_out /* [pop][n_segments] or NULL */,
                             unsigned char *status_out /* [pop] */, void *workspace, evogp_stream_t stream);
 
+/* The population Gram matrix (no counterpart in the reference; csrc/sr_gram.hip): the float64 inner products of
+ * the prediction (or residual) vectors of n chosen trees of a single-output forest, on the float64 matrix cores -- what a stacked
+ * ensemble, population-wide cosines and correlations, and semantic diversity statistics are built from.  For index i32[n] into the
+ * forest, 1 <= n <= EVOGP_GRAM_MAX_TREES:
+ *     p_i[d]        the float32 prediction of tree index[i] on row d of variables (data_points, var_len): evogp_hip_batch_evaluate's bits
+ *     v_i[d]        (double)p_i[d] - (double)labels[d] when residuals != 0 (labels must be given), else (double)p_i[d]
+ *     gram_out[i][j] = sum_d v_i[d] * v_j[d]                                  f64[n][n]
+ *     lin_out[i]     = (sum_d v_i[d], sum_d v_i[d] * (double)labels[d])       f64[n][2]; the second word is 0 without labels
+ *     usable_out[i]  = 1, or 0 for an unusable tree                           u8[n]
+ * A tree is UNUSABLE when it is malformed (the structural pre-pass of the SR kernels refuses it), when its prediction is not finite on
+ * some row, or when its index lies outside the forest (the rule of evogp_hip_sr_pair_moments).  An unusable tree makes its row and its
+ * column of gram_out and its two lin_out words NaN.  The flags decide, never the arithmetic: a malformed tree enters the matrix pass as
+ * zeros, a non-finite prediction as 0, and a word of two usable trees is always finite.
+ * THE ORDER OF SUMMATION is part of the definition (csrc/sr_gram_order.hpp).  The rows are cut into segments of 1024; a segment's value is
+ * one chain of v_mfma_f64_16x16x4_f64 over its 256 consecutive groups of 4 rows, in row order, from a zero accumulator, rows past
+ * data_points entering as 0; a word is ((0 + S_0) + S_1) + ..., the segments in order, added with __dadd_rn.  The order depends on
+ * data_points alone: a word is a function of its two trees, variables and labels -- the same bits at another place of index, under
+ * another n, next to other trees, from run to run and from stream to stream; gram_out equals its transpose bit for bit (one workgroup
+ * writes a word and its mirror); a repeated index gives identical rows.  lin_out follows the same rule: its words are those of tree i
+ * against two virtual vectors, 1 and labels, in the same matrix pass.
+ * Launches, per slab of 4096 rows: the register interpreter (LEAN then FULL build; the scratch-stack kernel for trees deeper than 16
+ * operands and for every tree at var_len > 32) writes the float32 predictions of the n trees into a workspace panel [n][slab]; the matrix
+ * kernel takes the upper-triangle 64 x 64 output blocks, panel rows and labels through LDS to float64 operands.  With fewer than 512
+ * output blocks a workgroup owns one segment and a second kernel adds the partial blocks in segment order; else a workgroup owns the
+ * slab's segments and adds them itself.  No float atomics, everything on the caller's stream, nothing synchronises with the host, the
+ * engine allocates nothing.  workspace: evogp_hip_sr_gram_workspace_bytes(n, data_points) bytes (no zeroing needed): the panel, at most
+ * 8192 x 4096 x 4 B = 128 MB, the flags, and below 512 blocks the partial blocks (at most 64 MB).
+ * Before any launch: EVOGP_E_BADARG for n > 8192, a zero data_points / var_len / pop_size / gp_len, gp_len > 1024, a size >= 2^31,
+ * residuals != 0 with labels == NULL; then EVOGP_E_NULLPTR for a NULL pointer other than labels.  n == 0 is EVOGP_OK and launches nothing
+ * (index, the outputs and the workspace may then be NULL).  The ABI is single-output by construction: there is no out_len. */
+#define EVOGP_GRAM_MAX_TREES 8192
+int evogp_hip_sr_gram_workspace_bytes(unsigned n, unsigned data_points, unsigned long long *bytes);
+int evogp_hip_sr_gram(unsigned n, unsigned data_points, unsigned var_len, unsigned pop_size, unsigned gp_len, const float *value,
+                      const int16_t *type, const int16_t *size, const float *variables, const float *labels /* [data_points] or NULL */,
+                      const int *index /* [n] */, int residuals, double *gram_out /* [n][n] */, double *lin_out /* [n][2] */,
+                      unsigned char *usable_out /* [n] */, void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),

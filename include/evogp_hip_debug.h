@@ -136,6 +136,10 @@ int evogp_hip_debug_lexicase(unsigned long long *device_counters, int stop_after
  * call (default).  Nothing else changes. */
 int evogp_hip_debug_pareto_rank(int stop_after);
 
+/* Measurement hook of evogp_hip_sr_gram (scripts/bench_gram.py).  stages: bit 0 the panel kernels run, bit 1 the matrix kernels run
+ * (stage timing: the outputs of a call that leaves a stage out are unspecified); 3: the whole call (default).  Nothing else changes. */
+int evogp_hip_debug_sr_gram(int stages);
+
 #ifdef __cplusplus
 }
 #endif
