@@ -92,6 +92,8 @@ PROTOTYPES = {
     "evogp_hip_sr_pair_moments": [_u, _u, _u, _u, _u, _u, _vp, _vp, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_gram_workspace_bytes": [_u, _u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_sr_gram": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_neighbours_workspace_bytes": [_u, _u, _u, _u, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_sr_neighbours": [_u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_rank_rows": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_rank_stats_workspace_bytes": [_u, _u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_sr_rank_stats": [_u, _u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -127,6 +129,7 @@ DEBUG_PROTOTYPES = {
     "evogp_hip_debug_tc_program": [_u, _vp, _i],
     "evogp_hip_debug_forget_function_classes": [],
     "evogp_hip_debug_sr_gram": [_i],
+    "evogp_hip_debug_sr_neighbours": [_i],
     "evogp_hip_debug_structural_mutate_given": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_insert_mutate_given": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_debug_point_mutate_given": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

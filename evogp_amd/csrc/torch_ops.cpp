@@ -38,6 +38,7 @@ namespace {
 using at::Tensor;
 using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
 using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+using Tensor5 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>;
 
 constexpr int64_t kMaxStack = EVOGP_MAX_STACK;
 
@@ -1054,6 +1055,44 @@ Tensor3 tree_SR_gram(const Tensor &value, const Tensor &type, const Tensor &size
     return {G, lin, usable};
 }
 
+// (dist2 float64 (n, k), neighbour int32 (n, k), count int32 (n, R), norm float64 (n,), usable bool (n,)): the k nearest trees of every
+// tree of index[0 .. n) by squared distance between prediction vectors and the trees within the radii radius2 float64 (R,), R <= 8
+// (evogp_hip_sr_neighbours); the workspace, the resident float32 panel included, comes from torch's caching allocator
+Tensor5 tree_SR_neighbours(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &variables, const Tensor &index, int64_t k,
+                           const Tensor &radius2) {
+    const char *op = "tree_SR_neighbours";
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(variables.dim() == 2 && variables.size(0) > 0 && variables.size(1) > 0, op,
+                ": variables must be a (data_points, var_len) tensor with data_points > 0 and var_len > 0, but got shape ", variables.sizes());
+    TORCH_CHECK(variables.size(0) <= 0x7FFFFFFF, op, ": variables has too many data points: ", variables.size(0));
+    const int64_t D = variables.size(0), var_len = variables.size(1);
+    check_tensor(variables, {D, var_len}, "variables", f.dev, at::kFloat);
+    TORCH_CHECK(index.dim() == 1 && index.size(0) <= EVOGP_NEIGH_MAX_TREES, op, ": index must be an (n,) tensor with n in [0, ",
+                EVOGP_NEIGH_MAX_TREES, "], but got shape ", index.sizes());
+    const int64_t n = index.size(0);
+    check_tensor(index, {n}, "index", f.dev, at::kInt);
+    TORCH_CHECK(k >= 1 && k <= 16, op, ": k must be in [1, 16], but got ", k);
+    TORCH_CHECK(radius2.dim() == 1 && radius2.size(0) <= 8, op, ": radius2 must be an (R,) tensor with R in [0, 8], but got shape ", radius2.sizes());
+    const int64_t R = radius2.size(0);
+    check_tensor(radius2, {R}, "radius2", f.dev, at::kDouble);
+    TORCH_CHECK(n * ((D + 3) / 4 * 4) <= (int64_t(1) << 29), op, ": index and variables need a resident panel of n * roundup4(data_points) = ",
+                n * ((D + 3) / 4 * 4), " floats, more than 2^29");
+    c10::DeviceGuard guard(f.dev);
+    Tensor dist2 = empty({n, k}, at::kDouble, f.dev), neighbour = empty({n, k}, at::kInt, f.dev), count = empty({n, R}, at::kInt, f.dev);
+    Tensor norm = empty({n}, at::kDouble, f.dev), usable = empty({n}, at::kBool, f.dev);
+    if (n == 0) return {dist2, neighbour, count, norm, usable};   // nothing to launch
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_neighbours_workspace_bytes((unsigned)n, (unsigned)D, (unsigned)k, (unsigned)R, &bytes), op);
+    Tensor ws = empty({(int64_t)bytes}, at::kByte, f.dev);
+    check_rc(evogp_hip_sr_neighbours((unsigned)n, (unsigned)D, (unsigned)var_len, (unsigned)f.pop, (unsigned)f.gp_len, f.value, f.type, f.size,
+                                     variables.data_ptr<float>(), index.data_ptr<int>(), (unsigned)k, (unsigned)R,
+                                     R ? radius2.data_ptr<double>() : nullptr, dist2.data_ptr<double>(), neighbour.data_ptr<int>(),
+                                     R ? count.data_ptr<int>() : nullptr, norm.data_ptr<double>(), (unsigned char *)usable.data_ptr<bool>(),
+                                     ws.data_ptr(), current_stream(f.dev)),
+             op);
+    return {dist2, neighbour, count, norm, usable};
+}
+
 // (r2 int32 (D,), consts int64 (G, 2), status int32 (G,)): the doubled mid-ranks of `values` within the segments of seg_start, and Q, Q2
 // of `payload` (None: of the ranks themselves) per segment (evogp_hip_rank_rows)
 Tensor3 rank_rows(const Tensor &values, const c10::optional<Tensor> &payload, const Tensor &seg_start, int64_t max_segment) {
@@ -1621,6 +1660,8 @@ TORCH_LIBRARY(evogp_hip, m) {
           " Tensor variables, Tensor? labels, Tensor first, Tensor candidates) -> (Tensor own, Tensor moments)");
     m.def("tree_SR_gram(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor? labels, Tensor index,"
           " bool residuals) -> (Tensor gram, Tensor lin, Tensor usable)");
+    m.def("tree_SR_neighbours(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor index, int k, Tensor radius2)"
+          " -> (Tensor dist2, Tensor neighbour, Tensor count, Tensor norm, Tensor usable)");
     m.def("rank_rows(Tensor values, Tensor? payload, Tensor seg_start, int max_segment) -> (Tensor r2, Tensor consts, Tensor status)");
     m.def("tree_SR_rank_stats(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor payload, Tensor seg_start,"
           " int max_segment, int metric, bool want_words, bool want_fused, bool want_scores) -> (Tensor words, Tensor fused, Tensor scores,"
@@ -1702,6 +1743,7 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_pair_moments", &tree_SR_pair_moments);
     m.impl("rank_rows", &rank_rows);
     m.impl("tree_SR_gram", &tree_SR_gram);
+    m.impl("tree_SR_neighbours", &tree_SR_neighbours);
     m.impl("tree_SR_rank_stats", &tree_SR_rank_stats);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);

@@ -139,6 +139,16 @@ def tree_SR_gram(value, node_type, subtree_size, variables, labels, index, resid
     return torch.ops.evogp_hip.tree_SR_gram(value, node_type, subtree_size, variables, labels, index, residuals)
 
 
+def tree_SR_neighbours(value, node_type, subtree_size, variables, index, k, radius2):
+    """``(dist2, neighbour, count, norm, usable)``: ``torch.ops.evogp_hip.tree_SR_neighbours`` (csrc/sr_neigh.hip).  For the trees
+    ``index`` (int32 ``(n,)``, ``n <= 131072``, ``n * roundup4(D) <= 2^29``) of a single-output forest, with ``G`` and its order those of
+    ``tree_SR_gram`` without residuals and ``d2(i, j) = max(0, fma(-2, G_ij, G_ii + G_jj))``: ``dist2`` float64 and ``neighbour`` int32
+    ``(n, k)``, ``k <= 16``, are the k usable positions ``j != i`` smallest by ``(d2, j)`` (``+inf`` / -1 beyond their number, NaN / -1 for an
+    unusable tree); ``count`` int32 ``(n, R)`` the neighbours with ``d2 <= radius2[r]`` (float64 ``(R,)``, ``R <= 8``, squared radii);
+    ``norm`` float64 ``(n,)`` is ``G_ii``; ``usable`` bool ``(n,)``.  The ``(n, n)`` matrix is never stored; bit-identical under any split"""
+    return torch.ops.evogp_hip.tree_SR_neighbours(value, node_type, subtree_size, variables, index, k, radius2)
+
+
 def rank_rows(values, payload, seg_start, max_segment):
     """``(r2, consts, status)``: ``torch.ops.evogp_hip.rank_rows`` (csrc/sr_rank.hip).  ``values`` float32 ``(D,)`` are mid-ranked within
     the contiguous segments ``seg_start`` int32 ``(G + 1,)`` (each of at most ``max_segment <= 8192`` rows): ``r2`` int32 ``(D,)`` is the

@@ -5,6 +5,7 @@ from .classification import Classification
 from .transformation import Transformation
 from .custom_loss import CustomLoss
 from .rank_fitness import RankFitness
+from .niching import NichedFitness
 from .rollout import LinearTrackingEnv, PendulumEnv, RolloutProblem
 
-__all__ = ["BaseProblem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RankFitness", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]
+__all__ = ["BaseProblem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RankFitness", "NichedFitness", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]

@@ -26,6 +26,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     backpropagation       SR_desired_semantics, SR_backprop_match: the values a subtree would have to return; the nearest library member
     pairs                 SR_pair_moments, semantic_distance: the residual inner products of pairs of trees; their distance
     Gram matrix           SR_gram, semantic_cosine, fit_ensemble, ensemble_predict: the inner products of all trees of a set; the stacked ensemble
+    neighbourhoods        SR_neighbours, semantic_novelty: the k nearest trees of every tree and the trees within a radius, without n x n
     midpoint              SR_midpoint_semantics, SR_midpoint_match: the same towards the midpoint of a tree and its mate (no labels)
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
@@ -56,6 +57,8 @@ GENES_MAX = 8  # outputs per tree SR_gene_fitness takes as features (include/evo
 WLOSS_MAX_WEIGHTS = 8  # weight rows per SR_weighted_loss call (include/evogp_hip.h EVOGP_WLOSS_MAX_WEIGHTS)
 PAIR_MAX_CANDIDATES = 16     # candidates per event of SR_pair_moments (include/evogp_hip.h EVOGP_PAIR_MAX_CANDIDATES)
 GRAM_MAX_TREES = 8192        # trees of one SR_gram call (include/evogp_hip.h EVOGP_GRAM_MAX_TREES)
+NEIGH_MAX_TREES = 131072     # trees of one SR_neighbours call (include/evogp_hip.h EVOGP_NEIGH_MAX_TREES)
+NEIGH_MAX_PANEL = 1 << 29    # ... and floats of its resident panel, n * roundup4(D)
 RANK_MAX_SEGMENT = 8192      # rows per segment of SR_rank_stats (include/evogp_hip.h EVOGP_RANK_MAX_SEGMENT)
 RANK_MAX_PAYLOAD = 16384     # largest payload word of SR_rank_stats: a doubled mid-rank within a segment
 RANK_METRICS = {"spearman": 0, "auc": 1}  # include/evogp_hip.h EVOGP_RANK_*
@@ -139,6 +142,15 @@ def _root_safe(lo: Tensor, hi: Tensor, flags: Tensor, max_abs: float) -> Tensor:
     """(pop,) bool from per-node enclosures: the root can not be a NaN, both its bounds are finite and neither exceeds ``max_abs``"""
     lo, hi = lo[:, 0], hi[:, 0]
     return (flags[:, 0] == 0) & torch.isfinite(lo) & torch.isfinite(hi) & (torch.maximum(lo.abs(), hi.abs()) <= max_abs)
+
+
+def novelty_from_dist2(dist2: Tensor) -> Tensor:
+    """(n,) float64 from ``SR_neighbours``' ``dist2`` ``(n, k)``: the mean of ``sqrt(dist2)`` over a row's finite slots; NaN for a row of
+    NaN (an unusable tree), 0 for a row without a finite slot (a tree without a neighbour)"""
+    finite = torch.isfinite(dist2)
+    total = torch.where(finite, torch.sqrt(dist2), torch.zeros_like(dist2)).sum(1)
+    mean = total / finite.sum(1).clamp(min=1)
+    return torch.where(torch.isnan(dist2).any(1), torch.full_like(mean, float("nan")), mean)
 
 
 class Forest:
@@ -704,6 +716,56 @@ class Forest:
         p = members.batch_forward(x)[:, :, 0].to(torch.float64)
         live = (inside & (weights != 0))[:, None]
         return (torch.where(live, p, 0.0) * torch.where(live, weights[:, None], 0.0)).sum(0) + torch.as_tensor(intercept, dtype=torch.float64, device=device)
+
+    # ---- semantic neighbourhoods ---------------------------------------------------------------------
+    def SR_neighbours(self, inputs: Tensor, index: Optional[Tensor] = None, k: int = 15, radii=None):
+        """``(dist2, neighbour, count, norm, usable)``: for every tree of a set, its nearest semantic neighbours and how many trees lie
+        within given radii, WITHOUT the ``(n, n)`` matrix (csrc/sr_neigh.hip, include/evogp_hip.h evogp_hip_sr_neighbours, DESIGN.md
+        3.32).  For the trees ``index`` ``(n,)`` (None: every tree; ``n <= 131072`` and ``n * roundup4(D) <= 2^29``), with ``p_i`` the
+        float32 predictions of ``batch_forward``, ``G_ij = sum_d p_i p_j`` in float64 in ``SR_gram``'s order and ``N_i = G_ii``, the
+        squared distance of two positions is ``d2 = max(0, fma(-2, G_ij, N_i + N_j))``: symmetric bit for bit, and exactly 0 between
+        trees that predict the same bits.  The neighbours of a usable tree are the usable positions ``j != i``.  ``dist2`` float64 and
+        ``neighbour`` int32 ``(n, k)``, ``1 <= k <= 16``: the k nearest by ``(d2, j)``, ascending, ``+inf`` and -1 beyond the number of
+        neighbours, NaN and -1 for an unusable tree (malformed, a prediction that is not finite, an index outside the forest);
+        ``count`` int32 ``(n, R)``: the neighbours within distance ``radii[r]`` (a sequence or tensor of at most 8 DISTANCES, squared
+        here in float64; None: no column), 0 for an unusable tree; ``norm`` float64 ``(n,)``: ``N_i``, the bits of ``SR_gram``'s
+        diagonal without residuals; ``usable`` bool ``(n,)``.  Positions count: a tree listed twice is its own neighbour at distance 0.
+        The same bits from run to run; no host synchronisation; ``ValueError`` before anything is launched for a multi-output forest,
+        a shape or dtype that does not fit, ``k`` or ``n`` out of range, or more than 8, negative or NaN radii given as a sequence."""
+        inputs = self._semantic_rows("SR_neighbours", inputs)
+        device = self.batch_node_value.device
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 16:
+            raise ValueError(f"k should be an integer in 1 .. 16, but got {k!r}")
+        if index is None:
+            index = torch.arange(self.pop_size, dtype=torch.int32, device=device)
+        index = check_tensor(index, device)
+        if index.dtype.is_floating_point or index.dtype == torch.bool:
+            raise ValueError(f"index should hold integers, but got {index.dtype}")
+        if index.dim() != 1 or not 1 <= index.shape[0] <= NEIGH_MAX_TREES:
+            raise ValueError(f"SR_neighbours takes an index of shape (n,) with n in 1 .. {NEIGH_MAX_TREES}, but got {tuple(index.shape)}")
+        if index.shape[0] * ((inputs.shape[0] + 3) // 4 * 4) > NEIGH_MAX_PANEL:
+            raise ValueError(f"SR_neighbours keeps n * roundup4(D) <= 2^29 predictions resident, but got n = {index.shape[0]}, D = {inputs.shape[0]}")
+        if radii is None:
+            radii = torch.zeros(0, dtype=torch.float64, device=device)
+        elif isinstance(radii, Tensor):
+            radii = check_tensor(radii, device)
+            if not radii.dtype.is_floating_point:
+                raise ValueError(f"radii should hold floats, but got {radii.dtype}")
+        else:
+            values = [float(r) for r in radii]
+            if any(not r >= 0.0 for r in values):
+                raise ValueError(f"radii should be distances >= 0, but got {values}")
+            radii = torch.tensor(values, dtype=torch.float64, device=device)
+        if radii.dim() != 1 or radii.shape[0] > 8:
+            raise ValueError(f"radii should be at most 8 distances, shape (R,), but got {tuple(radii.shape)}")
+        radii = radii.to(torch.float64)
+        return torch.ops.evogp_hip.tree_SR_neighbours(*self._tensors(), inputs, index.to(torch.int32).contiguous(), k, (radii * radii).contiguous())
+
+    def semantic_novelty(self, inputs: Tensor, k: int = 15, index: Optional[Tensor] = None) -> Tensor:
+        """``(n,)`` float64: the mean distance of every tree to its ``k`` nearest semantic neighbours (Lehman & Stanley's novelty, the
+        population as its own archive): ``novelty_from_dist2(SR_neighbours(inputs, index, k)[0])``.  NaN for an unusable tree, 0 for a
+        tree without a neighbour.  No host synchronisation."""
+        return novelty_from_dist2(self.SR_neighbours(inputs, index, k)[0])
 
     # ---- rank statistics: Spearman correlation and ROC-AUC ---------------------------------------
     def _rank_call(self, inputs: Tensor, payload: Tensor, segs: RankSegments, metric: str, want: str):

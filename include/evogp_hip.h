@@ -1095,6 +1095,43 @@ int evogp_hip_sr_gram(unsigned n, unsigned data_points, unsigned var_len, unsign
                       const int *index /* [n] */, int residuals, double *gram_out /* [n][n] */, double *lin_out /* [n][2] */,
                       unsigned char *usable_out /* [n] */, void *workspace, evogp_stream_t stream);
 
+/* Semantic neighbourhoods (no counterpart in the reference; csrc/sr_neigh.hip): for every tree of a list of up to
+ * EVOGP_NEIGH_MAX_TREES trees of a single-output forest its k nearest trees by the squared Euclidean distance between float32 prediction
+ * vectors, and how many trees lie within given radii -- what novelty search, fitness sharing, niching and crowding ask of a whole
+ * population -- on the float64 matrix cores and without ever storing the n x n matrix.  For index i32[n]:
+ *     p_i[d]     the float32 prediction of tree index[i] on row d of variables (data_points, var_len): evogp_hip_batch_evaluate's bits
+ *     G_ij     = sum_d (double)p_i[d] * (double)p_j[d]   in THE ORDER of evogp_hip_sr_gram (csrc/sr_gram_order.hpp); no labels, no residuals
+ *     N_i      = G_ii
+ *     d2(i, j) = max(0.0, fma(-2.0, G_ij, N_i + N_j))    (N_i + N_j rounded to nearest)
+ * usable[i] follows the rule of evogp_hip_sr_gram: a malformed tree, a prediction that is not finite, an index outside the forest are
+ * unusable.  d2 is symmetric bit for bit and exactly 0.0 between two trees whose prediction vectors have equal bits (N_i + N_i is exact and
+ * fma(-2, N_i, 2 N_i) is 0): semantic duplicates are neighbours at distance 0.  POSITIONS count: the same tree listed twice gives two
+ * neighbours at distance 0.  The neighbours of a usable i are the positions j != i with usable[j].
+ *     dist2_out[i][0 .. k), neighbour_out[i][0 .. k)   f64, i32: the k smallest neighbours in the total order (d2, j), ascending; slots
+ *                                                      beyond the number of neighbours hold +inf and -1; NaN and -1 for an unusable i
+ *     count_out[i][r], r < n_radii                     i32: the neighbours with d2 <= radius2[r] (f64 device array); 0 for an unusable i
+ *     norm_out[i]                                      f64: N_i, the bits of the diagonal of evogp_hip_sr_gram(residuals = 0); NaN if unusable
+ *     usable_out[i]                                    u8
+ * Launches: the panel kernels of evogp_hip_sr_gram once per slab of 4096 rows into a panel that keeps every row of every tree,
+ * [n][roundup4(data_points)] floats; a kernel over the diagonal 64 x 64 blocks for N_i; the strip kernel, grid (row block, column split):
+ * for each 64-tree column block of its split a workgroup chains v_mfma_f64_16x16x4_f64 over all rows and consumes the 64 x 64 distances in
+ * place (the lists and counts of its 64 rows live in registers), the full square, twice the matrix instructions of the triangle; a merge
+ * kernel over the splits' partial lists.  The result is the same bits from run to run, from stream to stream and under any split of
+ * the work.  No float atomics, everything on the caller's stream, nothing synchronises with the host, the engine allocates nothing.
+ * workspace: evogp_hip_sr_neighbours_workspace_bytes(n, data_points, k, n_radii) bytes (no zeroing needed): the panel (at most 2 GiB),
+ * the flags, N, and the partial lists [n][splits][k] (splits * 64-tree blocks is about 512; one split from 32768 trees on).
+ * Before any launch: EVOGP_E_BADARG for n > EVOGP_NEIGH_MAX_TREES, k outside 1 .. 16, n_radii > 8, n * roundup4(data_points) > 2^29, a
+ * zero data_points / var_len / pop_size / gp_len, gp_len > 1024, a size >= 2^31; then EVOGP_E_NULLPTR for a NULL pointer (radius2 and
+ * count_out may be NULL when n_radii == 0).  n == 0 is EVOGP_OK and launches nothing (index, the outputs and the workspace may then be
+ * NULL).  A separate query set against a reference set is not offered: concatenate the two forests and read the rows wanted. */
+#define EVOGP_NEIGH_MAX_TREES 131072
+int evogp_hip_sr_neighbours_workspace_bytes(unsigned n, unsigned data_points, unsigned k, unsigned n_radii, unsigned long long *bytes);
+int evogp_hip_sr_neighbours(unsigned n, unsigned data_points, unsigned var_len, unsigned pop_size, unsigned gp_len, const float *value,
+                            const int16_t *type, const int16_t *size, const float *variables, const int *index /* [n] */, unsigned k,
+                            unsigned n_radii, const double *radius2 /* [n_radii] */, double *dist2_out /* [n][k] */,
+                            int *neighbour_out /* [n][k] */, int *count_out /* [n][n_radii] */, double *norm_out /* [n] */,
+                            unsigned char *usable_out /* [n] */, void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),

@@ -140,6 +140,13 @@ int evogp_hip_debug_pareto_rank(int stop_after);
  * (stage timing: the outputs of a call that leaves a stage out are unspecified); 3: the whole call (default).  Nothing else changes. */
 int evogp_hip_debug_sr_gram(int stages);
 
+/* Measurement and test hook of evogp_hip_sr_neighbours (scripts/bench_neighbours.py, tests/test_gpu_neigh.py).  The low byte of stages:
+ * bit 0 the panel kernels run, bit 1 the norm kernel, bit 2 the strip kernel, bit 3 the merge kernel (stage timing: the outputs of a call
+ * that leaves a stage out are unspecified); 15: the whole call (default).  stages >> 8: the number of column splits S the strip kernel
+ * is launched with, clamped to the number of 64-tree blocks (0: the host's choice, default); the workspace query follows it.  No
+ * result depends on S. */
+int evogp_hip_debug_sr_neighbours(int stages);
+
 #ifdef __cplusplus
 }
 #endif
