@@ -241,6 +241,12 @@ struct LdsVars {
     int stride;         // rows per variable; a lane's K rows are consecutive
     __device__ inline float get(int k, uint32_t var) const { return base[var * stride + k]; }
 };
+// ONE register tuple [state | inputs of the step] that the caller rewrites between two interpretations (sr_simulate.hip; K = 1)
+template <int VL>
+struct TupleVars {
+    const typename VecOf<VL>::type &v;
+    __device__ inline float get(int, uint32_t var) const { return v[var]; }
+};
 
 template <bool MO, bool LEAN, int K, int DEPTH, class VA>
 __device__ inline void run_chunk(uint32_t opv, uint32_t payv, int n, RegStack<K, DEPTH> &st, const VA &vars, v16f (&outs)[K]) {

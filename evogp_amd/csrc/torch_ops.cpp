@@ -1093,6 +1093,76 @@ Tensor5 tree_SR_neighbours(const Tensor &value, const Tensor &type, const Tensor
     return {dist2, neighbour, count, norm, usable};
 }
 
+// The checked arguments of the two simulation ops (evogp_hip_sr_simulate, evogp_hip_sr_simulation_loss): x0 (B, S), u (B, T, U), the scheme
+// and the three step constants in float32
+struct Simulation {
+    Forest f;
+    int64_t B, T, S, U;
+    float dt, h2, h6;
+    const float *u;
+};
+
+Simulation check_simulation(const char *op, const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &x0, const Tensor &u,
+                            int64_t scheme, double dt) {
+    const Forest f = Forest::infer(value, type, size);
+    TORCH_CHECK(scheme >= EVOGP_SIM_MAP && scheme <= EVOGP_SIM_NARX, op, ": scheme must be 0 (map), 1 (euler), 2 (rk4) or 3 (narx), but got ", scheme);
+    TORCH_CHECK(x0.dim() == 2 && x0.size(0) > 0 && x0.size(1) >= 1 && x0.size(1) <= EVOGP_SIM_MAX_STATE, op,
+                ": x0 must be a (trajectories, state_len) tensor with trajectories > 0 and state_len in [1, ", EVOGP_SIM_MAX_STATE,
+                "], but got shape ", x0.sizes());
+    const int64_t B = x0.size(0), S = x0.size(1);
+    check_tensor(x0, {B, S}, "x0", f.dev, at::kFloat);
+    TORCH_CHECK(u.dim() == 3 && u.size(0) == B && u.size(1) >= 1 && u.size(1) <= 65535 && S + u.size(2) <= 32, op,
+                ": u must be a (trajectories, steps, inputs) tensor with ", B, " trajectories, steps in [1, 65535] and state_len + inputs <= 32,"
+                " but got shape ", u.sizes());
+    const int64_t T = u.size(1), U = u.size(2);
+    check_tensor(u, {B, T, U}, "u", f.dev, at::kFloat);
+    TORCH_CHECK(B * T <= 0x7FFFFFFF, op, ": x0 and u hold too many steps: trajectories * steps = ", B * T);
+    const float dtf = (float)dt;
+    return {f, B, T, S, U, dtf, dtf * 0.5f, dtf / 6.0f, U ? u.data_ptr<float>() : nullptr};
+}
+
+Tensor simulation_workspace(const char *op, const Simulation &s, int64_t scheme, bool with_target) {
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_simulate_workspace_bytes((unsigned)s.f.pop, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S, (unsigned)s.U, (int)scheme,
+                                                   with_target ? 1 : 0, &bytes), op);
+    return empty({(int64_t)bytes}, at::kByte, s.f.dev);
+}
+
+// states float32 (pop, B, T, S): every tree stepped T times from x0 under u (evogp_hip_sr_simulate)
+Tensor tree_SR_simulate(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &x0, const Tensor &u, int64_t scheme, double dt) {
+    const char *op = "tree_SR_simulate";
+    const Simulation s = check_simulation(op, value, type, size, x0, u, scheme, dt);
+    TORCH_CHECK(s.f.pop * s.B * s.T * s.S * 4 <= (int64_t(1) << 31), op, ": the states of ", s.f.pop, " trees, x0 ", x0.sizes(), " and u ", u.sizes(),
+                " take more than 2 GiB: simulate a slice of the forest, or take tree_SR_simulation_loss");
+    c10::DeviceGuard guard(s.f.dev);
+    Tensor states = empty({s.f.pop, s.B, s.T, s.S}, at::kFloat, s.f.dev);
+    Tensor ws = simulation_workspace(op, s, scheme, false);
+    check_rc(evogp_hip_sr_simulate((unsigned)s.f.pop, (unsigned)s.f.gp_len, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S, (unsigned)s.U, (int)scheme,
+                                   s.dt, s.h2, s.h6, s.f.value, s.f.type, s.f.size, x0.data_ptr<float>(), s.u, states.data_ptr<float>(),
+                                   ws.data_ptr(), current_stream(s.f.dev)),
+             op);
+    return states;
+}
+
+// loss float64 (pop, S) ((pop, 1) for narx): the mean squared distance of the simulated states from target (B, T, S) ((B, T) for narx),
+// without the (pop, B, T, S) array (evogp_hip_sr_simulation_loss)
+Tensor tree_SR_simulation_loss(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &x0, const Tensor &u, const Tensor &target,
+                               int64_t scheme, double dt) {
+    const char *op = "tree_SR_simulation_loss";
+    const Simulation s = check_simulation(op, value, type, size, x0, u, scheme, dt);
+    const bool narx = scheme == EVOGP_SIM_NARX;
+    if (narx) check_tensor(target, {s.B, s.T}, "target", s.f.dev, at::kFloat);
+    else check_tensor(target, {s.B, s.T, s.S}, "target", s.f.dev, at::kFloat);
+    c10::DeviceGuard guard(s.f.dev);
+    Tensor loss = empty({s.f.pop, narx ? 1 : s.S}, at::kDouble, s.f.dev);
+    Tensor ws = simulation_workspace(op, s, scheme, true);
+    check_rc(evogp_hip_sr_simulation_loss((unsigned)s.f.pop, (unsigned)s.f.gp_len, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S, (unsigned)s.U,
+                                          (int)scheme, s.dt, s.h2, s.h6, s.f.value, s.f.type, s.f.size, x0.data_ptr<float>(), s.u,
+                                          target.data_ptr<float>(), loss.data_ptr<double>(), ws.data_ptr(), current_stream(s.f.dev)),
+             op);
+    return loss;
+}
+
 // (r2 int32 (D,), consts int64 (G, 2), status int32 (G,)): the doubled mid-ranks of `values` within the segments of seg_start, and Q, Q2
 // of `payload` (None: of the ranks themselves) per segment (evogp_hip_rank_rows)
 Tensor3 rank_rows(const Tensor &values, const c10::optional<Tensor> &payload, const Tensor &seg_start, int64_t max_segment) {
@@ -1662,6 +1732,9 @@ TORCH_LIBRARY(evogp_hip, m) {
           " bool residuals) -> (Tensor gram, Tensor lin, Tensor usable)");
     m.def("tree_SR_neighbours(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor index, int k, Tensor radius2)"
           " -> (Tensor dist2, Tensor neighbour, Tensor count, Tensor norm, Tensor usable)");
+    m.def("tree_SR_simulate(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, int scheme, float dt) -> Tensor");
+    m.def("tree_SR_simulation_loss(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, Tensor target, int scheme,"
+          " float dt) -> Tensor");
     m.def("rank_rows(Tensor values, Tensor? payload, Tensor seg_start, int max_segment) -> (Tensor r2, Tensor consts, Tensor status)");
     m.def("tree_SR_rank_stats(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor payload, Tensor seg_start,"
           " int max_segment, int metric, bool want_words, bool want_fused, bool want_scores) -> (Tensor words, Tensor fused, Tensor scores,"
@@ -1744,6 +1817,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("rank_rows", &rank_rows);
     m.impl("tree_SR_gram", &tree_SR_gram);
     m.impl("tree_SR_neighbours", &tree_SR_neighbours);
+    m.impl("tree_SR_simulate", &tree_SR_simulate);
+    m.impl("tree_SR_simulation_loss", &tree_SR_simulation_loss);
     m.impl("tree_SR_rank_stats", &tree_SR_rank_stats);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);

@@ -149,6 +149,23 @@ def tree_SR_neighbours(value, node_type, subtree_size, variables, index, k, radi
     return torch.ops.evogp_hip.tree_SR_neighbours(value, node_type, subtree_size, variables, index, k, radius2)
 
 
+def tree_SR_simulate(value, node_type, subtree_size, x0, u, scheme, dt):
+    """``states`` float32 ``(pop, B, T, S)``: ``torch.ops.evogp_hip.tree_SR_simulate`` (csrc/sr_simulate.hip).  Every tree of a forest with
+    ``input_len = S + U`` and ``output_len = S`` (``scheme`` 3, narx: ``output_len = 1``, S lags) is stepped T times from ``x0`` float32
+    ``(B, S)`` under ``u`` float32 ``(B, T, U)`` inside one kernel; ``scheme`` 0 map, 1 euler, 2 rk4, 3 narx; ``dt`` is rounded to float32.
+    A trajectory whose new state is not finite is dead: NaN from that step on; a malformed tree is NaN everywhere.  The bits are those
+    of stepping ``tree_evaluate`` with the float32 formulas of include/evogp_hip.h"""
+    return torch.ops.evogp_hip.tree_SR_simulate(value, node_type, subtree_size, x0, u, scheme, dt)
+
+
+def tree_SR_simulation_loss(value, node_type, subtree_size, x0, u, target, scheme, dt):
+    """``loss`` float64 ``(pop, S)`` (``(pop, 1)`` for narx): ``torch.ops.evogp_hip.tree_SR_simulation_loss`` (csrc/sr_simulate.hip).  The
+    mean over trajectories and steps of ``((double)x_s - (double)target_s)^2`` of ``tree_SR_simulate``'s states against ``target`` float32
+    ``(B, T, S)`` (``(B, T)`` for narx), in a fixed order, without the ``(pop, B, T, S)`` array; NaN for a tree with a dead trajectory and
+    for a malformed tree.  The same bits from run to run and whatever population the tree stands in"""
+    return torch.ops.evogp_hip.tree_SR_simulation_loss(value, node_type, subtree_size, x0, u, target, scheme, dt)
+
+
 def rank_rows(values, payload, seg_start, max_segment):
     """``(r2, consts, status)``: ``torch.ops.evogp_hip.rank_rows`` (csrc/sr_rank.hip).  ``values`` float32 ``(D,)`` are mid-ranked within
     the contiguous segments ``seg_start`` int32 ``(G + 1,)`` (each of at most ``max_segment <= 8192`` rows): ``r2`` int32 ``(D,)`` is the

@@ -6,6 +6,7 @@ from .transformation import Transformation
 from .custom_loss import CustomLoss
 from .rank_fitness import RankFitness
 from .niching import NichedFitness
+from .dynamics import DynamicalSystem
 from .rollout import LinearTrackingEnv, PendulumEnv, RolloutProblem
 
-__all__ = ["BaseProblem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RankFitness", "NichedFitness", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]
+__all__ = ["BaseProblem", "DynamicalSystem", "SymbolicRegression", "Classification", "Transformation", "CustomLoss", "RankFitness", "NichedFitness", "RolloutProblem", "LinearTrackingEnv", "PendulumEnv"]

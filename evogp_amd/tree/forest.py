@@ -27,6 +27,7 @@ rest has no counterpart in the reference.  Every heavy method is one call into `
     pairs                 SR_pair_moments, semantic_distance: the residual inner products of pairs of trees; their distance
     Gram matrix           SR_gram, semantic_cosine, fit_ensemble, ensemble_predict: the inner products of all trees of a set; the stacked ensemble
     neighbourhoods        SR_neighbours, semantic_novelty: the k nearest trees of every tree and the trees within a radius, without n x n
+    simulation            SR_simulate, SR_simulation_loss: the tree as a recurrence or an ODE stepped in one kernel; its free-run loss
     midpoint              SR_midpoint_semantics, SR_midpoint_match: the same towards the midpoint of a tree and its mate (no labels)
     dimensions            SR_dimensions, dimension_mask: the physical unit of every subtree; the trees that can be made consistent
     structure             SR_structure, structure_mask, complexity: depth, weighted complexity, operand and nesting limits
@@ -59,7 +60,9 @@ PAIR_MAX_CANDIDATES = 16     # candidates per event of SR_pair_moments (include/
 GRAM_MAX_TREES = 8192        # trees of one SR_gram call (include/evogp_hip.h EVOGP_GRAM_MAX_TREES)
 NEIGH_MAX_TREES = 131072     # trees of one SR_neighbours call (include/evogp_hip.h EVOGP_NEIGH_MAX_TREES)
 NEIGH_MAX_PANEL = 1 << 29    # ... and floats of its resident panel, n * roundup4(D)
-RANK_MAX_SEGMENT = 8192      # rows per segment of SR_rank_stats (include/evogp_hip.h EVOGP_RANK_MAX_SEGMENT)
+SIM_MAX_STATE = 8            # state variables of SR_simulate (include/evogp_hip.h EVOGP_SIM_MAX_STATE)
+SIM_SCHEMES = {"map": 0, "euler": 1, "rk4": 2, "narx": 3}  # include/evogp_hip.h EVOGP_SIM_*
+RANK_MAX_SEGMENT = 8192     # rows per segment of SR_rank_stats (include/evogp_hip.h EVOGP_RANK_MAX_SEGMENT)
 RANK_MAX_PAYLOAD = 16384     # largest payload word of SR_rank_stats: a doubled mid-rank within a segment
 RANK_METRICS = {"spearman": 0, "auc": 1}  # include/evogp_hip.h EVOGP_RANK_*
 BACKPROP_MAX_LIBRARY = 1024  # library members per SR_backprop_match call (include/evogp_hip.h EVOGP_BACKPROP_MAX_LIB)
@@ -766,6 +769,58 @@ class Forest:
         population as its own archive): ``novelty_from_dist2(SR_neighbours(inputs, index, k)[0])``.  NaN for an unusable tree, 0 for a
         tree without a neighbour.  No host synchronisation."""
         return novelty_from_dist2(self.SR_neighbours(inputs, index, k)[0])
+
+    # ---- simulation: the tree as the law of motion ---------------------------------------------------
+    def _simulation_args(self, what: str, x0: Tensor, u: Optional[Tensor], steps: Optional[int], scheme: str):
+        """``(x0, u, scheme id)`` as the simulation ops take them, or ``ValueError`` before anything is launched"""
+        if scheme not in SIM_SCHEMES:
+            raise ValueError(f"scheme should be one of {list(SIM_SCHEMES)}, but got {scheme!r}")
+        device = self.batch_node_value.device
+        x0 = check_tensor(x0, device)
+        if x0.dim() != 2 or x0.shape[0] == 0 or not 1 <= x0.shape[1] <= SIM_MAX_STATE:
+            raise ValueError(f"{what} takes x0 of shape (trajectories, state_len) with state_len in 1 .. {SIM_MAX_STATE}, but got {tuple(x0.shape)}")
+        B, S = x0.shape
+        outs = 1 if scheme == "narx" else S
+        if self.output_len != outs:
+            raise ValueError(f"{what} with scheme {scheme!r} and {S} state variables needs a forest with {outs} outputs, but output_len is {self.output_len}")
+        U = self.input_len - S
+        if U < 0 or self.input_len > 32:
+            raise ValueError(f"{what} needs state_len <= input_len <= 32, but state_len is {S} and input_len is {self.input_len}")
+        if u is None:
+            if U or steps is None:
+                raise ValueError(f"{what} needs u of shape ({B}, steps, {U})" if U else f"{what} needs steps when u is None")
+            u = torch.zeros((B, int(steps), 0), dtype=torch.float32, device=device)
+        u = check_tensor(u, device)
+        if u.dim() != 3 or u.shape[0] != B or u.shape[2] != U or not 1 <= u.shape[1] <= 65535 or (steps is not None and u.shape[1] != steps):
+            raise ValueError(f"{what} takes u of shape ({B}, steps, {U}) with steps in 1 .. 65535, but got {tuple(u.shape)} (steps = {steps})")
+        return x0.contiguous().to(torch.float32), u.contiguous().to(torch.float32), SIM_SCHEMES[scheme]
+
+    def SR_simulate(self, x0: Tensor, u: Optional[Tensor] = None, steps: Optional[int] = None, scheme: str = "euler", dt: float = 1.0) -> Tensor:
+        """``states`` float32 ``(pop, B, steps, S)``: every tree run as the law of motion of a dynamical system, fed its own output for
+        ``steps`` steps inside ONE kernel (csrc/sr_simulate.hip, include/evogp_hip.h evogp_hip_sr_simulate).  The forest
+        has ``input_len = S + U`` and ``output_len = S``: variables ``0 .. S-1`` read the state, the others the exogenous inputs ``u``
+        ``(B, steps, U)`` of the current step (None when ``U = 0``; then ``steps`` is required).  ``x0`` ``(B, S)`` starts the ``B``
+        trajectories.  ``scheme``: ``"map"`` ``x+ = f(x, u)``; ``"euler"`` ``x+ = x + dt f(x, u)``; ``"rk4"`` the classical four stages
+        with ``u`` held over the step; ``"narx"`` a single-output forest whose state is its last ``S`` outputs, ``x+ = (f(x, u), x[0], ...,
+        x[S-2])``.  Float32, every operation rounded separately: the bits of stepping ``forward`` by hand.  A trajectory whose new state
+        is not finite is dead and NaN from that step on; a malformed tree is NaN everywhere.  No host synchronisation; ``ValueError``
+        before anything is launched for shapes that do not fit; more than 2 GiB of states is an error of the op."""
+        x0, u, sid = self._simulation_args("SR_simulate", x0, u, steps, scheme)
+        return torch.ops.evogp_hip.tree_SR_simulate(*self._tensors(), x0, u, sid, float(dt))
+
+    def SR_simulation_loss(self, x0: Tensor, u: Optional[Tensor], target: Tensor, scheme: str = "euler", dt: float = 1.0) -> Tensor:
+        """``loss`` float64 ``(pop, S)`` (``(pop, 1)`` for ``"narx"``): the mean squared distance of ``SR_simulate``'s states from
+        ``target`` ``(B, steps, S)`` (``(B, steps)`` for ``"narx"``, which scores the newest output alone), per state variable, summed in
+        float64 in an order fixed by ``(B, steps)`` alone and never storing the ``(pop, B, steps, S)`` states: the same bits from run to
+        run and whatever population the tree stands in.  NaN (every column) for a tree with a dead trajectory and for a malformed tree."""
+        target = check_tensor(target, self.batch_node_value.device)
+        if target.dim() < 2:
+            raise ValueError(f"SR_simulation_loss takes a target of shape (trajectories, steps[, state_len]), but got {tuple(target.shape)}")
+        x0, u, sid = self._simulation_args("SR_simulation_loss", x0, u, int(target.shape[1]), scheme)
+        want = (x0.shape[0], u.shape[1]) if scheme == "narx" else (x0.shape[0], u.shape[1], x0.shape[1])
+        if tuple(target.shape) != want:
+            raise ValueError(f"SR_simulation_loss with scheme {scheme!r} takes a target of shape {want}, but got {tuple(target.shape)}")
+        return torch.ops.evogp_hip.tree_SR_simulation_loss(*self._tensors(), x0, u, target.contiguous().to(torch.float32), sid, float(dt))
 
     # ---- rank statistics: Spearman correlation and ROC-AUC ---------------------------------------
     def _rank_call(self, inputs: Tensor, payload: Tensor, segs: RankSegments, metric: str, want: str):

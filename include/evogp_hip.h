@@ -1132,6 +1132,52 @@ int evogp_hip_sr_neighbours(unsigned n, unsigned data_points, unsigned var_len, 
                             int *neighbour_out /* [n][k] */, int *count_out /* [n][n_radii] */, double *norm_out /* [n] */,
                             unsigned char *usable_out /* [n] */, void *workspace, evogp_stream_t stream);
 
+/* Simulation fitness (no counterpart in the reference; csrc/sr_simulate.hip): the tree is the law of motion of a
+ * recurrence or an ODE, fed its own output for T steps inside one kernel.  THE DEFINITION (tests/simulate_ref.py restates it):
+ * a forest with var_len = S + U and out_len = S, 1 <= S <= EVOGP_SIM_MAX_STATE, S + U <= 32; variables 0 .. S-1 read the state, variables
+ * S .. S+U-1 the exogenous inputs of the current step.  x0 f32 (B, S), u f32 (B, T, U) (U = 0 allowed; u may then be NULL), target f32
+ * (B, T, S).  f(x, u) is the tree's output vector exactly as evogp_hip_evaluate defines it: the root value for S = 1, the accumulating OUT
+ * nodes for S > 1.  The state after step t (t = 0 .. T-1) uses u[:, t] and is compared with target[:, t]; it is computed in float32, every
+ * operation rounded separately in the order written, no contraction:
+ *     EVOGP_SIM_MAP     x+ = f(x, u)
+ *     EVOGP_SIM_EULER   x+ = x + dt * f(x, u)
+ *     EVOGP_SIM_RK4     k1 = f(x, u), k2 = f(x + h2 * k1, u), k3 = f(x + h2 * k2, u), k4 = f(x + dt * k3, u),
+ *                       x+ = x + h6 * (((k1 + 2 * k2) + 2 * k3) + k4); h2 = fl(dt * 0.5) and h6 = fl(dt / 6) come from the caller, computed
+ *                       once in float32; u is held over the step
+ *     EVOGP_SIM_NARX    the forest has out_len = 1 and var_len = p + U (state_len = p <= 8: the last p outputs),
+ *                       x+ = (f(x, u), x[0], ..., x[p-2]); target is (B, T) and only component 0 is scored
+ * A trajectory DIES at the first step whose new state has a component that is not finite; from that step on its materialised states are
+ * NaN.  A tree's loss is NaN -- every column -- when one of its trajectories is dead or the tree is malformed (the rule of
+ * evogp_hip_sr_linear_scaling); a malformed tree's states are all NaN.  (max, the comparisons and IF can swallow a NaN INSIDE a tree: a
+ * trajectory whose states stay finite stays alive.)
+ *   evogp_hip_sr_simulate          states_out f32 [pop][B][T][state_len]
+ *   evogp_hip_sr_simulation_loss   loss_out f64 [pop][SC], SC = state_len (1 for NARX): the sum over b and t of
+ *                                  ((double)x_s - (double)target_s)^2, every operation in float64, divided by (double)B * (double)T.
+ *                                  The order is fixed by (B, T) alone: a lane adds the terms of its trajectory in time order, the 64
+ *                                  trajectories of a tile are added by the fixed butterfly, the tiles in index order.  The result is the same
+ *                                  bits from run to run and whatever population the tree stands in; no (pop, B, T, S) array is stored.
+ * Launches (caller's stream, no host synchronisation, no float atomics): a transposition of u and target to [t][column][b]; the register
+ * interpreter with time as its inner loop (a tree is classified and decoded once, not T times), its LEAN build over every tree and its
+ * FULL build over the trees that use a transcendental function or pow; a stack interpreter over the trees too deep for 16 registers.
+ * workspace: evogp_hip_sr_simulate_workspace_bytes(...) bytes (no zeroing needed): the transposed arrays and one word per tree.
+ * Before any launch: EVOGP_E_BADARG for a zero size, gp_len > 1024, steps > 65535, state_len > 8, state_len + input_len > 32, a scheme
+ * outside 0 .. 3, trajectories * steps >= 2^31, pop_size >= 2^31, states_out above 2 GiB; then EVOGP_E_NULLPTR. */
+#define EVOGP_SIM_MAX_STATE 8
+#define EVOGP_SIM_MAP 0
+#define EVOGP_SIM_EULER 1
+#define EVOGP_SIM_RK4 2
+#define EVOGP_SIM_NARX 3
+int evogp_hip_sr_simulate_workspace_bytes(unsigned pop_size, unsigned trajectories, unsigned steps, unsigned state_len, unsigned input_len,
+                                          int scheme, int with_target, unsigned long long *bytes);
+int evogp_hip_sr_simulate(unsigned pop_size, unsigned gp_len, unsigned trajectories, unsigned steps, unsigned state_len, unsigned input_len,
+                          int scheme, float dt, float h2, float h6, const float *value, const int16_t *type, const int16_t *size,
+                          const float *x0 /* [B][S] */, const float *u /* [B][T][U] */, float *states_out, void *workspace,
+                          evogp_stream_t stream);
+int evogp_hip_sr_simulation_loss(unsigned pop_size, unsigned gp_len, unsigned trajectories, unsigned steps, unsigned state_len,
+                                 unsigned input_len, int scheme, float dt, float h2, float h6, const float *value, const int16_t *type,
+                                 const int16_t *size, const float *x0, const float *u, const float *target, double *loss_out,
+                                 void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
