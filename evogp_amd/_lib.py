@@ -97,6 +97,9 @@ PROTOTYPES = {
     "evogp_hip_sr_simulate_workspace_bytes": [_u, _u, _u, _u, _u, _i, _i, C.POINTER(C.c_ulonglong)],
     "evogp_hip_sr_simulate": [_u, _u, _u, _u, _u, _u, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_simulation_loss": [_u, _u, _u, _u, _u, _u, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_simulation_sens_workspace_bytes": [_u, _u, _u, _u, _u, _u, _i, _i, C.POINTER(C.c_ulonglong)],
+    "evogp_hip_sr_simulation_sensitivities": [_u, _u, _u, _u, _u, _u, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "evogp_hip_sr_simulation_normal_eq": [_u, _u, _u, _u, _u, _u, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_rank_rows": [_u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "evogp_hip_sr_rank_stats_workspace_bytes": [_u, _u, C.POINTER(C.c_ulonglong)],
     "evogp_hip_sr_rank_stats": [_u, _u, _u, _u, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],

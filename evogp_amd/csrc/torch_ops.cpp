@@ -1163,6 +1163,56 @@ Tensor tree_SR_simulation_loss(const Tensor &value, const Tensor &type, const Te
     return loss;
 }
 
+Tensor sensitivity_workspace(const char *op, const Simulation &s, int64_t scheme, bool with_target) {
+    unsigned long long bytes = 0;
+    check_rc(evogp_hip_sr_simulation_sens_workspace_bytes((unsigned)s.f.pop, (unsigned)s.f.gp_len, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S,
+                                                          (unsigned)s.U, (int)scheme, with_target ? 1 : 0, &bytes), op);
+    return empty({(int64_t)bytes}, at::kByte, s.f.dev);
+}
+
+// (states float32 (pop, B, T, S), sens float32 (pop, B, T, S, 8)): tree_SR_simulate's states and their derivatives in each tree's first 8
+// constants (evogp_hip_sr_simulation_sensitivities)
+std::tuple<Tensor, Tensor> tree_SR_simulation_sensitivities(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &x0,
+                                                            const Tensor &u, int64_t scheme, double dt) {
+    const char *op = "tree_SR_simulation_sensitivities";
+    const Simulation s = check_simulation(op, value, type, size, x0, u, scheme, dt);
+    TORCH_CHECK(s.f.pop * s.B * s.T * s.S * EVOGP_LM_MAX_CONSTS * 4 <= (int64_t(1) << 31), op, ": the sensitivities of ", s.f.pop, " trees, x0 ",
+                x0.sizes(), " and u ", u.sizes(), " take more than 2 GiB: take a slice of the forest, or tree_SR_simulation_normal_eq");
+    c10::DeviceGuard guard(s.f.dev);
+    Tensor states = empty({s.f.pop, s.B, s.T, s.S}, at::kFloat, s.f.dev);
+    Tensor sens = empty({s.f.pop, s.B, s.T, s.S, EVOGP_LM_MAX_CONSTS}, at::kFloat, s.f.dev);
+    Tensor ws = sensitivity_workspace(op, s, scheme, false);
+    check_rc(evogp_hip_sr_simulation_sensitivities((unsigned)s.f.pop, (unsigned)s.f.gp_len, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S,
+                                                   (unsigned)s.U, (int)scheme, s.dt, s.h2, s.h6, s.f.value, s.f.type, s.f.size,
+                                                   x0.data_ptr<float>(), s.u, states.data_ptr<float>(), sens.data_ptr<float>(), ws.data_ptr(),
+                                                   current_stream(s.f.dev)),
+             op);
+    return {states, sens};
+}
+
+// (loss64 float64 (pop, SC), loss float32 (pop,), normal float32 (pop, 44)): tree_SR_simulation_loss's loss, its state_weight-ed sum and
+// the Gauss-Newton normal equations of that sum in each tree's first 8 constants (evogp_hip_sr_simulation_normal_eq)
+Tensor3 tree_SR_simulation_normal_eq(const Tensor &value, const Tensor &type, const Tensor &size, const Tensor &x0, const Tensor &u,
+                                     const Tensor &target, const Tensor &state_weight, int64_t scheme, double dt) {
+    const char *op = "tree_SR_simulation_normal_eq";
+    const Simulation s = check_simulation(op, value, type, size, x0, u, scheme, dt);
+    const bool narx = scheme == EVOGP_SIM_NARX;
+    const int64_t SC = narx ? 1 : s.S;
+    if (narx) check_tensor(target, {s.B, s.T}, "target", s.f.dev, at::kFloat);
+    else check_tensor(target, {s.B, s.T, s.S}, "target", s.f.dev, at::kFloat);
+    check_tensor(state_weight, {SC}, "state_weight", s.f.dev, at::kFloat);
+    c10::DeviceGuard guard(s.f.dev);
+    Tensor loss64 = empty({s.f.pop, SC}, at::kDouble, s.f.dev), loss = empty({s.f.pop}, at::kFloat, s.f.dev);
+    Tensor normal = empty({s.f.pop, EVOGP_LM_NORMAL_WORDS}, at::kFloat, s.f.dev);
+    Tensor ws = sensitivity_workspace(op, s, scheme, true);
+    check_rc(evogp_hip_sr_simulation_normal_eq((unsigned)s.f.pop, (unsigned)s.f.gp_len, (unsigned)s.B, (unsigned)s.T, (unsigned)s.S, (unsigned)s.U,
+                                               (int)scheme, s.dt, s.h2, s.h6, s.f.value, s.f.type, s.f.size, x0.data_ptr<float>(), s.u,
+                                               target.data_ptr<float>(), state_weight.data_ptr<float>(), loss64.data_ptr<double>(),
+                                               loss.data_ptr<float>(), normal.data_ptr<float>(), ws.data_ptr(), current_stream(s.f.dev)),
+             op);
+    return {loss64, loss, normal};
+}
+
 // (r2 int32 (D,), consts int64 (G, 2), status int32 (G,)): the doubled mid-ranks of `values` within the segments of seg_start, and Q, Q2
 // of `payload` (None: of the ranks themselves) per segment (evogp_hip_rank_rows)
 Tensor3 rank_rows(const Tensor &values, const c10::optional<Tensor> &payload, const Tensor &seg_start, int64_t max_segment) {
@@ -1735,6 +1785,10 @@ TORCH_LIBRARY(evogp_hip, m) {
     m.def("tree_SR_simulate(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, int scheme, float dt) -> Tensor");
     m.def("tree_SR_simulation_loss(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, Tensor target, int scheme,"
           " float dt) -> Tensor");
+    m.def("tree_SR_simulation_sensitivities(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, int scheme, float dt)"
+          " -> (Tensor states, Tensor sens)");
+    m.def("tree_SR_simulation_normal_eq(Tensor value, Tensor node_type, Tensor subtree_size, Tensor x0, Tensor u, Tensor target,"
+          " Tensor state_weight, int scheme, float dt) -> (Tensor loss64, Tensor loss, Tensor normal)");
     m.def("rank_rows(Tensor values, Tensor? payload, Tensor seg_start, int max_segment) -> (Tensor r2, Tensor consts, Tensor status)");
     m.def("tree_SR_rank_stats(Tensor value, Tensor node_type, Tensor subtree_size, Tensor variables, Tensor payload, Tensor seg_start,"
           " int max_segment, int metric, bool want_words, bool want_fused, bool want_scores) -> (Tensor words, Tensor fused, Tensor scores,"
@@ -1819,6 +1873,8 @@ TORCH_LIBRARY_IMPL(evogp_hip, CUDA, m) {
     m.impl("tree_SR_neighbours", &tree_SR_neighbours);
     m.impl("tree_SR_simulate", &tree_SR_simulate);
     m.impl("tree_SR_simulation_loss", &tree_SR_simulation_loss);
+    m.impl("tree_SR_simulation_sensitivities", &tree_SR_simulation_sensitivities);
+    m.impl("tree_SR_simulation_normal_eq", &tree_SR_simulation_normal_eq);
     m.impl("tree_SR_rank_stats", &tree_SR_rank_stats);
     m.impl("tree_SR_linear_scaling", &tree_SR_linear_scaling);
     m.impl("tree_SR_weighted_loss", &tree_SR_weighted_loss);

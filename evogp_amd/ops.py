@@ -166,6 +166,22 @@ def tree_SR_simulation_loss(value, node_type, subtree_size, x0, u, target, schem
     return torch.ops.evogp_hip.tree_SR_simulation_loss(value, node_type, subtree_size, x0, u, target, scheme, dt)
 
 
+def tree_SR_simulation_sensitivities(value, node_type, subtree_size, x0, u, scheme, dt):
+    """``(states, sens)``: ``torch.ops.evogp_hip.tree_SR_simulation_sensitivities`` (csrc/sr_simulate_sens.hip).  ``states`` float32
+    ``(pop, B, T, S)`` are ``tree_SR_simulate``'s bits; ``sens`` float32 ``(pop, B, T, S, 8)`` their derivatives in each tree's first 8
+    CONST nodes in prefix order, carried through time by dual numbers inside the kernel (include/evogp_hip.h has the rule).  Slots past
+    the tree's constants are exactly 0; every slot is NaN from the step a trajectory dies and for a malformed tree"""
+    return torch.ops.evogp_hip.tree_SR_simulation_sensitivities(value, node_type, subtree_size, x0, u, scheme, dt)
+
+
+def tree_SR_simulation_normal_eq(value, node_type, subtree_size, x0, u, target, state_weight, scheme, dt):
+    """``(loss64, loss, normal)``: ``torch.ops.evogp_hip.tree_SR_simulation_normal_eq`` (csrc/sr_simulate_sens.hip).  ``loss64`` float64
+    ``(pop, SC)`` is ``tree_SR_simulation_loss``'s, bit for bit; ``loss`` float32 ``(pop,)`` its sum weighted by ``state_weight`` float32
+    ``(SC,)``; ``normal`` float32 ``(pop, 44)`` the Gauss-Newton model of that sum in the tree's first 8 constants, in the layout
+    ``tree_SR_lm_step`` takes.  A tree with a dead trajectory or a malformed tree: NaN losses, a zero row.  No ``(pop, B, T, S, 8)`` array"""
+    return torch.ops.evogp_hip.tree_SR_simulation_normal_eq(value, node_type, subtree_size, x0, u, target, state_weight, scheme, dt)
+
+
 def rank_rows(values, payload, seg_start, max_segment):
     """``(r2, consts, status)``: ``torch.ops.evogp_hip.rank_rows`` (csrc/sr_rank.hip).  ``values`` float32 ``(D,)`` are mid-ranked within
     the contiguous segments ``seg_start`` int32 ``(G + 1,)`` (each of at most ``max_segment <= 8192`` rows): ``r2`` int32 ``(D,)`` is the

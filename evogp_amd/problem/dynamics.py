@@ -29,7 +29,12 @@ class DynamicalSystem(BaseProblem):
     ``"map"``, ``"euler"``, ``"rk4"``, ``"narx"``, ``dt`` the step; ``state_scale``: ``(S,)`` positive scales (one for ``"narx"``), default
     the per-state variance of ``target`` (1 where that is 0).  The forest has ``input_len = S + U`` and ``output_len = S`` (1 for narx)."""
 
-    def __init__(self, x0: Tensor, u: Optional[Tensor], target: Tensor, scheme: str = "euler", dt: float = 1.0, state_scale=None):
+    def __init__(self, x0: Tensor, u: Optional[Tensor], target: Tensor, scheme: str = "euler", dt: float = 1.0, state_scale=None,
+                 const_opt_steps: int = 0):
+        """``const_opt_steps`` > 0: ``optimize`` -- which ``StandardPipeline`` calls in front of every evaluation -- tunes every tree's
+        constants by that many Levenberg-Marquardt steps under this fitness (``optimize_constants``); the tuned forest is scored and bred"""
+        assert const_opt_steps >= 0, f"const_opt_steps should be >= 0, but got {const_opt_steps}"
+        self.const_opt_steps = int(const_opt_steps)
         self.x0, self.u, self.target, self.scheme, self.dt = x0, u, target, scheme, float(dt)
         if x0.dim() != 2 or target.dim() != (2 if scheme == "narx" else 3) or target.shape[0] != x0.shape[0]:
             raise ValueError(f"x0 should be (B, S) and target (B, T{'' if scheme == 'narx' else ', S'}), but got {tuple(x0.shape)} and {tuple(target.shape)}")
@@ -44,7 +49,7 @@ class DynamicalSystem(BaseProblem):
 
     @staticmethod
     def from_series(series: Tensor, inputs: Optional[Tensor], window: int, stride: int = 1, scheme: str = "euler", dt: float = 1.0,
-                    state_scale=None, lags: int = 1) -> "DynamicalSystem":
+                    state_scale=None, lags: int = 1, const_opt_steps: int = 0) -> "DynamicalSystem":
         """Multiple shooting: ONE long recording ``series`` ``(N, S)`` (``(N,)`` for narx) with its inputs ``(N, U)`` or None is cut into
         overlapping windows of ``window`` steps, one every ``stride`` samples; each window starts a trajectory from the measured state
         and is compared with the ``window`` samples that follow.  (The windows are also what fills the 64 lanes of the kernel's tiles.)
@@ -64,7 +69,7 @@ class DynamicalSystem(BaseProblem):
             x0 = series[starts]
         target = series[steps + 1]
         u = None if inputs is None else inputs[steps]
-        return DynamicalSystem(x0.contiguous(), u, target.contiguous(), scheme, dt, state_scale)
+        return DynamicalSystem(x0.contiguous(), u, target.contiguous(), scheme, dt, state_scale, const_opt_steps=const_opt_steps)
 
     def losses(self, forest: Forest) -> Tensor:
         """``(pop, S)`` float64: the per-state free-run mean squared errors, NaN where the simulation died"""
@@ -72,6 +77,16 @@ class DynamicalSystem(BaseProblem):
 
     def evaluate(self, forest: Forest) -> Tensor:
         return simulation_fitness(self.losses(forest), self.state_scale)
+
+    def optimize_constants(self, forest: Forest, steps: int = 3, damping: float = 1e-3):
+        """``(forest, loss)``: ``Forest.optimize_simulation_constants`` on this problem's data with ``state_weight = 1 / state_scale``, so
+        the loss that is lowered, float32 ``(pop,)``, is minus ``evaluate``'s fitness (NaN where that is ``-inf``)"""
+        return forest.optimize_simulation_constants(self.x0, self.u, self.target, self.scheme, self.dt, steps, damping,
+                                                    (1.0 / self.state_scale).to(torch.float32))
+
+    def optimize(self, forest: Forest) -> Forest:
+        """the forest with its constants tuned by ``const_opt_steps`` steps (the forest itself when that is 0)"""
+        return forest if self.const_opt_steps <= 0 else self.optimize_constants(forest, self.const_opt_steps)[0]
 
     @property
     def problem_dim(self):

@@ -424,9 +424,18 @@ class Forest:
         else:
             w = self._tuning_loss("SR_normal_equations", inputs, True, weights, None, None)[0]
             loss, normal = torch.ops.evogp_hip.tree_SR_weighted_normal_eq(*self._shape(inputs), value, ntype, size, inputs, labels, w)
+        return (loss,) + self._unpack_normal(normal)
+
+    def _unpack_normal(self, normal: Tensor):
+        """``(A, b, const_index)`` of a packed ``(pop, 44)`` row of normal equations (include/evogp_hip.h EVOGP_LM_NORMAL_WORDS)"""
         K = LM_MAX_CONSTS
         T = K * (K + 1) // 2
-        A, b = _symmetric(normal[:, :T], K), normal[:, T:].clone()
+        return _symmetric(normal[:, :T], K), normal[:, T:].clone(), self._optimised_const_index()
+
+    def _optimised_const_index(self) -> Tensor:
+        """``(pop, 8)`` int64: the node positions of every tree's optimised constants, -1 where it has fewer"""
+        value, ntype, size = self._tensors()
+        K = LM_MAX_CONSTS
         L = self.max_tree_len
         pos = torch.arange(L, device=value.device)[None, :]
         is_c = (ntype == NType.CONST) & (pos < size[:, :1].clamp(0, L))
@@ -434,7 +443,7 @@ class Forest:
         const_index = torch.where(first < L, first, -1)
         if L < K:
             const_index = torch.nn.functional.pad(const_index, (0, K - L), value=-1)
-        return loss, A, b, const_index
+        return const_index
 
     # ---- structural duplicates ---------------------------------------------------------------
     def structure_hash(self) -> Tensor:
@@ -821,6 +830,64 @@ class Forest:
         if tuple(target.shape) != want:
             raise ValueError(f"SR_simulation_loss with scheme {scheme!r} takes a target of shape {want}, but got {tuple(target.shape)}")
         return torch.ops.evogp_hip.tree_SR_simulation_loss(*self._tensors(), x0, u, target.contiguous().to(torch.float32), sid, float(dt))
+
+    def SR_simulation_sensitivities(self, x0: Tensor, u: Optional[Tensor] = None, steps: Optional[int] = None, scheme: str = "euler",
+                                    dt: float = 1.0):
+        """``(states, sens, const_index)``: ``SR_simulate``'s states, bit for bit, and ``sens`` float32 ``(pop, B, steps, S, 8)``, the
+        derivative of every state in the tree's OPTIMISED constants -- its first 8 CONST nodes in prefix order, at the node positions
+        ``const_index`` ``(pop, 8)`` (-1 where the tree has fewer; further constants are held fixed).  The sensitivities are carried
+        through every step and stage by a dual-number build of the interpreter inside ONE kernel (csrc/sr_simulate_sens.hip,
+        include/evogp_hip.h evogp_hip_sr_simulation_sensitivities).  Slots of absent constants are exactly 0; every slot
+        is NaN from the step a trajectory dies and for a malformed tree.  The materialising form, for inspection: more than 2 GiB of
+        sensitivities is an error of the op."""
+        x0, u, sid = self._simulation_args("SR_simulation_sensitivities", x0, u, steps, scheme)
+        states, sens = torch.ops.evogp_hip.tree_SR_simulation_sensitivities(*self._tensors(), x0, u, sid, float(dt))
+        return states, sens, self._optimised_const_index()
+
+    def _simulation_tuning_args(self, what: str, x0, u, target, scheme: str, state_weight):
+        """``(x0, u, target, state_weight, scheme id)`` as ``tree_SR_simulation_normal_eq`` takes them"""
+        device = self.batch_node_value.device
+        target = check_tensor(target, device)
+        if target.dim() < 2:
+            raise ValueError(f"{what} takes a target of shape (trajectories, steps[, state_len]), but got {tuple(target.shape)}")
+        x0, u, sid = self._simulation_args(what, x0, u, int(target.shape[1]), scheme)
+        want = (x0.shape[0], u.shape[1]) if scheme == "narx" else (x0.shape[0], u.shape[1], x0.shape[1])
+        if tuple(target.shape) != want:
+            raise ValueError(f"{what} with scheme {scheme!r} takes a target of shape {want}, but got {tuple(target.shape)}")
+        SC = 1 if scheme == "narx" else x0.shape[1]
+        if state_weight is None:
+            state_weight = torch.ones(SC, dtype=torch.float32, device=device)
+        state_weight = torch.as_tensor(state_weight, device=device).to(torch.float32).reshape(-1).contiguous()
+        if state_weight.shape[0] != SC:
+            raise ValueError(f"{what} takes {SC} state weights, but got {state_weight.shape[0]}")
+        return x0, u, target.contiguous().to(torch.float32), state_weight, sid
+
+    def SR_simulation_normal_equations(self, x0: Tensor, u: Optional[Tensor], target: Tensor, scheme: str = "euler", dt: float = 1.0,
+                                       state_weight=None):
+        """``(loss, A, b, const_index)``: the Gauss-Newton model of the free-run loss ``sum_s w_s loss_s`` in each tree's optimised
+        constants, in one pass that stores neither states nor sensitivities.  ``loss`` float64 ``(pop, SC)`` is ``SR_simulation_loss``'s,
+        bit for bit; with ``J`` the sensitivity of a scored state at a step and ``r`` its float32 residual, ``A = sum w_s J J^T / (B T)``
+        ``(pop, 8, 8)`` and ``b = sum w_s J r / (B T)`` ``(pop, 8)``, unpacked like ``SR_normal_equations``.  ``state_weight``: ``(SC,)``
+        float32 weights, default 1.  A tree with a dead trajectory or a malformed tree: NaN loss, zero ``A`` and ``b``."""
+        x0, u, target, w, sid = self._simulation_tuning_args("SR_simulation_normal_equations", x0, u, target, scheme, state_weight)
+        loss, _, normal = torch.ops.evogp_hip.tree_SR_simulation_normal_eq(*self._tensors(), x0, u, target, w, sid, float(dt))
+        return (loss,) + self._unpack_normal(normal)
+
+    def optimize_simulation_constants(self, x0: Tensor, u: Optional[Tensor], target: Tensor, scheme: str = "euler", dt: float = 1.0,
+                                      steps: int = 3, damping: float = 1e-3, state_weight=None):
+        """``(forest, loss)``: ``steps`` Levenberg-Marquardt iterations on every tree's first 8 constants under SIMULATION fitness -- the
+        loss ``sum_s w_s loss_s`` of ``SR_simulation_normal_equations`` as float32 ``(pop,)`` -- with ``optimize_constants``'s accept /
+        reject rule (``tree_SR_lm_step``): a step is kept only if it lowers the tree's loss, so no tree's loss rises; a tree whose
+        simulation dies keeps its constants.  Two launches per step, no host synchronisation; multi-output forests (several states)
+        are served.  Returns a new Forest that differs from this one only in the optimised constants."""
+        assert steps >= 0, f"steps should be >= 0, but got {steps}"
+        x0, u, target, w, sid = self._simulation_tuning_args("optimize_simulation_constants", x0, u, target, scheme, state_weight)
+        hip = torch.ops.evogp_hip
+        evaluate = lambda *tree: hip.tree_SR_simulation_normal_eq(*tree, x0, u, target, w, sid, float(dt))[1:]  # noqa: E731
+        value, loss = self._tune(steps, damping, evaluate, hip.tree_SR_lm_step)
+        forest = Forest(self.input_len, self.output_len, value, self.batch_node_type.clone(), self.batch_subtree_size.clone(),
+                        func_mask=self.func_mask)
+        return forest, loss
 
     # ---- rank statistics: Spearman correlation and ROC-AUC ---------------------------------------
     def _rank_call(self, inputs: Tensor, payload: Tensor, segs: RankSegments, metric: str, want: str):

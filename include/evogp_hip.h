@@ -1178,6 +1178,48 @@ int evogp_hip_sr_simulation_loss(unsigned pop_size, unsigned gp_len, unsigned tr
                                  const int16_t *size, const float *x0, const float *u, const float *target, double *loss_out,
                                  void *workspace, evogp_stream_t stream);
 
+/* Constant tuning under simulation fitness (no counterpart in the reference; csrc/sr_simulate_sens.hip): the forward
+ * sensitivities of the simulation above in the tree's OPTIMISED constants -- its first nc <= K = EVOGP_LM_MAX_CONSTS CONST nodes (raw type
+ * word == 1) of the clamped live prefix in prefix order, the nodes evogp_hip_sr_lm_step addresses; further constants are held fixed.
+ * THE DEFINITION (tests/simulate_sens_ref.py restates it): s[v][k] = d x_v / d c_k starts at 0 and is carried through every stage by ONE
+ * evaluation of the tree on dual numbers (value, tangent): state variable v carries the stage's s[v][k], an input variable 0, the CONST node of
+ * constant k carries 1 and any other CONST 0.  Values are evogp_hip_sr_simulate's, bit for bit.  Tangents, every operation rounded
+ * separately (float32, no contraction), with (pa, pb) resp. pa the adjoint rules of DESIGN.md's "Constant gradients" table at g = 1:
+ *     binary  t_r = pa * t_a + pb * t_b        unary  t_r = pa * t_a        IF  the tangent of the branch taken (the condition's is dropped)
+ *     ADD  t_a + t_b     SUB  t_a - t_b     NEG  -t_a     LT GT LE GE and unknown ids  0
+ * A multi-output tree accumulates duals as values (outs[o] += r, the LAST operand's dual goes to the parent).  With k' the tangent of f:
+ *     map    s+ = k'                      euler  s+ = s + dt * k'                 narx  s+[0] = k', s+[v] = s[v-1]
+ *     rk4    stage inputs s + h * k' (h = h2, h2, dt), sum' = ((k1' + 2 * k2') + 2 * k3') + k4', s+ = s + h6 * sum'
+ *   evogp_hip_sr_simulation_sensitivities   states_out f32 [pop][B][T][S] (evogp_hip_sr_simulate's bits) and sens_out f32 [pop][B][T][S][K]:
+ *                                  s after step t; slots k >= nc are exactly 0; every slot is NaN from the step a trajectory dies, and
+ *                                  everywhere for a malformed tree.  EVOGP_E_BADARG when sens_out would take more than 2 GiB.
+ *   evogp_hip_sr_simulation_normal_eq   the Gauss-Newton model of L = sum_s w_s loss_s without the arrays above: loss64_out f64 [pop][SC] is
+ *                                  evogp_hip_sr_simulation_loss's, bit for bit; loss_out f32 [pop] = (float) sum_s (double)w_s * loss64[s]
+ *                                  in index order; normal_out f32 [pop][EVOGP_LM_NORMAL_WORDS]: the upper triangle of
+ *                                  A_ij = sum w_s J_i J_j / (B T), then b_i = sum w_s J_i r / (B T), over b, t and the scored states s < SC,
+ *                                  J_i = s+[s][i], r = x_s - target_s in float32, w_s = state_weight[s] f32 [SC].  Per term
+ *                                  wJ = w_s * J_i, A_ij += wJ * J_j, b_i += wJ * r in float32: a lane adds the terms of its trajectory in
+ *                                  (t, s) order, a tile's 64 lanes are added by the fixed butterfly, the tiles in index order, the sum is
+ *                                  divided by (float)(B T).  Rows and columns >= nc are exactly 0.  A tree with a dead trajectory or a
+ *                                  malformed tree: NaN in every loss, a zero row.  A tree whose states stay finite and whose sensitivities do
+ *                                  not hands out the non-finite words as they come (evogp_hip_sr_lm_step does not move on them).
+ * Launches (caller's stream, no host synchronisation, no float atomics): the transposition; the dual-number register interpreter (LEAN, then
+ * FULL over the trees with a transcendental function or pow), one workgroup per tree, ceil(nc / 4) interpretations per stage (one plain
+ * interpretation for nc = 0), the sensitivities in LDS; a one-wave build for the trees too deep for 16 registers.  The same bits whichever
+ * build takes a tree, from run to run, and whatever population the tree stands in.
+ * workspace: evogp_hip_sr_simulation_sens_workspace_bytes(...) bytes (no zeroing needed).  Errors before any launch as evogp_hip_sr_simulate. */
+int evogp_hip_sr_simulation_sens_workspace_bytes(unsigned pop_size, unsigned gp_len, unsigned trajectories, unsigned steps, unsigned state_len,
+                                                 unsigned input_len, int scheme, int with_target, unsigned long long *bytes);
+int evogp_hip_sr_simulation_sensitivities(unsigned pop_size, unsigned gp_len, unsigned trajectories, unsigned steps, unsigned state_len,
+                                          unsigned input_len, int scheme, float dt, float h2, float h6, const float *value, const int16_t *type,
+                                          const int16_t *size, const float *x0, const float *u, float *states_out, float *sens_out,
+                                          void *workspace, evogp_stream_t stream);
+int evogp_hip_sr_simulation_normal_eq(unsigned pop_size, unsigned gp_len, unsigned trajectories, unsigned steps, unsigned state_len,
+                                      unsigned input_len, int scheme, float dt, float h2, float h6, const float *value, const int16_t *type,
+                                      const int16_t *size, const float *x0, const float *u, const float *target,
+                                      const float *state_weight /* [SC] */, double *loss64_out, float *loss_out, float *normal_out,
+                                      void *workspace, evogp_stream_t stream);
+
 /* Engine-owned device memory (no counterpart in the reference, whose kernels keep a private copy of the tree per thread,
  * forward.cu:284-287).  evogp_hip_sr_fitness compiles every tree into PROGRAM RECORDS that its interpreter kernel reads: one
  * buffer per device, allocated with hipMalloc on first use, grown on demand (never while a HIP graph is being captured),
