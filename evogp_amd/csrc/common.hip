@@ -97,20 +97,24 @@ struct CounterRing {
 };
 static std::vector<CounterRing> g_ring[64];
 
-__global__ void zero_words_kernel(unsigned *p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+__global__ void fill_words_kernel(unsigned *p, unsigned word, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = word;
 }
 
-hipError_t zero_words_async(void *ptr, size_t nwords, hipStream_t stream) {
+hipError_t fill_words_async(void *ptr, unsigned word, size_t nwords, hipStream_t stream) {
+    const unsigned byte = word & 0xFFu;
+    if (word != byte * 0x01010101u) return hipErrorInvalidValue;   // one byte repeated (callers fill with 0 or ~0): what a memset can write
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    if (!capturing) return hipMemsetAsync(ptr, 0, nwords * sizeof(unsigned), stream);
+    if (!capturing) return hipMemsetAsync(ptr, (int)byte, nwords * sizeof(unsigned), stream);
     size_t blocks = (nwords + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned *)ptr, nwords);
+    hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned *)ptr, word, nwords);
     return hipGetLastError();
 }
+
+hipError_t zero_words_async(void *ptr, size_t nwords, hipStream_t stream) { return fill_words_async(ptr, 0u, nwords, stream); }
 
 unsigned *acquire_counter(hipStream_t stream, hipError_t *err) {
     int dev = 0;

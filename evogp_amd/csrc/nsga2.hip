@@ -335,7 +335,7 @@ extern "C" int evogp_hip_pareto_rank(unsigned pop, unsigned cx_bound, const floa
     if (g_nsga_stop == 2) return EVOGP_OK;
 
     // 3. the fronts
-    if ((e = hipMemsetAsync(w.fen, 0xFF, ((size_t)pop + 1u) * 4, stream)) != hipSuccess) return (int)e;
+    if ((e = fill_words_async(w.fen, 0xFFFFFFFFu, (size_t)pop + 1u, stream)) != hipSuccess) return (int)e;
     NsgaChain ch{w.k32_b, w.f2, w.t2, w.gid, w.bend, w.fen, w.front_u, front, pop};
     hipLaunchKernelGGL(nsga_chain_kernel, dim3(1), dim3(kNsgaChainThreads), 0, stream, ch);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
