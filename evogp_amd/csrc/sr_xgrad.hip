@@ -31,7 +31,7 @@
 //                    ballot and popcount per tile, integer sums per wave, the waves in wave order;
 //   a malformed tree has every column NaN and viol = D.
 // No float atomics, nothing synchronises with the host: the same inputs give the same bits.
-#include "sr_adjoint.hpp"
+#include "sr_hyperdual.hpp"
 #include "sr_moments.hpp"
 
 namespace evogp {
@@ -265,6 +265,13 @@ __global__ __launch_bounds__(kTapeMaxWaves * 64) void sr_xgrad_kernel(XgradParam
 
 using namespace evogp;
 
+// Does wrt hold a pair code (EVOGP_XGRAD_PAIR | a << 15 | b)?  Then the call is sr_hessian.hip's: second derivatives.
+static bool xgrad_has_pair(unsigned n_wrt, const int *wrt) {
+    for (unsigned k = 0; k < n_wrt; ++k)
+        if (wrt[k] >= 0 && (wrt[k] & EVOGP_XGRAD_PAIR)) return true;
+    return false;
+}
+
 // the checks both entry points share, in the order of evogp_hip_sr_gradient: bad argument, null pointer, out_len
 static int xgrad_check(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len, unsigned n_wrt,
                        const int *wrt) {
@@ -272,6 +279,7 @@ static int xgrad_check(unsigned pop_size, unsigned data_points, unsigned gp_len,
         out_len == 0 || pop_size > 0x7FFFFFFFu || data_points > 0x7FFFFFFFu || n_wrt == 0 || n_wrt > (unsigned)kXgradMaxVars)
         return EVOGP_E_BADARG;
     if (!wrt) return EVOGP_E_NULLPTR;
+    if (xgrad_has_pair(n_wrt, wrt)) return 0;   // pair codes: hessian_run (sr_hessian.hip) checks them, a mix with plain entries included
     for (unsigned k = 0; k < n_wrt; ++k) {
         if (wrt[k] < 0 || (unsigned)wrt[k] >= var_len) return EVOGP_E_BADARG;
         for (unsigned j = 0; j < k; ++j)
@@ -299,6 +307,9 @@ extern "C" int evogp_hip_sr_input_gradient(unsigned pop_size, unsigned data_poin
     if (const int rc = xgrad_check(pop_size, data_points, gp_len, var_len, out_len, n_wrt, wrt)) return rc;
     if (!value || !type || !size || !variables || !pred || !dpred) return EVOGP_E_NULLPTR;
     if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    if (xgrad_has_pair(n_wrt, wrt))
+        return hessian_run(pop_size, data_points, gp_len, var_len, value, type, size, variables, nullptr, nullptr, nullptr, nullptr, n_wrt, wrt,
+                           pred, dpred, nullptr, nullptr, (hipStream_t)stream_);
     XgradParams p{};
     p.value = value; p.type = type; p.size = size; p.X = variables; p.pred = pred; p.dpred = dpred;
     p.pop = (int)pop_size; p.D = (int)data_points; p.gp_len = (int)gp_len; p.var_len = (int)var_len;
@@ -312,6 +323,9 @@ extern "C" int evogp_hip_sr_derivative_loss(unsigned pop_size, unsigned data_poi
     if (const int rc = xgrad_check(pop_size, data_points, gp_len, var_len, out_len, n_wrt, wrt)) return rc;
     if (!value || !type || !size || !variables || !labels || !loss || !violations) return EVOGP_E_NULLPTR;
     if (out_len != 1) return EVOGP_E_UNSUPPORTED;
+    if (xgrad_has_pair(n_wrt, wrt))
+        return hessian_run(pop_size, data_points, gp_len, var_len, value, type, size, variables, labels, dlabels, dmin, dmax, n_wrt, wrt,
+                           nullptr, nullptr, loss, violations, (hipStream_t)stream_);
     XgradParams p{};
     p.value = value; p.type = type; p.size = size; p.X = variables; p.y = labels; p.dy = dlabels; p.dmin = dmin; p.dmax = dmax;
     p.loss = loss; p.viol = violations;

@@ -663,7 +663,21 @@ XgradCall check_xgrad(const char *op, const Tensor &value, const Tensor &type, c
     c.D = variables.size(0), c.var_len = variables.size(1), c.V = (int64_t)wrt.size();
     check_tensor(variables, {c.D, c.var_len}, "variables", c.f.dev, at::kFloat);
     TORCH_CHECK(c.V >= 1 && c.V <= EVOGP_XGRAD_MAX_VARS, op, ": wrt must hold 1 to ", EVOGP_XGRAD_MAX_VARS, " variables, but got ", c.V);
+    // a pair code EVOGP_XGRAD_PAIR | a << 15 | b asks for d^2 / dx_a dx_b; one call holds plain variables or pair codes
+    const auto is_pair = [](int64_t v) { return v >= 0 && (v >> 30) == 1; };
+    int64_t n_pairs = 0;
+    for (int64_t k = 0; k < c.V; ++k) n_pairs += is_pair(wrt[k]) ? 1 : 0;
+    TORCH_CHECK(n_pairs == 0 || n_pairs == c.V, op, ": wrt must hold plain variables or pair codes, not both, but ", n_pairs, " of its ", c.V,
+                " entries are pair codes");
     for (int64_t k = 0; k < c.V; ++k) {
+        if (n_pairs) {
+            const int64_t a = (wrt[k] >> 15) & 0x7FFF, b = wrt[k] & 0x7FFF;
+            TORCH_CHECK(a <= b && b < c.var_len, op, ": wrt[", k, "] is the pair code of (", a, ", ", b, "), but a pair needs 0 <= a <= b < ",
+                        c.var_len);
+            for (int64_t j = 0; j < k; ++j) TORCH_CHECK(wrt[j] != wrt[k], op, ": wrt holds the pair (", a, ", ", b, ") twice");
+            c.wrt[k] = (int)wrt[k];
+            continue;
+        }
         TORCH_CHECK(wrt[k] >= 0 && wrt[k] < c.var_len, op, ": wrt[", k, "] must be in range [0, ", c.var_len, "), but got ", wrt[k]);
         for (int64_t j = 0; j < k; ++j) TORCH_CHECK(wrt[j] != wrt[k], op, ": wrt holds variable ", wrt[k], " twice");
         c.wrt[k] = (int)wrt[k];

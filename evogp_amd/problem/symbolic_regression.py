@@ -31,7 +31,7 @@ class SymbolicRegression(BaseProblem):
                  loss_param: Optional[float] = None, sample_weights: Optional[Tensor] = None,
                  validation_mask: Optional[Tensor] = None, const_opt_loss: Optional[str] = None,
                  scaling_loss: Optional[str] = None, derivative_labels: Optional[Tensor] = None, derivative_wrt=None,
-                 derivative_weight=1.0, sampled_monotonic=None, intron_removal_every: int = 0):
+                 derivative_weight=1.0, sampled_monotonic=None, intron_removal_every: int = 0, sampled_convex=None):
         """``const_opt_steps`` > 0 (no counterpart in the reference): ``optimize`` tunes every tree's constants by that many steps of
         ``Forest.optimize_constants``, and StandardPipeline scores the optimised forest (Lamarckian).  ``const_opt_method``:
         ``"descent"`` (gradient descent with steps of ``const_step_size``) or ``"lm"`` (Levenberg-Marquardt; MSE, single-output).
@@ -122,6 +122,12 @@ class SymbolicRegression(BaseProblem):
         leaves its range, or is NaN, on any datapoint gets NaN from ``evaluate`` and -inf from ``scores`` (the optimistic companion
         of ``monotonic``; the two may be combined).  Alone it only masks: the fitness of the other trees is the plain one, bit for
         bit.  Its variables are appended to ``derivative_wrt`` where that lacks them (they carry no label and no weight).
+        ``sampled_convex`` (sampled curvature constraints; single-output problems): ``{variable | (a, b): +1 | -1 | (lo, hi)}`` holds the
+        second derivative d^2 tree / dx_a dx_b (a variable ``a`` means ``(a, a)``; at most 8 pairs) to [0, inf] (+1: convex in the
+        variable), [-inf, 0] (-1: concave) or [lo, hi] on every datapoint: a tree with a violating or NaN row is masked as under
+        ``sampled_monotonic`` (``Forest.SR_curvature_loss``; ``curvature_loss(forest)`` returns its columns).  It may be combined with
+        ``sampled_monotonic``; the second derivatives are a pass of their own, so the two together cost two passes over the data.
+        ``ValueError`` together with ``multigene`` or labels of more than one column.
 
         ``intron_removal_every`` = k > 0 (single-output problems): every k-th call of ``optimize`` first takes the semantic introns out
         of the forest (``Forest.remove_introns`` on the datapoints: nodes that take the value of one of their own descendants on every
@@ -276,6 +282,20 @@ class SymbolicRegression(BaseProblem):
                 self._loss_weights = w[None, :].contiguous()
 
         self._init_derivatives(derivative_labels, derivative_wrt, derivative_weight, sampled_monotonic)
+        self.sampled_convex = None
+        if sampled_convex is not None:
+            if self.multigene:
+                raise ValueError("multigene cannot be combined with sampled_convex: that pass works on single-output trees")
+            self._one_label_column("sampled_convex")
+            num_inputs = self.datapoints.shape[1]
+            keys, bounds, signs = parse_monotonic(sampled_convex)
+            pairs = [(k, k) if isinstance(k, int) else tuple(sorted(k)) if isinstance(k, (tuple, list)) and len(k) == 2 else None for k in keys]
+            if not pairs or None in pairs or len(set(pairs)) != len(pairs) or len(pairs) > 8 or not all(
+                    isinstance(v, int) and 0 <= v < num_inputs for q in pairs for v in q):
+                raise ValueError(f"sampled_convex should hold 1 to 8 distinct variables or (a, b) pairs of variables in 0 .. {num_inputs - 1}, "
+                                 f"but got {list(keys)}")
+            self.sampled_convex = {q: s if s else b for q, b, s in zip(pairs, bounds, signs)}
+            self._constrained = True
 
     def _init_derivatives(self, derivative_labels, derivative_wrt, derivative_weight, sampled_monotonic):
         """the derivative options, checked on the host: ``_deriv_wrt`` (the variables of one ``SR_derivative_loss`` call),
@@ -338,6 +358,13 @@ class SymbolicRegression(BaseProblem):
         if not self._deriv_wrt:
             raise ValueError("this problem has neither derivative_labels nor sampled_monotonic")
         return forest.SR_derivative_loss(self.datapoints, self.labels, self.derivative_labels, self._deriv_wrt, self.sampled_monotonic)
+
+    def curvature_loss(self, forest: Forest):
+        """``(loss (pop, 1 + P), violations (pop, P))``: ``Forest.SR_curvature_loss`` on this problem's data under its
+        ``sampled_convex`` bounds, the pairs in the dictionary's order (no labels: the loss columns are mean squared curvatures)"""
+        if self.sampled_convex is None:
+            raise ValueError("this problem has no sampled_convex")
+        return forest.SR_curvature_loss(self.datapoints, self.labels, list(self.sampled_convex), None, self.sampled_convex)
 
     def _one_label_column(self, feature: str, claim: str = "works on single-output problems only"):
         if self.labels.dim() != 2 or self.labels.shape[1] != 1:
@@ -413,6 +440,9 @@ class SymbolicRegression(BaseProblem):
             pending, self._deriv_pending = self._deriv_pending, None   # what _loss has just computed for this very forest
             viol = pending[1] if pending is not None and pending[0] is forest else self.derivative_loss(forest)[1]
             obeys = (viol[:, cols] == 0).all(1).to(fitness.device)
+            mask = obeys if mask is None else mask & obeys
+        if self.sampled_convex is not None:   # (a pass of its own: second derivatives)
+            obeys = (self.curvature_loss(forest)[1] == 0).all(1).to(fitness.device)
             mask = obeys if mask is None else mask & obeys
         counted = []   # (violations, penalty) of the passes that count violations
         if self.input_units is not None:

@@ -67,6 +67,7 @@ RANK_MAX_PAYLOAD = 16384     # largest payload word of SR_rank_stats: a doubled 
 RANK_METRICS = {"spearman": 0, "auc": 1}  # include/evogp_hip.h EVOGP_RANK_*
 BACKPROP_MAX_LIBRARY = 1024  # library members per SR_backprop_match call (include/evogp_hip.h EVOGP_BACKPROP_MAX_LIB)
 XGRAD_MAX_VARS = 8  #variables per SR_input_gradients / SR_derivative_loss call (include/evogp_hip.h EVOGP_XGRAD_MAX_VARS)
+XGRAD_PAIR = 1 << 30  # a wrt entry XGRAD_PAIR | a << 15 | b of the two ops names d^2 / dx_a dx_b (include/evogp_hip.h EVOGP_XGRAD_PAIR)
 LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2, "pinball": 3, "logcosh": 4}  # include/evogp_hip.h EVOGP_LOSS_*
 _WRAP_FUNCS = (1 << 1) | (1 << 3)  # Func.ADD, Func.MUL: the two nodes apply_scaling puts on top of a tree
 _SR_MODES = {"hybrid parallel": 0, "data parallel": 1, "tree parallel": 2, "auto": 4}  # forest.py:340-347
@@ -1361,6 +1362,73 @@ class Forest:
                 lo[idx.index(v)], hi[idx.index(v)] = a, b
             dmin, dmax = torch.tensor(lo, dtype=torch.float32).to(dev), torch.tensor(hi, dtype=torch.float32).to(dev)
         return torch.ops.evogp_hip.tree_SR_derivative_loss(*self._tensors(), inputs, labels, dlabels, idx, dmin, dmax)
+
+    # ---- second input derivatives on the data --------------------------------------------------------
+    def _hessian_pairs(self, what: str, pairs, extra=()):
+        """``pairs`` (an int ``a`` for ``(a, a)``, a pair, or a list of them) and the pairs of ``extra`` it lacks as a list of canonical
+        ``(a, b)``, ``a <= b``: 1 to ``XGRAD_MAX_VARS`` distinct pairs of variables of this forest; ``ValueError`` otherwise"""
+        self._single_output(what, ValueError)
+
+        def canon(q):
+            q = (q, q) if isinstance(q, int) and not isinstance(q, bool) else q
+            if not (isinstance(q, (tuple, list)) and len(q) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in q)):
+                raise ValueError(f"{what}: a pair should be a variable or a (a, b) tuple of variables, but got {q!r}")
+            if not all(0 <= v < self.input_len for v in q):
+                raise ValueError(f"{what}: pair {tuple(q)} names a variable outside 0 .. {self.input_len - 1}")
+            return (min(q), max(q))
+
+        if isinstance(pairs, int) or (isinstance(pairs, tuple) and len(pairs) == 2 and all(isinstance(v, int) for v in pairs)):
+            pairs = [pairs]
+        out = [canon(q) for q in pairs]
+        if len(set(out)) != len(out):
+            raise ValueError(f"{what}: pairs names a second derivative twice: {out}")
+        out = out + [q for q in dict.fromkeys(canon(e) for e in extra) if q not in out]
+        if not 1 <= len(out) <= XGRAD_MAX_VARS:
+            raise ValueError(f"{what}: {len(out)} pairs are requested, but one call takes 1 to {XGRAD_MAX_VARS}")
+        return out
+
+    def SR_input_hessians(self, inputs: Tensor, pairs):
+        """``(pred, hess)``: ``pred`` (pop, D) the prediction of every tree on every row of ``inputs`` (D, input_len) -- the bits of
+        ``SR_input_gradients`` -- and ``hess`` (pop, D, P) its second derivative d^2 tree / dx_a dx_b at that row for ``pairs[k] = (a, b)``
+        (an int ``a`` means ``(a, a)``; 1 to 8 pairs, stored with ``a <= b``, distinct after that).  Forward mode on hyper-dual numbers in
+        the register interpreter (csrc/sr_hessian.hip, no tape): reached through ``tree_SR_input_gradient`` with ``wrt`` holding the pair
+        codes ``XGRAD_PAIR | a << 15 | b``.  ``hess`` is a permuted view of the kernel's (P, pop, D) array.  A pair whose variables the
+        tree does not both hold has exactly +0.0; a malformed tree NaN everywhere.  Unlike a first derivative, a second derivative is
+        NaN only where the branch taken makes it so.  ``ValueError`` before any launch for a bad pair or a multi-output forest."""
+        codes = [XGRAD_PAIR | a << 15 | b for a, b in self._hessian_pairs("SR_input_hessians", pairs)]
+        inputs = check_tensor(inputs, self.batch_node_value.device)
+        assert inputs.dim() == 2 and inputs.shape[1] == self.input_len, (
+            f"inputs shape[1] should be {self.input_len}, but got {tuple(inputs.shape)}")
+        pred, dpred = torch.ops.evogp_hip.tree_SR_input_gradient(*self._tensors(), inputs.contiguous().to(torch.float32), codes)
+        return pred, dpred.permute(1, 2, 0)
+
+    def SR_curvature_loss(self, inputs: Tensor, labels: Tensor, pairs, d2labels: Optional[Tensor] = None, bounds=None):
+        """``(loss, violations)`` without a (pop, D) array (csrc/sr_hessian.hip, no host synchronisation): ``loss`` (pop, 1 + P) float32 --
+        column 0 the mean squared error of the prediction against ``labels`` (D, 1), column 1 + k that of the second derivative
+        ``pairs[k]`` (``SR_input_hessians``) against ``d2labels[:, k]`` (``d2labels`` (D, P); None: zeros); ``violations`` (pop, P) int32 --
+        the rows on which that second derivative is NaN or outside its range in ``bounds`` = ``{pair: +1 | -1 | (lo, hi)}``
+        (``parse_monotonic``'s values: +1 is [0, inf], convex in x_a for the pair (a, a); -1 concave); a key is a pair or a variable
+        ``a`` for ``(a, a)``.  Pairs of ``bounds`` that ``pairs`` lacks are appended; the columns follow that order.  A column is NaN
+        when a row term is not finite; a malformed tree has NaN columns and ``D`` violations.  Sums are float64 in a fixed order:
+        bit-identical from run to run.  ``ValueError`` as for ``SR_input_hessians``."""
+        keys, ranges, _ = parse_monotonic(bounds or {})
+        idx = self._hessian_pairs("SR_curvature_loss", pairs, keys)
+        inputs, labels = self._sr_data(inputs, labels)
+        dev, P = self.batch_node_value.device, len(idx)
+        if d2labels is not None:
+            d2labels = check_tensor(d2labels, dev)
+            if d2labels.shape != (inputs.shape[0], P):
+                raise ValueError(f"d2labels should have shape ({inputs.shape[0]}, {P}): one column per requested pair {idx}, "
+                                 f"but got {tuple(d2labels.shape)}")
+            d2labels = d2labels.contiguous().to(torch.float32)
+        dmin = dmax = None
+        if keys:
+            lo, hi = [float("-inf")] * P, [float("inf")] * P
+            for q, (a, b) in zip(self._hessian_pairs("SR_curvature_loss", list(keys)), ranges):
+                lo[idx.index(q)], hi[idx.index(q)] = a, b
+            dmin, dmax = torch.tensor(lo, dtype=torch.float32).to(dev), torch.tensor(hi, dtype=torch.float32).to(dev)
+        codes = [XGRAD_PAIR | a << 15 | b for a, b in idx]
+        return torch.ops.evogp_hip.tree_SR_derivative_loss(*self._tensors(), inputs, labels, d2labels, codes, dmin, dmax)
 
     # ---- semantic backpropagation --------------------------------------------------------------------
     def _backprop_args(self, what: str, inputs: Tensor, labels: Tensor, positions: Tensor):

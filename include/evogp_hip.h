@@ -833,8 +833,20 @@ int evogp_hip_sr_weighted_scaling(unsigned pop_size, unsigned data_points, unsig
  * EVOGP_E_BADARG before any launch: a zero size, gp_len > 1024, var_len >= 2^28, n_wrt outside 1 .. 8, an entry of wrt out of range or
  * repeated.  Then a NULL pointer other than dlabels, dmin, dmax: EVOGP_E_NULLPTR; then out_len != 1: EVOGP_E_UNSUPPORTED.
  * One launch each, no float atomics: bit-identical from run to run.  Rows of more than 64 nodes use the per-stream tape buffer of
- * evogp_hip_sr_gradient, under the same rules.  Any data_points and var_len; the outputs must not alias the inputs or one another. */
+ * evogp_hip_sr_gradient, under the same rules.  Any data_points and var_len; the outputs must not alias the inputs or one another.
+ *
+ * SECOND derivatives (csrc/sr_hessian.hip): an entry of wrt may instead be a PAIR CODE
+ * EVOGP_XGRAD_PAIR | a << 15 | b with 0 <= a <= b < var_len, which names h_{k,d} = d^2 tree / dx_a dx_b at X[d].  One call holds plain
+ * entries or pair codes, never both.  With pair codes both entry points keep their arguments and layouts, h_{k,d} standing where g_{k,d}
+ * stands above (dpred, the loss columns against dlabels, the violations against dmin / dmax: [0, +inf] asks for convexity in x_a when
+ * a == b), p_d and loss[t][0]'s terms are the same bits, and the sums are taken in an order fixed by data_points, var_len and the device.
+ * h is computed in forward mode on hyper-dual numbers (v, t_a, t_b, t_ab) by the rules of csrc/sr_hyperdual.hpp, every float32 operation
+ * rounded on its own; a pair whose variables the tree does not both hold has +0.0f exactly; an IF contributes the branch it took and
+ * max / min the winning operand only, so h is NaN only where the path taken makes it so (unlike g above).  A malformed tree: as above.
+ * EVOGP_E_BADARG: a mix of plain entries and pair codes, a > b, b >= var_len, bits 31 or 30 not 0 1, a repeated code.  Three launches,
+ * no float atomics; the per-stream tape buffer holds a word per tree and the operand stacks of trees deeper than 16 entries. */
 #define EVOGP_XGRAD_MAX_VARS 8
+#define EVOGP_XGRAD_PAIR (1 << 30)
 int evogp_hip_sr_input_gradient(unsigned pop_size, unsigned data_points, unsigned gp_len, unsigned var_len, unsigned out_len,
                                 const float *value, const int16_t *type, const int16_t *size, const float *variables, unsigned n_wrt,
                                 const int *wrt /* host */, float *pred /* [pop][D] */, float *dpred /* [n_wrt][pop][D] */,
